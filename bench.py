@@ -126,6 +126,41 @@ def algorithmic_bytes_per_iter(n, w=8, m=M_LBFGS, n_al=2, n_fb=1, p_al=6):
     return w * n * ((8 * m + 1) + p_al * n_al + 4 * n_fb + 8)
 
 
+DUMP_SAMPLE = 1 << 20          # --dump-outputs: at most this many elements per vector (8 MiB each in fp64)
+DUMP_SEED = 20240607
+
+
+def dump_sample_index(n):
+    """The fixed, seeded sample of [0, n) that --dump-outputs writes of a long vector (all of it when it is short)."""
+    if n <= DUMP_SAMPLE:
+        return np.arange(n, dtype=np.int64)
+    return np.unique(np.random.default_rng(DUMP_SEED).integers(0, n, size=DUMP_SAMPLE, dtype=np.int64))
+
+
+def dump_outputs(out_dir, prob, n_global=None, lo=0, grp=None, rank=0):
+    """--dump-outputs DIR: what a caller of the timed path receives after its last step — the solution z (what
+    bz_panoc_finish returns), the iterate x, the fixed-point residual res and the solver's scalars — as DIR/<name>.npy.
+    Vectors longer than DUMP_SAMPLE are written at the sample `dump_sample_index` picks (its global indices in
+    index.npy).  Sharded runs: every rank reads its own block, rank 0 writes the concatenation in global order."""
+    n_global = prob.n if n_global is None else n_global
+    idx = dump_sample_index(n_global)
+    mine = idx[(idx >= lo) & (idx < lo + prob.n)] - lo
+    arrays = {}
+    for name in ("z", "x", "res"):
+        v = np.ascontiguousarray(prob.panoc_vector(name)[mine])
+        if grp is not None:
+            v = np.concatenate([np.frombuffer(b, dtype=v.dtype) for b in grp.allgather(v.tobytes())])
+        arrays[name] = v
+    if rank != 0:
+        return
+    arrays["index"] = idx.astype(np.float64)
+    arrays["scalars"] = np.array([prob.panoc_scalars()[k] for k in prob.SCALAR_NAMES], dtype=np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    note(f"outputs of the last timed step written to {out_dir}: " + ", ".join(f"{k}{list(a.shape)}" for k, a in arrays.items()))
+
+
 def note(msg):
     """progress line on stderr (a long silent run looks hung to the GPU box's watchdog)"""
     print(f"[bench {time.strftime('%H:%M:%S')}] {msg}", file=sys.stderr, flush=True)
@@ -540,6 +575,8 @@ def side_workload(args):
                                   "achieved": round(prof[k]["timed_bytes"] / prof[k]["timed_ms"] / 1e6, 1), "form": prof[k]["form"]}
                               for k in ("gemv", "k_gemv_t_mfma") if prof[k]["timed_launches"] and k != roof["category"]}
     rep = repeat_blocks(elapsed, args.steps, lambda: (fresh(), run_block(prob, args.steps, None))[1])
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prob)
     cpu = None
     if not args.no_cpu_baseline:
         note(f"{args.workload}: cpu baseline on the numpy oracle")
@@ -673,6 +710,10 @@ def main():
                     help="N > 1: do not create the RCCL communicator (p2p mailboxes only, checked for rank agreement "
                          "instead of against RCCL).  With BZ_BENCH_SAME_GPU=1 (all ranks on device 0) this rehearses "
                          "the N > 1 path on a one-GPU box, where RCCL refuses two ranks on one device")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the timed path computed in its last step (z, x, res: a fixed "
+                         "seeded sample of at most %d elements each, with its indices; the solver's scalars) as DIR/<name>.npy"
+                         % DUMP_SAMPLE)
     args = ap.parse_args()
 
     # N > 1 without a launcher: start the N ranks ourselves, BEFORE anything touches the GPU (or loads the library)
@@ -1021,6 +1062,8 @@ def main():
         repeats = {"blocks": len(ts), "ms_per_step_median": round(msb[len(msb) // 2], 5), "ms_per_step_min": round(msb[0], 5),
                    "ms_per_step_max": round(msb[-1], 5), "value_median": round(1e3 / msb[len(msb) // 2], 3),
                    "note": "the K-step block lasts < 100 ms: repeated from a fresh solve with the same warm-up; `value` is block 1"}
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, prob, n, lo_i, grp, rank)
     prob.close()
     # N > 1: north_star names RCCL for the scalar reductions — when the timed transport is the p2p mailboxes, the
     # RCCL all-gather transport is timed as well and printed beside it

@@ -61,3 +61,22 @@ def test_als_line_small():
     d = _run("--workload", "als", "--size", "300000", "--steps", "20", "--warmup", "4")
     _check_common(d, 20, 4)
     assert d["config"]["workload"].startswith("als") and d["cpu_baseline"]["kind"] == "port"
+
+
+@pytest.mark.timeout(900)
+def test_dump_outputs_are_reproducible_and_follow_steps(tmp_path):
+    """--dump-outputs: two runs with the same arguments write the same arrays (same inputs, same iterates), and the
+    iteration count the solver reports is the warm-up plus exactly --steps timed steps."""
+    import numpy as np
+    args = ("--size", "400000", "--steps", "30", "--warmup", "5", "--no-cpu-baseline", "--no-extras")
+    outs = []
+    for rep in ("a", "b"):
+        d = _run(*args, "--dump-outputs", str(tmp_path / rep))
+        assert d["steps"] == 30
+        outs.append({f[:-4]: np.load(str(tmp_path / rep / f)) for f in os.listdir(tmp_path / rep)})
+    a, b = outs
+    assert set(a) == {"z", "x", "res", "index", "scalars"} and set(a) == set(b)
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]), k
+    assert len(a["z"]) == len(a["index"]) and np.all(np.isfinite(a["z"]))
+    assert a["scalars"][0] == 1 + 5 + 30                  # k: the initial state (k = 1), then warm-up + timed steps
