@@ -11,6 +11,7 @@
 #include <hip/hip_ext.h>
 
 #include <algorithm>
+#include <array>
 #include <atomic>
 #include <chrono>
 #include <cmath>
@@ -18,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <optional>
 #include <type_traits>
 
 namespace bz {
@@ -378,11 +380,11 @@ template <class T> class Solver final : public SolverBase {
         case 1: ensure_z(false); copy_out(out, Z_[zc].p, n); break;
         case 2: ensure_z(); copy_out(out, RES_[rc].p, n); break;
         case 3:
-            if (!gx_valid) { algrad(X_[xc].p, GX_.p, SL_AUX); gx_valid = true; }
+            if (!gx_valid) { dense_redo([&] { algrad(X_[xc].p, GX_.p, SL_AUX); }); gx_valid = true; }
             copy_out(out, GX_.p, n); break;
         case 4:
             ensure_z();
-            if (!gz_valid) { algrad(Z_[zc].p, GZ_.p, SL_AUX); gz_valid = true; }
+            if (!gz_valid) { dense_redo([&] { algrad(Z_[zc].p, GZ_.p, SL_AUX); }); gz_valid = true; }
             copy_out(out, GZ_.p, n); break;
         default: throw Error(BZ_ERR_ARG, "unknown vector id");
         }
@@ -390,8 +392,11 @@ template <class T> class Solver final : public SolverBase {
 
     void eval_al_gradient(const void* x, void* dlx, double* vals3) override {
         copy_in(TMP_.p, x, n);
-        algrad(TMP_.p, D_.p, SL_AUX);           // (exchanges its two slots itself)
-        auto v = collect({SL_AUX, SL_AUX + 1}, 0u);
+        std::vector<double> v;
+        dense_redo([&] {
+            algrad(TMP_.p, D_.p, SL_AUX);           // (exchanges its two slots itself)
+            v = collect({SL_AUX, SL_AUX + 1}, 0u);
+        });
         T half_pen = T(0.5) * T(v[1]);
         vals3[0] = (double)al_value(v[0], v[1]);
         vals3[1] = (double)f_value(v[0]);
@@ -774,7 +779,7 @@ template <class T> class Solver final : public SolverBase {
     // candidates (CXD_, CZN_, GXN_, GZN_) and the images of every stored pair (AS_, AY_: ny-vectors; GS_, GY_: n).
     bool affine_ok_ = false, aff_track_ = false;
     int aff_refresh_ = 8, aff_count_ = 0;
-    int64_t n_affine_ = 0, n_affine_verify_ = 0;
+    int64_t n_affine_ = 0, n_affine_verify_ = 0, n_affine_blends_ = 0;
     T* cx_keep_ = nullptr;                   // algrad (dense c): also leave c(point) here
     DBuf<T> CXS_, CZS_, CXD_, CZN_, GXN_, GZN_;
     std::vector<DBuf<T>> AS_, AY_, GS_, GY_;
@@ -1462,8 +1467,10 @@ template <class T> class Solver final : public SolverBase {
             launch(C_FB, k_zres_elem<T>, grid, (const T*)X_[xc].p, P, gamma, Z_[zc].p,
                    res_valid ? (T*)nullptr : RES_[rc].p, n);      // the two kernels below in one pass
         } else {
-            algrad(X_[xc].p, D_.p, SL_AUX);                  // scratch gradient: GX_/GZ_ keep their meaning
-            fbstep(X_[xc].p, D_.p, gamma, Z_[zc].p, res_valid ? (T*)nullptr : RES_[rc].p, SL_ZS);
+            dense_redo([&] {
+                algrad(X_[xc].p, D_.p, SL_AUX);              // scratch gradient: GX_/GZ_ keep their meaning
+                fbstep(X_[xc].p, D_.p, gamma, Z_[zc].p, res_valid ? (T*)nullptr : RES_[rc].p, SL_ZS);
+            });
         }
         z_valid = true; res_valid = true;
     }
@@ -1568,6 +1575,46 @@ template <class T> class Solver final : public SolverBase {
         else launch(C_COLLECT, k_collect, a.n, a, host_out_dev_);
         return wait_host(a.n, a.ticket);
     }
+    // what a kernel's bounded poll reported in *ptimeout_ (read once the stream has run): cleared, and thrown as the error
+    // that names it
+    [[noreturn]] void raise_timeout() {
+        const int code = *ptimeout_;
+        *ptimeout_ = 0;
+        if (code == 1 && ctx->nranks == 1) throw PersistTimeout();
+        if (code == 6 || code == 7) throw GateTimeout(code);
+        if (code == 8) {      // (whoever can redo its work does; every later evaluation takes the two-kernel form)
+            dense_fused_broken_ = true; ++n_dense_fallbacks_;
+            throw DenseFusedTimeout();
+        }
+        throw Error(code == 1 ? BZ_ERR_HIP : BZ_ERR_COMM,
+                    code == 1 ? "persistent two-loop kernel: grid barrier timed out (blocks not co-resident?)"
+                    : code == 2 ? "p2p scalar exchange timed out waiting for a peer rank"
+                    : code == 4 ? "stencil halo exchange timed out waiting for a neighbour rank"
+                    : code == 5 ? "dense-constraint all-reduce timed out waiting for a peer rank"
+                    : code == 6 ? "a pre-launched pass timed out at its gate (the host never released it)"
+                    : code == 7 ? "a pre-launched pass: workgroups timed out waiting for workgroup 0 to open the gate"
+                                : "persistent two-loop kernel: p2p phase exchange timed out waiting for a peer rank");
+    }
+    // An AL gradient outside an iteration — eval_al_gradient, a gradient of the state asked for, z re-materialised: `run`
+    // queues it (and its read-back, if it has one).  A one-pass launch among it that timed out (reported at the read-back, or
+    // here once the stream has run) is forgotten and `run` is redone: dense_fused_on() is off now, so in the two-kernel form.
+    // (Inside step() the iteration's own read-back sees it and step() redoes the iteration from the state it started from.)
+    template <class F> void dense_redo(F&& run) {
+        const int64_t launched = n_dense_onepass_;
+        try {
+            run();
+            if (n_dense_onepass_ != launched) {
+                BZ_HIP(hipStreamSynchronize(cur_));
+                std::atomic_thread_fence(std::memory_order_acquire);
+                if (*ptimeout_) raise_timeout();
+            }
+        } catch (const DenseFusedTimeout&) {
+            if (ctx->nranks > 1 || gate_pending_) throw;
+            BZ_HIP(hipStreamSynchronize(cur_));
+            *ptimeout_ = 0;
+            run();
+        }
+    }
     // read n scalars from the pinned mailbox once both tagged words of each carry this read-back's tag
     std::vector<double> wait_host(int cnt, unsigned long long ticket) {
         struct { int n; } a{cnt};
@@ -1603,24 +1650,7 @@ template <class T> class Solver final : public SolverBase {
             if (!complete && !*ptimeout_)
                 throw Error(BZ_ERR_HIP, "a read-back did not arrive although the stream is idle (no kernel posted these scalars)");
         }
-        if (*ptimeout_) {
-            const int code = *ptimeout_;
-            *ptimeout_ = 0;
-            if (code == 1 && ctx->nranks == 1) throw PersistTimeout();
-            if (code == 6 || code == 7) throw GateTimeout(code);
-            if (code == 8) {      // (whoever can redo its work does; every later evaluation takes the two-kernel form)
-                dense_fused_broken_ = true; ++n_dense_fallbacks_;
-                throw DenseFusedTimeout();
-            }
-            throw Error(code == 1 ? BZ_ERR_HIP : BZ_ERR_COMM,
-                        code == 1 ? "persistent two-loop kernel: grid barrier timed out (blocks not co-resident?)"
-                        : code == 2 ? "p2p scalar exchange timed out waiting for a peer rank"
-                        : code == 4 ? "stencil halo exchange timed out waiting for a neighbour rank"
-                        : code == 5 ? "dense-constraint all-reduce timed out waiting for a peer rank"
-                        : code == 6 ? "a pre-launched pass timed out at its gate (the host never released it)"
-                        : code == 7 ? "a pre-launched pass: workgroups timed out waiting for workgroup 0 to open the gate"
-                                    : "persistent two-loop kernel: p2p phase exchange timed out waiting for a peer rank");
-        }
+        if (*ptimeout_) raise_timeout();
         std::vector<double> out(a.n);
         const unsigned long long* hw = (const unsigned long long*)host_out_;
         for (int i = 0; i < a.n; ++i) {
@@ -2206,7 +2236,7 @@ template <class T> class Solver final : public SolverBase {
         static const int aff_env = std::getenv("BZ_AFFINE") ? std::atoi(std::getenv("BZ_AFFINE")) : -1;
         if (aff_env >= 0) aff_refresh_ = aff_env;
         aff_track_ = affine_ok_ && aff_refresh_ > 0 && o.lbfgs_compact != 0 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS;
-        aff_count_ = 0; n_affine_ = 0; n_gated_ = 0; n_gate_aborts_ = 0; n_dense_onepass_ = 0;
+        aff_count_ = 0; n_affine_ = 0; n_affine_blends_ = 0; n_gated_ = 0; n_gate_aborts_ = 0; n_dense_onepass_ = 0;
         compact_ok = M >= 1 && (o.lbfgs_compact == 1 || dir_kind_ == BZ_DIR_ANDERSON ||
                                 (o.lbfgs_compact == 2 && (fused_ok || stencil_fast_ || aff_track_) && M <= CM));
         {
@@ -2421,6 +2451,11 @@ template <class T> class Solver final : public SolverBase {
             k_ = sv[0]; n_grad = sv[1]; n_prox = sv[2]; n_bt = sv[3]; n_halv = sv[4]; n_fused = sv[5]; n_skips = sv[6];
             gx_valid = false; gz_valid = false;
         };
+        // (a one-pass dense timeout is seen at a read-back of the iteration, possibly a later one than the first: by then the
+        // attempt may have traded the image buffers, halved gamma, reset the memory and replaced the state's scalars)
+        // (only the one-pass kernel reports such a timeout: other problems skip the snapshot)
+        std::optional<StepState> sv_state;
+        if (dense_fused_on()) sv_state = save_state();
         try {
             try {
                 step_impl();
@@ -2443,8 +2478,9 @@ template <class T> class Solver final : public SolverBase {
                 BZ_HIP(hipStreamSynchronize(cur_));
                 cur_ = ctx->stream;
                 *ptimeout_ = 0;
+                if (!sv_state || (dir_kind_ == BZ_DIR_BROYDEN && n_halv != sv[4])) throw;      // (a halving resets Broyden's operator itself)
                 restore();
-                aff_count_ = aff_refresh_;      // (the images of this iteration's points were being formed: evaluate afresh)
+                load_state(*sv_state);
                 std::fprintf(stderr, "Warning: the one-pass dense kernel timed out (is the GPU shared?); using the two-kernel form\n");
                 step_impl();
             } catch (const PersistTimeout&) {
@@ -2469,6 +2505,47 @@ template <class T> class Solver final : public SolverBase {
     }
     int64_t n_persist_fallbacks_ = 0;
    private:
+    // What step_impl changes before its last read-back (the ring indices, the pair insertion and the stop norm are committed
+    // after it): the state's scalars, the L-BFGS bookkeeping (a halving resets it), the affine-image buffers — traded by
+    // pointer, and only the candidates (GXN_, GZN_, CXD_, CZN_) and the spare pair's images are written — and the image
+    // counters.  Put back, the iteration can be redone from the state it started from, images and memory included.
+    struct StepState {
+        T gamma, f_x, g_z, dot_gr, ss_res, f_z_al, fraw_last, fbe_last, H;
+        std::deque<int> order;
+        std::vector<int> freeslots;
+        int gm, aff_count;
+        bool pw_valid, gx_valid, gz_valid, z_valid, res_valid;
+        double hp[CM], hw[CM];
+        int64_t n_affine, n_affine_verify, n_affine_blends;
+        T* img_p[8];
+        size_t img_n[8];
+    };
+    std::array<DBuf<T>*, 8> image_bufs() { return {&GX_, &GXN_, &GZ_, &GZN_, &CXS_, &CXD_, &CZS_, &CZN_}; }
+    StepState save_state() {
+        StepState st;
+        st.gamma = gamma; st.f_x = f_x; st.g_z = g_z; st.dot_gr = dot_gr; st.ss_res = ss_res; st.f_z_al = f_z_al;
+        st.fraw_last = fraw_last; st.fbe_last = fbe_last; st.H = H;
+        st.order = order; st.freeslots = freeslots; st.gm = gm; st.aff_count = aff_count_;
+        st.pw_valid = pw_valid; st.gx_valid = gx_valid; st.gz_valid = gz_valid; st.z_valid = z_valid; st.res_valid = res_valid;
+        for (int i = 0; i < CM; ++i) { st.hp[i] = hp_[i]; st.hw[i] = hw_[i]; }
+        st.n_affine = n_affine_; st.n_affine_verify = n_affine_verify_; st.n_affine_blends = n_affine_blends_;
+        const auto b = image_bufs();
+        for (int i = 0; i < 8; ++i) { st.img_p[i] = b[i]->p; st.img_n[i] = b[i]->n; }
+        return st;
+    }
+    void load_state(const StepState& st) {
+        gamma = st.gamma; f_x = st.f_x; g_z = st.g_z; dot_gr = st.dot_gr; ss_res = st.ss_res; f_z_al = st.f_z_al;
+        fraw_last = st.fraw_last; fbe_last = st.fbe_last; H = st.H;
+        order = st.order; freeslots = st.freeslots; gm = st.gm; aff_count_ = st.aff_count;
+        pw_valid = st.pw_valid; z_valid = st.z_valid; res_valid = st.res_valid;
+        for (int i = 0; i < CM; ++i) { hp_[i] = st.hp[i]; hw_[i] = st.hw[i]; }
+        n_affine_ = st.n_affine; n_affine_verify_ = st.n_affine_verify; n_affine_blends_ = st.n_affine_blends;
+        const auto b = image_bufs();
+        for (int i = 0; i < 8; ++i) { b[i]->p = st.img_p[i]; b[i]->n = st.img_n[i]; }
+        cx_keep_ = nullptr;
+        // without images the attempt wrote grad L at its trial points into GX_ and GZ_ themselves (the redo evaluates them)
+        gx_valid = aff_track_ && st.gx_valid; gz_valid = aff_track_ && st.gz_valid;
+    }
     void step_impl() {
         ++k_;
         const T eps = std::numeric_limits<T>::epsilon();
@@ -3055,6 +3132,7 @@ template <class T> class Solver final : public SolverBase {
                 // pass over A.  (As for x_d: a failing step-size test on images is re-run on evaluations, img_trial.)  The rejected
                 // trial's z images (CZN_, GZN_) are dead: they take the results and trade places.
                 ++aff_count_; img_trial = true;      // (n_affine_images counts iterations whose trial point x + d went on images)
+                ++n_affine_blends_;
                 mv(3, ny);
                 launch(C_MISC, k_blend<T>, grid_y, (const T*)CXD_.p, (const T*)CZS_.p, tau, T(1) - tau, CZN_.p, ny);
                 std::swap(CXD_.p, CZN_.p); std::swap(CXD_.n, CZN_.n);
@@ -3154,6 +3232,7 @@ template <class T> class Solver final : public SolverBase {
         st->n_gate_fallbacks = n_gate_fallbacks_;
         st->n_dense_onepass = n_dense_onepass_;
         st->n_dense_fallbacks = n_dense_fallbacks_;
+        st->n_affine_blends = n_affine_blends_;
     }
 };
 

@@ -310,6 +310,8 @@ typedef struct {
                                  A'yhat from one read of every row, demo/basispursuit.jl:38-49) instead of two products         */
     int64_t n_dense_fallbacks;/* times that kernel's row groups timed out waiting for each other (workgroups not all resident:
                                  the GPU has another tenant) and the solve went on with the two-kernel form (0 or 1)           */
+    int64_t n_affine_blends;  /* iterations whose first tau-backtracked trial point took its images under c and grad L as the
+                                 blend of the images at hand (no pass over A; BZ_AFFINE_BLEND=0 turns it off)                  */
 } bz_panoc_stats;
 
 /* Multipliers/penalties of the current subproblem:  AugLagUpdate!(alFun, mu, y)

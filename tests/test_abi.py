@@ -53,6 +53,8 @@ def test_struct_layouts_match_the_header(bz):
         assert int(got[cname]) == C.sizeof(st), cname
         for fname, _ in st._fields_:
             assert int(got[f"{cname}.{fname}"]) == getattr(st, fname).offset, f"{cname}.{fname}"
+    # (fields are only ever appended: the newest last)
+    assert L.PanocStats._fields_[-1] == ("n_affine_blends", C.c_int64)
 
 
 def test_header_is_plain_c(bz):

@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from tests.test_gpu_parity import make_cfg4, rel, run_traces
+from tests.test_gpu_parity import LongDoubleReducer, _err, make_cfg4, rel, run_traces
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
@@ -314,3 +314,240 @@ def test_dense_one_pass_timeout_falls_back_to_two_kernels(bz, ref, monkeypatch, 
     assert st2.n_dense_fallbacks == 0 and st2.n_dense_onepass == 0
     assert abs(st.iters - st2.iters) <= max(3, 0.1 * st2.iters)
     assert np.max(np.abs(z - z2)) <= 1e-3 * max(1.0, np.max(np.abs(z2)))
+    # ... and step by step: the same launch sabotaged, 2 CM states past it, against the two-kernel run to fp32 rounding
+    states = 9 + 2 * CM + 4 if where == "in-the-loop" else 2 * CM + 2
+    monkeypatch.setenv("BZ_DENSE_FUSED", "1")
+    monkeypatch.setenv("BZ_TEST_DENSE_TIMEOUT", "9" if where == "in-the-loop" else "2")
+    sab = _trajectory(bz, ref, dev, orc, n, ny, np.float32, mu, y, x0, states, 8, 1e-7, oracle=False)
+    monkeypatch.setenv("BZ_TEST_DENSE_TIMEOUT", "0")
+    monkeypatch.setenv("BZ_DENSE_FUSED", "0")
+    two = _trajectory(bz, ref, dev, orc, n, ny, np.float32, mu, y, x0, states, 8, 1e-7, oracle=False)
+    assert sab["stats"][-1][1] == 1 and two["stats"][-1][1] == 0
+    for k in range(states):
+        for key in ("x", "z"):
+            assert _err(sab[key][k], two[key][k]) <= 1e-5, (k, key, _err(sab[key][k], two[key][k]))
+        assert abs(sab["gamma"][k] - two["gamma"][k]) <= 1e-5 * two["gamma"][k], k
+
+
+# ---- a one-pass timeout inside an iteration, state by state ---------------------------------------------------------------
+# The timeout is seen at the iteration's read-back, after the attempt has traded the affine-image buffers (GX_ <-> GXN_, and
+# with a blended backtrack CXD_ <-> CZN_, GX_ <-> GZN_) and possibly replaced the state's scalars: step() puts the state the
+# iteration started from back (StepState) and redoes it in the two-kernel form.  A redo from a half-traded state leaves
+# GS_ = GX_ - GXN_ ~ 0 as the image of the new pair, and every image-built grad L(x_d) of the next CM iterations wrong.
+CM = 5
+_ST = ("n_dense_onepass", "n_dense_fallbacks", "n_affine_images", "n_affine_blends", "n_backtracks", "n_gamma_halvings", "n_grad")
+
+
+def _trajectory(bz, ref, dev, orc, n, ny, dtype, mu, y, x0, states, refresh, minimum_gamma, oracle=True):
+    """Step the device solver (run_traces' options) and record every state: x, z, gamma, the stop norm, the counters of
+    panoc_stats (_ST) and — with `oracle` — run_traces' rows against the oracle and its long-double twin."""
+    prob = bz.Problem(*dev, n, ny, dtype)
+    prob.set_multipliers(mu, y)
+    sub = bz.PANOCplus(tol=0.0, maxit=10 ** 9, minimum_gamma=minimum_gamma, fuse=True, directions=bz.LBFGS(5),
+                       affine_refresh=refresh)
+    prob.panoc_begin(sub.c_opts(), x0)
+    if oracle:
+        its, sts = [], []
+        for red in (None, LongDoubleReducer()):
+            ref.set_reducer(red)
+            al = ref.AugLagFun(orc[0], orc[2], orc[3], mu.copy(), y.copy(), x0)
+            it = ref.PANOCplusIteration(al, ref.NonsmoothCostFun(orc[1]), x0, minimum_gamma=minimum_gamma)
+            its.append(it)
+            sts.append(it.init())
+        ref.set_reducer(None)
+    out = {"x": [], "z": [], "gamma": [], "stop": [], "stats": [], "rows": []}
+    env = 0.0
+    for k in range(states):
+        sc = prob.panoc_scalars()
+        st = prob.panoc_stats()
+        out["x"].append(prob.panoc_vector("x")); out["z"].append(prob.panoc_vector("z"))
+        out["gamma"].append(sc["gamma"]); out["stop"].append(sc["stop_norm"])
+        out["stats"].append(tuple(int(getattr(st, f)) for f in _ST))
+        if oracle:
+            o = sts[0]
+            env = max(env, _err(sts[1].x, o.x), _err(sts[1].z, o.z))
+            out["rows"].append((k, _err(out["x"][-1], o.x), _err(out["z"][-1], o.z), sc["gamma"], float(o.gamma), sc["stop_norm"],
+                                float(its[0].stop_norm(o)), env))
+        if k + 1 < states:
+            prob.panoc_step()
+            if oracle:
+                sts[0] = its[0].step(sts[0])
+                ref.set_reducer(LongDoubleReducer())
+                sts[1] = its[1].step(sts[1])
+                ref.set_reducer(None)
+    prob.close()
+    return out
+
+
+def _delta(t, i, f):
+    """counter f (_ST) moved by iteration i (state i - 1 -> i)"""
+    j = _ST.index(f)
+    return t["stats"][i][j] - t["stats"][i - 1][j]
+
+
+def _pick(probe, case, first):
+    """(iteration, 1-based index of the k_dense_fused launch to sabotage) for the case, from an unsabotaged one-pass run of
+    the same problem (deterministic: test_dense_one_pass_is_deterministic)"""
+    for i in range(first, len(probe["stats"]) - 2 * CM - 1):
+        launches = _delta(probe, i, "n_dense_onepass")
+        img, bt, hv = (_delta(probe, i, f) for f in ("n_affine_images", "n_backtracks", "n_gamma_halvings"))
+        base = probe["stats"][i - 1][0]
+        if hv:
+            continue
+        if case == "image" and img == 1 and bt == 0 and launches == 1:
+            return i, base + 1                 # the only pass over A: grad L at z, behind the image-built x_d
+        if case == "refresh" and img == 0 and bt == 0 and launches == 2:
+            return i, base + 1                 # grad L at x_d, the refresh's first pass over A
+        if case == "blend" and img == 1 and bt == 1 and launches == 2:
+            # (a backtrack with no pass over A at its trial point: the blend of images, and its step-size test passed on them)
+            return i, base + 2                 # grad L at the blended trial's z: after the blend has traded the images
+    return None
+
+
+_A_SETUPS = {"image": ((600, 8192), np.float32, 8, 30), "refresh": ((600, 8192), np.float32, 8, 30),
+             "blend": ((64, 512), np.float64, 16, 60)}
+
+
+@pytest.mark.timeout(600)
+@pytest.mark.parametrize("case", ["image", "refresh", "blend"])
+def test_dense_timeout_inside_an_iteration_redoes_it_from_its_own_state(bz, ref, case, monkeypatch):
+    """A k_dense_fused launch made to time out (BZ_TEST_DENSE_TIMEOUT=k, a short BZ_DENSE_SPIN) in (a) an iteration whose
+    trial point was built on images, (b) a refresh iteration, (c) the blended first backtrack: the run goes on in the
+    two-kernel form and follows, state by state for 2 CM states and more past the fallback, (i) the unsabotaged one-pass run
+    bit for bit up to the fallback, (ii) a BZ_DENSE_FUSED=0 run to rounding — the gap the two forms show unsabotaged, at
+    least fp32 / fp64 rounding — x, z, gamma and the stop norm, (iii) the oracle inside the envelope of
+    test_dense_iterates_follow_oracle_with_and_without_affine_images."""
+    (ny, n), dtype, refresh, states = _A_SETUPS[case]
+    d, dev, orc = make_cfg4(bz, ref, ny, n, dtype, density=0.05)
+    mu, y = np.full(ny, 0.1, dtype), (0.1 * np.random.default_rng(2).standard_normal(ny)).astype(dtype)
+    x0 = np.zeros(n, dtype)
+    mg = float(np.finfo(dtype).eps)
+    monkeypatch.setenv("BZ_DENSE_SPIN", "20000")
+    monkeypatch.setenv("BZ_TEST_DENSE_TIMEOUT", "0")
+    probe = _trajectory(bz, ref, dev, orc, n, ny, dtype, mu, y, x0, states, refresh, mg, oracle=False)
+    hit = _pick(probe, case, CM + 1)
+    assert hit is not None, (case, probe["stats"])
+    it, launch = hit
+    monkeypatch.setenv("BZ_TEST_DENSE_TIMEOUT", str(launch))
+    sab = _trajectory(bz, ref, dev, orc, n, ny, dtype, mu, y, x0, states, refresh, mg)
+    monkeypatch.setenv("BZ_TEST_DENSE_TIMEOUT", "0")
+    monkeypatch.setenv("BZ_DENSE_FUSED", "0")
+    two = _trajectory(bz, ref, dev, orc, n, ny, dtype, mu, y, x0, states, refresh, mg, oracle=False)
+    tol = 1e-5 if dtype == np.float32 else 1e-12
+    gap, sgap, worst, log, bad = 0.0, 0.0, [0.0, 0.0], [], []
+    for k in range(states):
+        # the gap the two forms show unsabotaged (one-pass probe against the two-kernel run): what rounding amounts to here
+        gap = max(gap, _err(probe["x"][k], two["x"][k]), _err(probe["z"][k], two["z"][k]))
+        sgap = max(sgap, abs(probe["stop"][k] - two["stop"][k]) / max(two["stop"][k], 1e-300))
+        ex, ez = _err(sab["x"][k], two["x"][k]), _err(sab["z"][k], two["z"][k])
+        eg = abs(sab["gamma"][k] - two["gamma"][k]) / two["gamma"][k]
+        es = abs(sab["stop"][k] - two["stop"][k]) / max(two["stop"][k], 1e-300)
+        worst[k >= it] = max(worst[k >= it], ex, ez)
+        same = k >= it or (np.array_equal(sab["x"][k], probe["x"][k]) and np.array_equal(sab["z"][k], probe["z"][k]))
+        log.append("k=%d ex=%.3e ez=%.3e egamma=%.3e estop=%.3e gap=%.3e stopgap=%.3e bitwise_before=%s %s"
+                   % (k, ex, ez, eg, es, gap, sgap, same, sab["stats"][k]))
+        if not (same and ex <= max(tol, 10.0 * gap) and ez <= max(tol, 10.0 * gap) and eg <= tol and es <= max(1e3 * tol, 10.0 * sgap)):
+            bad.append(k)
+    _log(f"dense_timeout_{case}", [f"iteration {it} launch {launch}: max |sab - two| before {worst[0]:.3e}, from the "
+                                       f"fallback on {worst[1]:.3e}; counters {_ST}", "probe " + str(probe["stats"][it])] + log)
+    # the fallback happened, once, in the chosen iteration, after the launches of that iteration's attempt
+    F = _ST.index
+    assert sab["stats"][it - 1][F("n_dense_fallbacks")] == 0 and sab["stats"][it][F("n_dense_fallbacks")] == 1
+    assert sab["stats"][-1][F("n_dense_fallbacks")] == 1
+    assert sab["stats"][-1][F("n_dense_onepass")] == probe["stats"][it][F("n_dense_onepass")] >= launch
+    assert two["stats"][-1][F("n_dense_onepass")] == 0 and two["stats"][-1][F("n_dense_fallbacks")] == 0
+    # ... and the redo took the decisions of the unsabotaged iteration: its images (a blend included), its backtracks
+    for f in ("n_affine_images", "n_affine_blends", "n_backtracks", "n_gamma_halvings"):
+        assert _delta(sab, it, f) == _delta(probe, it, f), (f, sab["stats"][it - 1:it + 1], probe["stats"][it - 1:it + 1])
+        assert [s[F(f)] for s in sab["stats"]] == [s[F(f)] for s in two["stats"]], f
+    if case == "blend":
+        assert _delta(sab, it, "n_affine_blends") == 1
+    assert not bad, (it, [log[k] for k in bad[:3]])
+    base = 1e-9 if dtype == np.float64 else 5e-5
+    for k, ex, ez, g_d, g_r, sn_d, sn_r, sens in sab["rows"]:
+        assert abs(g_d - g_r) <= (1e-12 if dtype == np.float64 else 1e-5) * g_r, k
+        assert ex <= max(base, 100 * sens) and ez <= max(base, 100 * sens), (k, ex, ez, sens)
+
+
+def _log(name, lines):
+    """the step-wise numbers of a test, in its captured output (shown on failure, or with -rA / -s)"""
+    print("---- " + name)
+    print("\n".join(lines))
+
+
+# ---- a one-pass timeout outside an iteration: the call itself is redone in the two-kernel form ----------------------------
+@pytest.mark.parametrize("dtype", [np.float32, np.float64])
+def test_dense_timeout_in_eval_al_gradient_is_redone_in_two_kernel_form(bz, ref, dtype, monkeypatch):
+    """eval_al_gradient with its k_dense_fused launch timing out returns the oracle's grad L and L (the tolerance of
+    test_dense_one_pass_gradient_matches_oracle_and_two_kernel_form), counts the fallback, and every later gradient of the
+    problem — a solve's start included — is in the two-kernel form"""
+    ny, n = 600, 8192
+    rng = np.random.default_rng(11)
+    A = (rng.standard_normal((ny, n)) / np.sqrt(ny)).astype(dtype)
+    b = rng.standard_normal(ny).astype(dtype)
+    x = (rng.standard_normal(n) * (rng.random(n) < 0.2)).astype(dtype)
+    mu = (10.0 ** rng.uniform(-2, 0, ny)).astype(dtype)
+    yv = rng.standard_normal(ny).astype(dtype)
+    monkeypatch.setenv("BZ_DENSE_SPIN", "20000")
+    monkeypatch.setenv("BZ_TEST_DENSE_TIMEOUT", "1")
+    prob = bz.Problem(bz.Zero(), bz.NormL1(1.0), bz.DenseAffine(A, b), bz.ZeroSet(), n, ny, dtype)
+    prob.set_multipliers(mu, yv)
+    g, vals = prob.eval_al_gradient(x)
+    g2, vals2 = prob.eval_al_gradient(x)
+    prob.panoc_begin(bz.PANOCplus(tol=0.0, maxit=10 ** 9, minimum_gamma=float(np.finfo(dtype).eps)).c_opts(), x)
+    st = prob.panoc_stats()
+    prob.close()
+    assert st.n_dense_fallbacks == 1 and st.n_dense_onepass == 0, (st.n_dense_fallbacks, st.n_dense_onepass)
+    al = ref.AugLagFun(ref.Zero(), ref.DenseAffine(A, b), ref.ZeroSet(), mu.copy(), yv.copy(), x)
+    g_ref = np.empty(n, dtype)
+    L_ref = al.gradient(g_ref, x)
+    tol = 1e-12 if dtype == np.float64 else 2e-5
+    scale = max(1.0, float(np.max(np.abs(g_ref))))
+    assert np.max(np.abs(g - g_ref)) <= tol * scale, np.max(np.abs(g - g_ref))
+    assert abs(vals[0] - L_ref) <= tol * max(1.0, abs(L_ref)), (vals[0], L_ref)
+    assert np.array_equal(g, g2) and vals == vals2          # (the redo is the two-kernel form the next call takes)
+
+
+# ---- the blended first backtrack against evaluations, state by state -----------------------------------------------------
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_blended_backtrack_follows_evaluated_backtrack_state_by_state(bz, ref, dtype, monkeypatch):
+    """BZ_AFFINE_BLEND=1 (a first tau backtrack takes its images under c and grad L as the blend of the images at hand)
+    against BZ_AFFINE_BLEND=0 (evaluated with a pass over A): the same decisions, and x, z, gamma state by state to
+    rounding over 60 states of the backtracking set-up of test_backtracked_trial_points_on_images_follow_the_oracle —
+    with at least one blended trial whose step-size test PASSED on images (its iteration made no pass over A beyond the
+    two gradients at z).  Rounding: 1e-12 relative in fp64 (1e-5 in fp32), or ten times the gap that two evaluated runs
+    differing only in their summation order (the one-pass kernel and the two-kernel form) show by then — the states
+    near convergence amplify it (fp64, measured: the blend within 1e-12 for 45 states, 2.2e-11 at state 57)."""
+    ny, n = 64, 512
+    d, dev, orc = make_cfg4(bz, ref, ny, n, dtype, density=0.05)
+    mu, y = np.full(ny, 0.1, dtype), (0.1 * np.random.default_rng(2).standard_normal(ny)).astype(dtype)
+    x0 = np.zeros(n, dtype)
+    mg = 2.3e-16 if dtype == np.float64 else float(np.finfo(np.float32).eps)
+    # (fp32: the two runs round differently from the first blend on, and 58 states in a step-size test flips — measured;
+    # 50 states are compared)
+    states = 60 if dtype == np.float64 else 50
+    runs = {}
+    for blend, fused in (("1", "1"), ("0", "1"), ("0", "0")):
+        monkeypatch.setenv("BZ_AFFINE_BLEND", blend)
+        monkeypatch.setenv("BZ_DENSE_FUSED", fused)
+        runs[blend + fused] = _trajectory(bz, ref, dev, orc, n, ny, dtype, mu, y, x0, states, 16, mg, oracle=False)
+    a, b, c = runs["11"], runs["01"], runs["00"]
+    F = _ST.index
+    passed = [i for i in range(1, states) if _delta(a, i, "n_affine_blends") == 1 and _delta(a, i, "n_backtracks") == 1
+              and _delta(a, i, "n_dense_onepass") == 2]
+    tol = 1e-12 if dtype == np.float64 else 1e-5
+    log, bad, gap = ["blended trials that passed on images: %s" % passed], [], 0.0
+    for k in range(states):
+        gap = max(gap, _err(b["x"][k], c["x"][k]), _err(b["z"][k], c["z"][k]))
+        ex, ez = _err(a["x"][k], b["x"][k]), _err(a["z"][k], b["z"][k])
+        eg = abs(a["gamma"][k] - b["gamma"][k]) / b["gamma"][k]
+        log.append("k=%d ex=%.3e ez=%.3e egamma=%.3e gap=%.3e %s %s" % (k, ex, ez, eg, gap, a["stats"][k], b["stats"][k]))
+        if not (ex <= max(tol, 10.0 * gap) and ez <= max(tol, 10.0 * gap) and eg <= tol):
+            bad.append(k)
+    _log(f"dense_blend_{np.dtype(dtype).name}", log)
+    assert b["stats"][-1][F("n_affine_blends")] == 0 and a["stats"][-1][F("n_affine_blends")] >= 1
+    for f in ("n_backtracks", "n_gamma_halvings"):
+        assert [s[F(f)] for s in a["stats"]] == [s[F(f)] for s in b["stats"]], f
+    assert a["stats"][-1][F("n_backtracks")] >= 4
+    assert passed, a["stats"]
+    assert not bad, [log[k + 1] for k in bad[:3]]
