@@ -3105,8 +3105,12 @@ constexpr int FAM_HEADLINE = fam_code(FAM_F_DIAG, FAM_G_L1, FAM_D_BOX);
 
 //   UNI / TRIAL = -1: taken at run time from C.uni_rt / C.trial_rt (the family instantiations: a wave-uniform branch
 //   around two loads and one store costs nothing next to a third of the instantiations)
+//   PP = 1: the invariant parameter streams q and b are loaded with the default (allocating) cache policy even when NT
+//   streams everything else: they are read unchanged by every pass of a solve, and the 256 MB Infinity Cache then
+//   serves them from one pass to the next behind the non-temporal ring (tools/probes/mall_params.hip).  Same
+//   arithmetic, same bits; only the cache bits of two loads differ from PP = 0.
 template <class T, int MM, bool NT, bool SPEC, bool OFF32 = false, int XR = 0, int UNI = 0, int TRIAL = 0,
-          int FAM = FAM_HEADLINE>
+          int FAM = FAM_HEADLINE, int PP = 0>
 __global__ void __launch_bounds__(BLOCK)
 k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x,
                 const T* __restrict__ res_prev, ElemParams<T> P, T gamma, T* __restrict__ x_d,
@@ -3217,10 +3221,11 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
     constexpr int NSTREAMS = MM + 1 + (fam_fk(FAM) ? 2 : 0) + (UNI >= 2 ? 0 : (UNI == 1 ? 1 : 2)) + (TRIAL == 0 ? 0 : 1) +
                              (GKC == FAM_G_L1BOX ? 1 : 0) + (GKC == FAM_G_INDBOX_VEC ? 2 : 0) + (DKC == FAM_D_BOX_VEC ? 2 : 0);
     constexpr int DEPTH = NSTREAMS <= 11 ? 2 : 1;
+    constexpr bool NTP = NT && PP == 0;      // (the policy of q and b)
     struct Stage { Pack<T> q, b, mu, muy, px, ps[MM], xt, gu, glo, ghi, dlo, dhi; };
     auto load_stage = [&](Stage& S, unsigned bo) {
         asm volatile("" : "+v"(bo));
-        if (fk == BZ_F_DIAG_QUADRATIC) { S.q = ldo<T, NT>(P.q, bo); S.b = ldo<T, NT>(P.b, bo); }
+        if (fk == BZ_F_DIAG_QUADRATIC) { S.q = ldo<T, NTP>(P.q, bo); S.b = ldo<T, NTP>(P.b, bo); }
         if (uni < 1) S.mu = ldo<T, NT>(P.mu, bo);
         if (uni < 2) S.muy = ldo<T, NT>(P.muy, bo);
         S.px = ldo<T, NT>(x, bo);
@@ -3261,7 +3266,7 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
 #pragma unroll
             for (int i = 0; i < MM; ++i) ps[i] = SG.ps[i];
         } else if constexpr (O32 && !FAMILY) {
-            L.q = ldo<T, NT>(P.q, bo); L.b = ldo<T, NT>(P.b, bo);
+            L.q = ldo<T, NTP>(P.q, bo); L.b = ldo<T, NTP>(P.b, bo);
             if (P.uni >= 1) L.mu = splat(P.mu_uniform); else L.mu = ldo<T, NT>(P.mu, bo);
             if (P.uni >= 2) L.muy = splat(T(0)); else L.muy = ldo<T, NT>(P.muy, bo);
             L.dlo = splat(P.D_lo); L.dhi = splat(P.D_hi);
@@ -3275,7 +3280,7 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
             }
         } else {
             if (SPEC && !FAMILY) {
-                L.q = ldp<T, NT>(P.q, i0, cnt); L.b = ldp<T, NT>(P.b, i0, cnt);
+                L.q = ldp<T, NTP>(P.q, i0, cnt); L.b = ldp<T, NTP>(P.b, i0, cnt);
                 if (P.uni >= 1) L.mu = splat(P.mu_uniform); else L.mu = ldp<T, NT>(P.mu, i0, cnt);
                 if (P.uni >= 2) L.muy = splat(T(0)); else L.muy = ldp<T, NT>(P.muy, i0, cnt);
                 L.dlo = splat(P.D_lo); L.dhi = splat(P.D_hi);

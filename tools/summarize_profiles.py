@@ -50,16 +50,17 @@ def form_of(kernel):
     if m:
         a = [x.strip() for x in m.group(1).split(",")]
         a += ["false", "0", "0", "0", "35"][len(a) - 4:] if len(a) < 9 else []
-        # <T, MM, NT, SPEC, OFF32, XR, UNI, TRIAL, FAM>
+        # <T, MM, NT, SPEC, OFF32, XR, UNI, TRIAL, FAM, PP>
         nt, spec, xr, uni = a[2] == "true", a[3] == "true", a[5], a[6]
         trial = {"true": "1", "false": "0"}.get(a[7], a[7])
         fam = a[8] if len(a) > 8 else "35"
+        pp = a[9] if len(a) > 9 else "0"
         if xr == "2":
             s = f"k_fused_compact<XR=2,UNI={uni},NT={int(nt)},TRIAL={trial}"
             # (the headline family's own instantiations carry no FAM tag: they are the ones with the default FAM = 35 and a
-            # compile-time UNI that the host launches outside the family table)
+            # compile-time UNI that the host launches outside the family table; PP = 1 — q and b cacheable — is tagged)
             table = uni == "-1" or (len(a) > 8 and fam != "35")
-            return s + (f",FAM={fam}>" if table else ">")
+            return s + (f",FAM={fam}>" if table else (",PP=1>" if pp == "1" else ">"))
         if xr == "1":
             return f"k_fused_compact<XR=1,NT={int(nt)}>"
         return f"k_fused_compact<XR=0,SPEC={int(spec)},NT={int(nt)}>"
