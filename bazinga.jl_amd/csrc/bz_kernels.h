@@ -15,6 +15,7 @@
 // Per-element arithmetic mirrors the CPU oracle operation for operation (build with
 // -ffp-contract=off), so element-wise outputs are bit-identical to oracle/.
 #pragma once
+#include <algorithm>
 #include <type_traits>
 
 #include <hip/hip_runtime.h>
@@ -301,6 +302,40 @@ __device__ __forceinline__ Pack<T> ldo(const T* __restrict__ base, unsigned byte
     for (int e = 0; e < PackN<T>::N; ++e) r.v[e] = v[e];
     return r;
 }
+// K (1..4) 16-byte-per-lane direct-to-LDS loads of one cache policy behind ONE write of M0: load j reads
+// (base[j] + j KiB, 32-bit byte offset) into LDS [lds + j KiB, + 1 KiB), lane-linear.  The instruction offset of
+// global_load_lds applies to the global and the LDS address alike, so the caller passes each base j KiB low (loop-invariant
+// scalar arithmetic).  Invisible to the compiler's wait bookkeeping: the caller counts the loads with its own vmcnt.
+#define BZ_GLDS_POL_1 " nt"
+#define BZ_GLDS_POL_0 ""
+#define BZ_GLDS_HEAD "s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\t"
+#define BZ_GLDS_TAIL "s_mov_b32 m0, %0"
+#define BZ_GLDS_L(j, off, P) "global_load_lds_dwordx4 %1, %" #j " offset:" #off P "\n\t"
+#define BZ_GLDS_ASM(P)                                                                                                       \
+    if constexpr (K == 1)                                                                                                    \
+        asm volatile(BZ_GLDS_HEAD BZ_GLDS_L(3, 0, P) BZ_GLDS_TAIL : "=&s"(keep) : "v"(byte_off), "s"(m0v), "s"(b[0]) : "memory"); \
+    else if constexpr (K == 2)                                                                                               \
+        asm volatile(BZ_GLDS_HEAD BZ_GLDS_L(3, 0, P) BZ_GLDS_L(4, 1024, P) BZ_GLDS_TAIL                                     \
+                     : "=&s"(keep) : "v"(byte_off), "s"(m0v), "s"(b[0]), "s"(b[1]) : "memory");                              \
+    else if constexpr (K == 3)                                                                                               \
+        asm volatile(BZ_GLDS_HEAD BZ_GLDS_L(3, 0, P) BZ_GLDS_L(4, 1024, P) BZ_GLDS_L(5, 2048, P) BZ_GLDS_TAIL               \
+                     : "=&s"(keep) : "v"(byte_off), "s"(m0v), "s"(b[0]), "s"(b[1]), "s"(b[2]) : "memory");                   \
+    else                                                                                                                     \
+        asm volatile(BZ_GLDS_HEAD BZ_GLDS_L(3, 0, P) BZ_GLDS_L(4, 1024, P) BZ_GLDS_L(5, 2048, P) BZ_GLDS_L(6, 3072, P)      \
+                     BZ_GLDS_TAIL : "=&s"(keep) : "v"(byte_off), "s"(m0v), "s"(b[0]), "s"(b[1]), "s"(b[2]), "s"(b[3]) : "memory");
+template <bool NT, int K>
+__device__ __forceinline__ void glds16x(const void* const* b, unsigned byte_off, unsigned lds) {
+    static_assert(K >= 1 && K <= 4, "one M0 write covers at most four 1 KiB destinations (13-bit instruction offset)");
+    unsigned keep;
+    const unsigned m0v = __builtin_amdgcn_readfirstlane(lds);
+    if constexpr (NT) { BZ_GLDS_ASM(BZ_GLDS_POL_1) } else { BZ_GLDS_ASM(BZ_GLDS_POL_0) }
+}
+#undef BZ_GLDS_ASM
+#undef BZ_GLDS_L
+#undef BZ_GLDS_TAIL
+#undef BZ_GLDS_HEAD
+#undef BZ_GLDS_POL_0
+#undef BZ_GLDS_POL_1
 template <class T, bool NT>
 __device__ __forceinline__ void sto(T* __restrict__ base, unsigned byte_off, const Pack<T>& r) {
     using V = typename PackVec<T>::type;
@@ -3109,8 +3144,12 @@ constexpr int FAM_HEADLINE = fam_code(FAM_F_DIAG, FAM_G_L1, FAM_D_BOX);
 //   streams everything else: they are read unchanged by every pass of a solve, and the 256 MB Infinity Cache then
 //   serves them from one pass to the next behind the non-temporal ring (tools/probes/mall_params.hip).  Same
 //   arithmetic, same bits; only the cache bits of two loads differ from PP = 0.
+//   LQ = 1 (headline family, pipelined form): the packs ahead are loaded straight into a per-wave LDS ring
+//   (global_load_lds_dwordx4, the same streams with the same cache policy) instead of into two register stages, and
+//   each pack is read back with ds_read_b128 one pack before it is consumed: the loads of the packs ahead need no
+//   registers, and the register cap's AGPR overflow goes.  Same chunk map, same body, same bits.
 template <class T, int MM, bool NT, bool SPEC, bool OFF32 = false, int XR = 0, int UNI = 0, int TRIAL = 0,
-          int FAM = FAM_HEADLINE, int PP = 0>
+          int FAM = FAM_HEADLINE, int PP = 0, int LQ = 0>
 __global__ void __launch_bounds__(BLOCK)
 k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x,
                 const T* __restrict__ res_prev, ElemParams<T> P, T gamma, T* __restrict__ x_d,
@@ -3223,15 +3262,22 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
     constexpr int DEPTH = NSTREAMS <= 11 ? 2 : 1;
     constexpr bool NTP = NT && PP == 0;      // (the policy of q and b)
     struct Stage { Pack<T> q, b, mu, muy, px, ps[MM], xt, gu, glo, ghi, dlo, dhi; };
+    // the streams of one pack with a compile-time list (the headline family's): f(its Stage member, base, policy),
+    // in the order both the register pipeline and the LDS ring load them
+    using PolQB = std::integral_constant<bool, NTP>;
+    using PolNT = std::integral_constant<bool, NT>;
+    auto for_fixed_streams = [&](Stage& S, auto&& f) {
+        if (fk == BZ_F_DIAG_QUADRATIC) { f(S.q, P.q, PolQB{}); f(S.b, P.b, PolQB{}); }
+        if (uni < 1) f(S.mu, P.mu, PolNT{});
+        if (uni < 2) f(S.muy, P.muy, PolNT{});
+        f(S.px, x, PolNT{});
+        if (trial) f(S.xt, (const T*)x_d, PolNT{});
+#pragma unroll
+        for (int i = 0; i < MM; ++i) f(S.ps[i], V.S[i], PolNT{});
+    };
     auto load_stage = [&](Stage& S, unsigned bo) {
         asm volatile("" : "+v"(bo));
-        if (fk == BZ_F_DIAG_QUADRATIC) { S.q = ldo<T, NTP>(P.q, bo); S.b = ldo<T, NTP>(P.b, bo); }
-        if (uni < 1) S.mu = ldo<T, NT>(P.mu, bo);
-        if (uni < 2) S.muy = ldo<T, NT>(P.muy, bo);
-        S.px = ldo<T, NT>(x, bo);
-        if (trial) S.xt = ldo<T, NT>((const T*)x_d, bo);
-#pragma unroll
-        for (int i = 0; i < MM; ++i) S.ps[i] = ldo<T, NT>(V.S[i], bo);
+        for_fixed_streams(S, [&](Pack<T>& d, const T* p, auto pol) { d = ldo<T, decltype(pol)::value>(p, bo); });
         if constexpr (GKC == FAM_G_L1BOX) S.gu = ldo<T, NT>(P.g_u, bo);
         if constexpr (GKC == FAM_G_INDBOX_VEC) {
             S.glo = P.g_lo_vec ? ldo<T, NT>(P.g_lo_vec, bo) : splat(P.g_lo);
@@ -3424,7 +3470,85 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
         auto fetch = [&](Stage& S, int64_t k) { load_stage(S, (unsigned)(clampc(k) * N * (int64_t)sizeof(T))); };
         auto use = [&](const Stage& S, int64_t k) { body(k * N, std::integral_constant<int, N>{}, std::true_type{}, S); };
         Stage sa, sb;
-        if constexpr (DEPTH == 2) {
+        if constexpr (LQ) {
+            // LDS ring of LQ_R slots per wave, one slot = one pack of every stream (stream j at j KiB, lane-linear).  Each
+            // pack is read out of the ring into registers one pack before it is consumed (two register stages, the loop
+            // unrolled by two), so the ds_read latency hides behind the previous pack's arithmetic; LQ_R - 2 packs'
+            // loads stay in flight across every wait.  A slot is refilled two iterations after it was read.
+            static_assert(FAM == FAM_HEADLINE && N * sizeof(T) == 16, "the LDS ring serves the headline family's 16-byte packs");
+            constexpr int SLOTB = NSTREAMS * 64 * 16;
+            constexpr int LQ_R = std::min(4, (160 * 1024 - 2048) / (WAVES * SLOTB));      // (2 KiB: epilogue scratch)
+            static_assert(LQ_R >= 3 && (LQ_R - 2) * NSTREAMS <= 63, "ring depth / vmcnt range");
+            constexpr int NQB = 2, NNT = NSTREAMS - NQB;      // q, b first (their own policy), then the non-temporal streams
+            __shared__ __attribute__((aligned(16))) unsigned char lq_ring[WAVES * LQ_R * SLOTB];
+            const unsigned wave_off = (threadIdx.x >> 6) * (unsigned)(LQ_R * SLOTB);
+            const unsigned ring_lds = (unsigned)(uintptr_t)lq_ring + wave_off;      // (LDS byte address: the low 32 bits)
+            const unsigned lane_off = (threadIdx.x & 63) * 16u;
+            // the stream bases in slot order, each lowered by its offset inside its group of four (see glds16x)
+            const void* lq_base[NSTREAMS];
+            {
+                int j = 0;
+                Stage none;
+                for_fixed_streams(none, [&](Pack<T>&, const T* p, auto) {
+                    const int g = j < NQB ? j : (j - NQB) % 4;
+                    lq_base[j++] = (const void*)((uintptr_t)p - 1024u * (unsigned)g);
+                });
+            }
+            auto lq_fetch = [&](unsigned slot, int64_t k) {
+                unsigned bo = (unsigned)(clampc(k) * N * (int64_t)sizeof(T));
+                asm volatile("" : "+v"(bo));
+                asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");      // (the slot's last reads have returned)
+                const unsigned dst = ring_lds + slot;
+                static_assert(fam_fk(FAM) == FAM_F_DIAG, "q and b lead the slot");
+                glds16x<NTP, NQB>(lq_base, bo, dst);
+#pragma unroll
+                for (int g = 0; g < NNT; g += 4) {
+                    const unsigned d = dst + 1024u * (unsigned)(NQB + g);
+                    if (NNT - g >= 4) glds16x<NT, 4>(lq_base + NQB + g, bo, d);
+                    else if (NNT - g == 3) glds16x<NT, 3>(lq_base + NQB + g, bo, d);
+                    else if (NNT - g == 2) glds16x<NT, 2>(lq_base + NQB + g, bo, d);
+                    else glds16x<NT, 1>(lq_base + NQB + g, bo, d);
+                }
+            };
+            auto lq_read = [&](Stage& S, unsigned slot) {
+                const unsigned char* src = lq_ring + wave_off + slot + lane_off;
+                for_fixed_streams(S, [&](Pack<T>& d, const T*, auto) {
+                    const typename PackVec<T>::type v = *reinterpret_cast<const typename PackVec<T>::type*>(src);
+#pragma unroll
+                    for (int e = 0; e < N; ++e) d.v[e] = v[e];
+                    src += 1024;
+                });
+            };
+            // pack k's loads are complete once no more than the LQ_R - 2 newer packs' loads are outstanding (the
+            // stores issued in between are not counted: they only make the wait longer)
+            auto lq_wait = [&]() { asm volatile("s_waitcnt vmcnt(%0)" ::"n"((LQ_R - 2) * NSTREAMS) : "memory"); };
+            auto next_slot = [](unsigned s) { return s + SLOTB == (unsigned)(LQ_R * SLOTB) ? 0u : s + SLOTB; };
+            if (c < nfull) {
+#pragma unroll
+                for (int r = 0; r < LQ_R - 1; ++r) lq_fetch(r * SLOTB, c + r * stride);
+            }
+            if (gate_late) {
+                if (!gate_wait()) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
+            }
+            // sc: the slot of chunk c (already in registers), sn: the slot chunk c + (LQ_R - 1) stride is loaded into
+            unsigned sc = 0, sn = (LQ_R - 1) * SLOTB;
+            if (c < nfull) { lq_wait(); lq_read(sa, sc); }
+            auto step = [&](const Stage& cur, Stage& nxt) {
+                lq_fetch(sn, c + (LQ_R - 1) * stride);
+                lq_wait();
+                sc = next_slot(sc); sn = next_slot(sn);
+                lq_read(nxt, sc);      // chunk c + stride (past the end: a clamped, valid re-request, never consumed)
+                use(cur, c);
+                c += stride;
+            };
+            for (;;) {
+                if (c >= nfull) break;
+                step(sa, sb);
+                if (c >= nfull) break;
+                step(sb, sa);
+            }
+            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // nothing may land in the ring after the wave ends
+        } else if constexpr (DEPTH == 2) {
             // two packs ahead: with one, a wave has 8..10 KB in flight and the pass is bound by latency x concurrency
             // (three stages used in rotation, the loop unrolled by three: no register copies between iterations)
             Stage sc;

@@ -835,6 +835,7 @@ template <class T> class Solver final : public SolverBase {
     int slackdepth_env_ = 1;     // BZ_SLACKDEPTH=0: ... without the one-pack-ahead register pipeline (232 against 227 us per pass)
     int nt_env_ = -1;            // BZ_NT: -1 (default) non-temporal streams by working-set size, 0 / 1 forced
     int keepp_env_ = -1;         // BZ_KEEPP: -1 (default) q and b of the headline pass cacheable by size (keep_params), 0 / 1 forced
+    int ldsq_env_ = -1;          // BZ_LDSQ: -1 (default) / 1 the non-temporal headline pass streams through its LDS ring (lds_ring), 0 off
     int famrt_env_ = 0;          // BZ_FAMRT=1: the headline family through its family-table instantiation (run-time UNI / TRIAL)
     bool sy_stale_ = false;      // S_/Y_ do not hold the stored pairs (they live in the rings)
     bool rh_stale_ = false;      // ... and the residual ring was not written either during this run
@@ -987,11 +988,12 @@ template <class T> class Solver final : public SolverBase {
         T* xd;
         double gam0, gamma;
         int uni, gfc, fam, m_now;
-        bool nt, table, keep_params;
+        bool nt, table, keep_params, lds_ring;
         bool operator==(const GatePlan& o) const {
             for (int i = 0; i < CM; ++i) if (S[i] != o.S[i]) return false;
             return x == o.x && xd == o.xd && gam0 == o.gam0 && gamma == o.gamma && uni == o.uni && gfc == o.gfc &&
-                   fam == o.fam && m_now == o.m_now && nt == o.nt && table == o.table && keep_params == o.keep_params;
+                   fam == o.fam && m_now == o.m_now && nt == o.nt && table == o.table && keep_params == o.keep_params &&
+                   lds_ring == o.lds_ring;
         }
     };
     // The headline pass's invariant parameter streams q and b through the Infinity Cache (k_fused_compact<..., PP = 1>:
@@ -1003,6 +1005,9 @@ template <class T> class Solver final : public SolverBase {
         if (!nt || table || fam != FAM_HEADLINE) return false;
         return keepp_env_ >= 0 ? keepp_env_ != 0 : (double)n * sizeof(T) * 2 <= KEEP_PARAMS_BYTES;
     }
+    // The non-temporal headline pass (fp64) loads its packs ahead into a per-wave LDS ring instead of two register stages
+    // (k_fused_compact<..., LQ = 1>): the LDS read one pack ahead of use, 246 VGPRs instead of 256 + 18 AGPRs.
+    bool lds_ring(bool nt, bool table) const { return sizeof(T) == 8 && nt && !table && ldsq_env_ != 0; }
     // The early launch goes on the OTHER of two streams, so that it is dispatched (and, registers permitting, resident)
     // while the current pass still runs instead of queueing behind the read-back kernel; when it is released the
     // solver's launches move over to that stream (everything on the old one has completed by then: the host has the
@@ -1056,6 +1061,7 @@ template <class T> class Solver final : public SolverBase {
         pl.nt = nt_env >= 0 ? nt_env != 0 : (double)n * sizeof(T) * streams > 340e6;
         pl.table = !(spec_env && fam == FAM_HEADLINE) || famrt_env_;
         pl.keep_params = keep_params(pl.nt, pl.table, fam);
+        pl.lds_ring = lds_ring(pl.nt, pl.table);
         return true;
     }
     void gate_launch(const GatePlan& pl, CompactCoef<CM> C2, T* zarg, bool trial_unused = false) {
@@ -1078,11 +1084,17 @@ template <class T> class Solver final : public SolverBase {
                    (T*)nullptr, n, parts_.p, (int)SL_TRIAL);
         } else {
             form_[C_FUSED_IT] = std::string("k_fused_compact<XR=2,UNI=") + char('0' + pl.uni) + (pl.nt ? ",NT=1" : ",NT=0") + ",TRIAL=0" +
-                                (pl.keep_params ? ",PP=1>" : ">");
-#define BZ_LAUNCH_G(NT_, UNI_, PP_)                                                                               \
-    launch(C_FUSED_IT, k_fused_compact<T, CM, NT_, true, true, 2, UNI_, 0, FAM_HEADLINE, PP_>, pl.gfc, XV, C2, pl.x, \
-           (const T*)nullptr, P, gam, pl.xd, zarg, (T*)nullptr, (T*)nullptr, (T*)nullptr, n, parts_.p, (int)SL_TRIAL)
-            if (pl.nt && pl.keep_params) { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 1); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 1); else BZ_LAUNCH_G(true, 0, 1); }
+                                (pl.keep_params ? ",PP=1" : "") + (pl.lds_ring ? ",LQ=1>" : ">");
+#define BZ_LAUNCH_G(NT_, UNI_, PP_, ...)                                                                          \
+    launch(C_FUSED_IT, k_fused_compact<T, CM, NT_, true, true, 2, UNI_, 0, FAM_HEADLINE, PP_, ##__VA_ARGS__>, pl.gfc, XV, C2, \
+           pl.x, (const T*)nullptr, P, gam, pl.xd, zarg, (T*)nullptr, (T*)nullptr, (T*)nullptr, n, parts_.p, (int)SL_TRIAL)
+            if (pl.lds_ring) {      // (fp64 only: lds_ring)
+                if constexpr (sizeof(T) == 8) {
+                    if (pl.keep_params) { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 1, 1); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 1, 1); else BZ_LAUNCH_G(true, 0, 1, 1); }
+                    else { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 0, 1); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 0, 1); else BZ_LAUNCH_G(true, 0, 0, 1); }
+                }
+            }
+            else if (pl.nt && pl.keep_params) { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 1); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 1); else BZ_LAUNCH_G(true, 0, 1); }
             else if (pl.nt) { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 0); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 0); else BZ_LAUNCH_G(true, 0, 0); }
             else { if (pl.uni == 2) BZ_LAUNCH_G(false, 2, 0); else if (pl.uni == 1) BZ_LAUNCH_G(false, 1, 0); else BZ_LAUNCH_G(false, 0, 0); }
 #undef BZ_LAUNCH_G
@@ -2292,6 +2304,7 @@ template <class T> class Solver final : public SolverBase {
         famrt_env_ = std::getenv("BZ_FAMRT") ? std::atoi(std::getenv("BZ_FAMRT")) : 0;
         nt_env_ = std::getenv("BZ_NT") ? std::atoi(std::getenv("BZ_NT")) : -1;
         keepp_env_ = std::getenv("BZ_KEEPP") ? std::atoi(std::getenv("BZ_KEEPP")) : -1;
+        ldsq_env_ = std::getenv("BZ_LDSQ") ? std::atoi(std::getenv("BZ_LDSQ")) : -1;
         slackfast_env_ = std::getenv("BZ_SLACKFAST") ? std::atoi(std::getenv("BZ_SLACKFAST")) : 1;
         slackkind_env_ = std::getenv("BZ_SLACKKIND") ? std::atoi(std::getenv("BZ_SLACKKIND")) : 1;
         densesmall_env_ = std::getenv("BZ_DENSESMALL") ? std::atoi(std::getenv("BZ_DENSESMALL")) : 1;
@@ -2599,7 +2612,7 @@ template <class T> class Solver final : public SolverBase {
         bool img_trial = false;      // grad L (and f) at the trial point x + d are affine images, not evaluations
         // a backtracked trial point can go through the one-pass kernel too ("trial given" variant) when this
         // iteration's first trial did: what that launch used is kept here
-        bool trial_ok = false, trial_nt = false, trial_keep = false;
+        bool trial_ok = false, trial_nt = false, trial_keep = false, trial_lq = false;
         bool head_on = false, head_fb = false;      // cfg 4: k_dense_head serves this iteration ; ... and has made the FB step of its first trial
         bool state_imgs = false, halved_here = false;      // cfg 4: the state's images are valid ; gamma was halved inside this step
         int trial_uni = 0, trial_gfc = 0, trial_fam = -1;
@@ -2720,6 +2733,7 @@ template <class T> class Solver final : public SolverBase {
                 cur.x = X_[xp].p; cur.xd = X_[xd].p; cur.gam0 = CC.gam0; cur.gamma = (double)gamma; cur.uni = uni; cur.gfc = gfc;
                 cur.fam = fam; cur.m_now = m_now; cur.nt = nt; cur.table = table;
                 cur.keep_params = keep_params(nt, table, fam);
+                cur.lds_ring = lds_ring(nt, table);
                 if (gate_pending_ && cur == gate_plan_) {
                     // this very launch was made early, behind the previous iteration's read-back: hand it its coefficients
                     gate_release(CC, zstore);
@@ -2735,7 +2749,7 @@ template <class T> class Solver final : public SolverBase {
                 sy_stale_ = true; rh_stale_ = true; res_skipped = true;
                 const int tf_now = trialfuse_env_;
                 trial_ok = tf_now != 0; trial_nt = nt; trial_uni = uni; trial_gfc = gfc; trial_XV = XV; trial_CC = CC;
-                trial_table = table; trial_fam = fam; trial_keep = cur.keep_params;
+                trial_table = table; trial_fam = fam; trial_keep = cur.keep_params; trial_lq = cur.lds_ring;
             } else if (xr) {
                 CompactVecs<T, CM> XV;
                 XV.m = CM;
@@ -3113,9 +3127,9 @@ template <class T> class Solver final : public SolverBase {
                 // the blended point through the one-pass kernel: given in X_[xb], evaluated against the same ring
                 // of iterates; z and res of the new state are stored (Z_[zn], RES_[rn])
                 for (int kk = 0; kk < NFC; ++kk) slot_n[SL_TRIAL + kk] = trial_gfc;
-#define BZ_LAUNCH_FCT(NT_, UNI_, PP_)                                                                             \
-    launch(C_FUSED_IT, k_fused_compact<T, CM, NT_, true, true, 2, UNI_, 1, FAM_HEADLINE, PP_>, trial_gfc, trial_XV, trial_CC, \
-           (const T*)X_[xp].p, (const T*)nullptr, P, gamma, X_[xb].p, Z_[zn].p, RES_[rn].p, (T*)nullptr,         \
+#define BZ_LAUNCH_FCT(NT_, UNI_, PP_, ...)                                                                        \
+    launch(C_FUSED_IT, k_fused_compact<T, CM, NT_, true, true, 2, UNI_, 1, FAM_HEADLINE, PP_, ##__VA_ARGS__>, trial_gfc, trial_XV, \
+           trial_CC, (const T*)X_[xp].p, (const T*)nullptr, P, gamma, X_[xb].p, Z_[zn].p, RES_[rn].p, (T*)nullptr,         \
            (T*)nullptr, n, parts_.p, (int)SL_TRIAL)
                 // the iterates, the parameter vectors (mu, mu*y unless numbers), the trial point ; z, res
                 mv((m_at_trial + 1) + pstreams(true, true, true) + 1 + 2);
@@ -3127,8 +3141,14 @@ template <class T> class Solver final : public SolverBase {
                            X_[xb].p, Z_[zn].p, RES_[rn].p, (T*)nullptr, (T*)nullptr, n, parts_.p, (int)SL_TRIAL);
                 } else {
                 form_[C_FUSED_IT] = std::string("k_fused_compact<XR=2,UNI=") + char('0' + trial_uni) + (trial_nt ? ",NT=1" : ",NT=0") + ",TRIAL=1" +
-                                    (trial_keep ? ",PP=1>" : ">");
-                if (trial_nt && trial_keep) { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 1); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 1); else BZ_LAUNCH_FCT(true, 0, 1); }
+                                    (trial_keep ? ",PP=1" : "") + (trial_lq ? ",LQ=1>" : ">");
+                if (trial_lq) {      // (fp64 only: lds_ring)
+                    if constexpr (sizeof(T) == 8) {
+                        if (trial_keep) { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 1, 1); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 1, 1); else BZ_LAUNCH_FCT(true, 0, 1, 1); }
+                        else { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 0, 1); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 0, 1); else BZ_LAUNCH_FCT(true, 0, 0, 1); }
+                    }
+                }
+                else if (trial_nt && trial_keep) { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 1); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 1); else BZ_LAUNCH_FCT(true, 0, 1); }
                 else if (trial_nt) { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 0); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 0); else BZ_LAUNCH_FCT(true, 0, 0); }
                 else { if (trial_uni == 2) BZ_LAUNCH_FCT(false, 2, 0); else if (trial_uni == 1) BZ_LAUNCH_FCT(false, 1, 0); else BZ_LAUNCH_FCT(false, 0, 0); }
                 }
