@@ -543,9 +543,9 @@ __device__ __forceinline__ T prox_elem(int g_kind, T y, T gl, T u, T lo, T hi, T
         break;
     }
     case BZ_G_NORM_L1_BOX: {        // normL1Box.jl:30-39  max(0, min(x-gl, u))
-        T a = y - gl;
-        a = a < u ? a : u;          // min(x-gl, u)
-        z = a > T(0) ? a : T(0);    // max(0, .)
+        T a = y - gl;               // (Julia's min and max return a NaN argument: so do these)
+        a = (a < u || a != a) ? a : u;          // min(x-gl, u)
+        z = (a > T(0) || a != a) ? a : T(0);    // max(0, .)
         gterm = z;
         break;
     }

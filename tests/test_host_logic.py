@@ -235,3 +235,56 @@ def test_dense_ring_kernel_has_no_spill_code_and_exact_waits():
     r = subprocess.run([sys.executable, os.path.join(ROOT, "tools", "check_dense_ring.py")], capture_output=True, text=True, timeout=600)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-2000:]
     assert r.stdout.count(" 0 findings") == 5, r.stdout
+
+
+def test_family_table_is_complete():
+    """Every oracle family has its one-pass instantiations (bz_families.inc, one translation unit per D class and
+    type), the host dispatches every D class to them, and the family codes the GPU tests expect are the header's:
+    a missing instantiation shows up here, not as "no one-pass kernel instantiation" on the GPU."""
+    import itertools
+    import os
+    import re
+    import subprocess
+    from tests.test_gpu_family_table import FAM_D, FAM_F, FAM_G, fam_code
+    csrc = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "bazinga.jl_amd", "csrc")
+    src = lambda name: open(os.path.join(csrc, name)).read()
+    hdr = src("bz_kernels.h")
+    # the kinds: the Python names of the tests against the header's constants
+    consts = {k: int(v) for k, v in re.findall(r"\b(FAM_[FGD]_[A-Z0-9_]+)\s*=\s*(\d+)", hdr)}
+    names = {"F": {"zero": "ZERO", "diag": "DIAG"},
+             "G": {"zero": "ZERO", "l1": "L1", "nonneg": "L1NONNEG", "l1box": "L1BOX", "indbox": "INDBOX",
+                   "indbox_vec": "INDBOX_VEC"},
+             "D": {"zero": "ZERO", "free": "FREE", "box": "BOX", "box_vec": "BOX_VEC", "vc": "VC", "cc": "CC",
+                   "eitheror": "EITHEROR", "xor": "XOR"}}
+    kinds = {"F": {k: v for k, v in consts.items() if k.startswith("FAM_F_")},
+             "G": {k: v for k, v in consts.items() if k.startswith("FAM_G_") and k != "FAM_G_COUNT"},
+             "D": {k: v for k, v in consts.items() if k.startswith("FAM_D_") and k != "FAM_D_COUNT"}}
+    for c, py in (("F", FAM_F), ("G", FAM_G), ("D", FAM_D)):
+        assert {"FAM_%s_%s" % (c, names[c][k]): v for k, v in py.items()} == kinds[c], c
+    assert consts["FAM_G_COUNT"] == len(FAM_G) and consts["FAM_D_COUNT"] == len(FAM_D)
+    m = re.search(r"constexpr int fam_code\(int fk, int gk, int dk\) \{ return ([^;]+); \}", hdr)
+    assert m, "fam_code not found in bz_kernels.h"
+    for fk, gk, dk in itertools.product(FAM_F.values(), FAM_G.values(), FAM_D.values()):
+        assert eval(m.group(1), {}, {"fk": fk, "gk": gk, "dk": dk}) == fam_code(fk, gk, dk)
+    assert len({fam_code(*t) for t in itertools.product(FAM_F.values(), FAM_G.values(), FAM_D.values())}) == 96
+    # both switches of bz_families.inc (the compile-time UNI one and the run-time UNI / TRIAL one) list all 12 (f, g)
+    inc = re.sub(r"#define BZ_FAM\(FK, GK\)[^\n]*(\\\n[^\n]*)*", "", src("bz_families.inc"))
+    blocks = re.findall(r"switch \(fam\) \{(.*?)#undef BZ_FAM", inc, re.S)
+    assert len(blocks) == 2, len(blocks)
+    want = {("FAM_F_" + f, "FAM_G_" + g) for f in names["F"].values() for g in names["G"].values()}
+    for b in blocks:
+        got = re.findall(r"BZ_FAM\((FAM_F_\w+), (FAM_G_\w+)\)", b)
+        assert len(got) == len(set(got)) and set(got) == want, sorted(want ^ set(got))
+    # one translation unit per D class and type, each built by the Makefile
+    built = subprocess.run(["make", "-n", "-B", "-C", csrc], capture_output=True, text=True, timeout=120).stdout
+    for k, (t, ty) in itertools.product(range(8), (("f32", "float"), ("f64", "double"))):
+        name = "bz_families_dk%d_%s.hip" % (k, t)
+        text = src(name)
+        assert re.search(r"#define BZ_FAMILY_DK %d\b" % k, text) and re.search(r"#define BZ_FAMILY_T %s\b" % ty, text), name
+        assert '#include "bz_families.inc"' in text, name
+        assert re.search(r"-c %s\b" % re.escape(name), built), name + " is not compiled by the Makefile"
+    # the host's dispatch: every D class to its translation unit
+    body = re.search(r"FusedFn<T> family_kernel\(int fam, bool nt, int uni\) \{(.*?)\n\}", src("bz_solver.hip"), re.S)
+    assert body, "family_kernel not found in bz_solver.hip"
+    for d in kinds["D"]:
+        assert re.search(r"case %s: return family_kernel_dk<T, %s>\(fam, nt, uni\);" % (d, d), body.group(1)), d
