@@ -20,6 +20,7 @@
 #include <cstring>
 #include <limits>
 #include <optional>
+#include <tuple>
 #include <type_traits>
 
 namespace bz {
@@ -119,9 +120,70 @@ enum Cat : int { C_TWOLOOP = 0, C_FUSED = 1, C_ALGRAD = 2, C_FB = 3, C_UPDATE = 
                  C_COLLECT = 5, C_GATHER = 6, C_MISC = 7, C_DOT = 8, C_GEMV = 9, C_PERSIST = 10, C_GEMV_MFMA = 11, C_FUSED_IT = 12,
                  C_STENCIL_FB = 13, C_STENCIL_UPD = 14, C_XD = 15 };
 
+// ---------------------------------------------------------------------------
+// Environment knobs (development aids).  Each variable is parsed here, and only here, with the default that
+// is measured, at one of three moments: when the problem is created (CreateKnobs), at every bz_panoc_begin (BeginKnobs),
+// at every AugLagUpdate! (BZ_UNI).  Constructing a table reads the environment; a table is not changed afterwards: what
+// the solver switches at run time (gate_env_ after a gate fallback, the withheld gate release) has members of its own.
+static int env_int(const char* name, int dflt) { const char* e = std::getenv(name); return e ? std::atoi(e) : dflt; }
+static long long env_ll(const char* name, long long dflt) { const char* e = std::getenv(name); return e ? std::atoll(e) : dflt; }
+static std::optional<int> env_opt(const char* name) { const char* e = std::getenv(name); return e ? std::optional<int>(std::atoi(e)) : std::nullopt; }
+struct CreateKnobs {
+    std::optional<int> grid = env_opt("BZ_GRID");                        // grid of the streaming kernels
+    std::optional<int> persist_blocks = env_opt("BZ_PERSIST_BLOCKS");    // the persistent kernel on b CUs (two ranks on one GPU)
+    int dense_fused = env_int("BZ_DENSE_FUSED", 1);      // 0: the dense constraint through two products, not k_dense_fused
+    std::optional<int> dense_kp = env_opt("BZ_DENSE_KP");                // k_dense_fused's packs per row and lane
+    // test-only
+    int test_dense_timeout = env_int("BZ_TEST_DENSE_TIMEOUT", 0);        // the k-th k_dense_fused exchange is sabotaged
+    unsigned dense_spin = (unsigned)env_ll("BZ_DENSE_SPIN", 0);          // k_dense_fused's poll bound (0: the default)
+};
+struct BeginKnobs {
+    explicit BeginKnobs(int nranks) : gate(env_int("BZ_GATE", nranks > 1 ? 0 : 1)) {}
+    int gate;                                    // BZ_GATE: gated pre-launch off (0) / on the solver's stream (1) / a second one (2)
+    int xr = env_int("BZ_XR", 2);                // one-pass pass on the stored pairs (0) / history as iterates (1) / residuals re-evaluated (2)
+    int skipz = env_int("BZ_SKIPZ", 1);          // 0: the one-pass pass always stores z
+    int gfc = env_int("BZ_GFC", 0);              // k_fused_compact on k workgroups per CU (0: the per-form default)
+    int trialfuse = env_int("BZ_TRIALFUSE", 1);  // 0: a tau-backtracked point finishes in the generic kernels
+    int fused_begin = env_int("BZ_FUSED_BEGIN", 1);      // 0: the start of a solve (and ensure_z) in the generic kernels
+    int slackfast = env_int("BZ_SLACKFAST", 1);  // 0: the slack iterate-history pass always in its run-time-kinds instantiation
+    int slackkind = env_int("BZ_SLACKKIND", 1);  // 0: ... its fast instantiations with run-time kinds of g and D
+    int slackdepth = env_int("BZ_SLACKDEPTH", 1);        // 0: ... without the one-pack-ahead register pipeline (232 against 227 us per pass)
+    int suc_grid = env_int("BZ_SUC_GRID", 1);    // k_stencil_update_c on k workgroups per CU (0: the problem's grid)
+    int stencil_regx = env_int("BZ_STENCIL_REGX", 1);    // cfg 3's second pass reads res and grad L(x_d) (0) / re-forms res (1) / both (2)
+    int affine_blend = env_int("BZ_AFFINE_BLEND", 1);    // 0: a tau-backtracked point of cfg 4 always evaluated with a pass over A
+    int densesmall = env_int("BZ_DENSESMALL", 1);        // 0: cfg 4's short kernels around the pass over A as launches of their own
+    int nt = env_int("BZ_NT", -1);               // non-temporal streams by working-set size (-1) / forced off (0) or on (1)
+    int keepp = env_int("BZ_KEEPP", -1);         // q and b of the headline pass cacheable by size (-1, keep_params) / forced
+    int ldsq = env_int("BZ_LDSQ", -1);           // the non-temporal fp64 headline pass through its LDS ring (-1, 1) / not (0)
+    int famrt = env_int("BZ_FAMRT", 0);          // 1: the headline family through its family-table instantiation
+    int famct = env_int("BZ_FAMCT", 1);          // 0: family kernels always in the run-time UNI / TRIAL instantiation
+    int spec = env_int("BZ_SPEC", 1);            // 0: k_fused_compact always in its generic instantiation (run-time kinds)
+    int off32 = env_int("BZ_OFF32", 1);          // 0: k_fused_compact with 64-bit per-stream addresses
+    int xdnt = env_int("BZ_XDNT", 1);            // 0: k_compact_xd, k_stencil_fb, k_stencil_update_c never non-temporal
+    int affine = env_int("BZ_AFFINE", -1);       // overrides bz_panoc_opts.affine_refresh (-1: no override)
+    int gatelate = env_int("BZ_GATELATE", 1);    // 0: the gated launch goes to its gate before issuing any load
+    int collect_wave = env_int("BZ_COLLECT_WAVE", 1);    // 0: read-back with one 256-thread workgroup per scalar, not one wave
+    bool gemv_valu = std::getenv("BZ_GEMV_VALU") != nullptr;     // set: A'v (fp32) on the vector ALUs, not the MFMA form
+    long long persist_min_n = env_ll("BZ_PERSIST_MIN_N", 300000);        // the length from which the persistent kernel runs
+    // test-only
+    bool test_persist_timeout = env_int("BZ_TEST_PERSIST_TIMEOUT", 0) != 0;      // the persistent kernel's barrier misses its target
+    int test_gate_timeout = env_int("BZ_TEST_GATE_TIMEOUT", 0);  // the k-th gate release is withheld
+    unsigned gate_spin = (unsigned)env_ll("BZ_GATE_SPIN", 0);    // poll bound of a gated launch's workgroup 0 (0: the default)
+};
+static int read_uni_knob() { return env_int("BZ_UNI", 2); }      // BZ_UNI=0|1|2, read at every AugLagUpdate! (tests toggle it)
+
+// f(c) with the run-time value as a compile-time constant c (kernel template arguments): a bool, or a UNI (2, 1, else 0)
+template <class F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <class F> static void with_uni(int u, F&& f) {
+    if (u >= 2) f(std::integral_constant<int, 2>{});
+    else if (u == 1) f(std::integral_constant<int, 1>{});
+    else f(std::integral_constant<int, 0>{});
+}
+
 template <class T> class Solver final : public SolverBase {
    public:
-    Solver(Ctx* c, const bz_problem_desc& d) : ctx(c), desc(d), n(d.n), ny(d.ny), nx(d.n), slack(d.slack != 0) {
+    Solver(Ctx* c, const bz_problem_desc& d)
+        : ctx(c), desc(d), n(d.n), ny(d.ny), nx(d.n), slack(d.slack != 0), env_(c->nranks) {
         cur_ = ctx->stream;
         if (n <= 0 || ny < 0) throw Error(BZ_ERR_ARG, "n must be positive");
         if (d.c_kind == BZ_C_IDENTITY && ny != n)
@@ -199,7 +261,7 @@ template <class T> class Solver final : public SolverBase {
             num_cus = prop.multiProcessorCount;
             pblocks = num_cus;
             // BZ_PERSIST_BLOCKS: run the persistent kernel on fewer CUs (two ranks sharing one GPU in tests)
-            if (const char* e = getenv("BZ_PERSIST_BLOCKS")) pblocks = std::max(1, std::min(num_cus, atoi(e)));
+            if (cenv_.persist_blocks) pblocks = std::max(1, std::min(num_cus, *cenv_.persist_blocks));
             // persistent two-loop: one 512-thread block per CU, KR register packs per thread; its vectors
             // are zero-padded to KR*num_cus*512 packs so that every round is in-bounds (no masks)
             const int64_t kneed = (nchunks + (int64_t)pblocks * PBLOCK - 1) / ((int64_t)pblocks * PBLOCK);
@@ -212,7 +274,7 @@ template <class T> class Solver final : public SolverBase {
             if (persist_kr) vcap = std::max<int64_t>(n, (int64_t)persist_kr * pblocks * PBLOCK * PackN<T>::N);
         }
         int g = (int)std::min<int64_t>(PSTRIDE, std::max<int64_t>(1, (nchunks + BLOCK - 1) / BLOCK));
-        if (const char* e = getenv("BZ_GRID")) g = std::max(1, std::min(PSTRIDE, atoi(e)));
+        if (cenv_.grid) g = std::max(1, std::min(PSTRIDE, *cenv_.grid));
         grid = g;
         const int64_t nychunks = (ny + PackN<T>::N - 1) / PackN<T>::N;
         grid_y = (int)std::min<int64_t>(grid, std::max<int64_t>(1, (nychunks + BLOCK - 1) / BLOCK));
@@ -683,6 +745,8 @@ template <class T> class Solver final : public SolverBase {
     int64_t n, ny;
     int64_t nx;                              // length of x (== n unless slack: then n = nx + ny)
     bool slack;
+    const CreateKnobs cenv_;                 // the knobs read when the problem was created
+    BeginKnobs env_;                         // ... at the last bz_panoc_begin (at creation before the first)
     int grid = 1, grid_y = 1;
     ElemParams<T> P;
     DBuf<T> q_, b_, gu_, glo_, ghi_, dlo_, dhi_, mu_, muy_, ymul_, sproj_;
@@ -795,7 +859,6 @@ template <class T> class Solver final : public SolverBase {
         return V;
     }
     bool persist_broken_ = false;            // a grid barrier timed out once on this problem: the kernel chain from then on
-    bool persist_sabotage_ = false;          // BZ_TEST_PERSIST_TIMEOUT=1: make the barrier miss its target (tests the fallback)
     std::vector<DBuf<T>> S_, Y_;
     DBuf<double> parts_, alphas_, send_, recv_;
     double* host_out_ = nullptr;             // pinned mailbox: {value, ticket} per collected scalar
@@ -824,19 +887,6 @@ template <class T> class Solver final : public SolverBase {
     // stops writing res as well: reads CM+1 iterates + q, b, mu, mu*y, writes x_d.  Same operations on the
     // same inputs as when each residual was first computed -> the same bits.
     int xr_run_ = 0;             // consecutive plain, pair-inserting iterations so far
-    int xr_env_ = 2, skipz_env_ = 1;     // BZ_XR / BZ_SKIPZ, read at every bz_panoc_begin (tests toggle them)
-    int gfc_env_ = 0, trialfuse_env_ = 1, fused_begin_env_ = 1;      // BZ_GFC / BZ_TRIALFUSE / BZ_FUSED_BEGIN, likewise
-    int slackfast_env_ = 1;      // BZ_SLACKFAST=0: the slack iterate-history pass always in its run-time-kinds instantiation
-    int suc_grid_env_ = 1;       // BZ_SUC_GRID=k: k_stencil_update_c on k workgroups per CU (default 1; 0: the problem's grid)
-    int stencil_regx_env_ = 1;   // BZ_STENCIL_REGX=0|1|2: cfg 3's second pass reads res and grad L(x_d) / re-forms res (default) / re-forms both (slower)
-    int affblend_env_ = 1;       // BZ_AFFINE_BLEND=0: a tau-backtracked point of cfg 4 is always evaluated with a pass over A (no images)
-    int densesmall_env_ = 1;     // BZ_DENSESMALL=0: cfg 4's short kernels either side of the pass over A as launches of their own (k_dense_head / k_dense_tail off)
-    int slackkind_env_ = 1;      // BZ_SLACKKIND=0: its fast instantiations with run-time kinds of g and D
-    int slackdepth_env_ = 1;     // BZ_SLACKDEPTH=0: ... without the one-pack-ahead register pipeline (232 against 227 us per pass)
-    int nt_env_ = -1;            // BZ_NT: -1 (default) non-temporal streams by working-set size, 0 / 1 forced
-    int keepp_env_ = -1;         // BZ_KEEPP: -1 (default) q and b of the headline pass cacheable by size (keep_params), 0 / 1 forced
-    int ldsq_env_ = -1;          // BZ_LDSQ: -1 (default) / 1 the non-temporal headline pass streams through its LDS ring (lds_ring), 0 off
-    int famrt_env_ = 0;          // BZ_FAMRT=1: the headline family through its family-table instantiation (run-time UNI / TRIAL)
     bool sy_stale_ = false;      // S_/Y_ do not hold the stored pairs (they live in the rings)
     bool rh_stale_ = false;      // ... and the residual ring was not written either during this run
     double gring_[NXR] = {0};    // the gamma the residual of each iterate in the ring was (or would be) formed with
@@ -982,19 +1032,15 @@ template <class T> class Solver final : public SolverBase {
     double hp_[CM] = {0}, hw_[CM] = {0};
 
     // ---- gated pre-launch of the next iteration's one-pass kernel (see GateRec in bz_kernels.h) ----
-    struct GatePlan {                        // everything the launch needs except the coefficients and the z store
+    struct GatePlan {                        // everything the launch needs except the coefficients and the z address
         const T* S[CM];
         const T* x;
         T* xd;
         double gam0, gamma;
         int uni, gfc, fam, m_now;
         bool nt, table, keep_params, lds_ring;
-        bool operator==(const GatePlan& o) const {
-            for (int i = 0; i < CM; ++i) if (S[i] != o.S[i]) return false;
-            return x == o.x && xd == o.xd && gam0 == o.gam0 && gamma == o.gamma && uni == o.uni && gfc == o.gfc &&
-                   fam == o.fam && m_now == o.m_now && nt == o.nt && table == o.table && keep_params == o.keep_params &&
-                   lds_ring == o.lds_ring;
-        }
+        auto key() const { return std::tie(x, xd, gam0, gamma, uni, gfc, fam, m_now, nt, table, keep_params, lds_ring); }
+        bool operator==(const GatePlan& o) const { return std::equal(S, S + CM, o.S) && key() == o.key(); }
     };
     // The headline pass's invariant parameter streams q and b through the Infinity Cache (k_fused_compact<..., PP = 1>:
     // default-policy loads for them, non-temporal for the ring and x_d) while both fit it.  Bare 6-iterate + q + b + x_d
@@ -1003,11 +1049,11 @@ template <class T> class Solver final : public SolverBase {
     static constexpr double KEEP_PARAMS_BYTES = 256e6;
     bool keep_params(bool nt, bool table, int fam) const {
         if (!nt || table || fam != FAM_HEADLINE) return false;
-        return keepp_env_ >= 0 ? keepp_env_ != 0 : (double)n * sizeof(T) * 2 <= KEEP_PARAMS_BYTES;
+        return env_.keepp >= 0 ? env_.keepp != 0 : (double)n * sizeof(T) * 2 <= KEEP_PARAMS_BYTES;
     }
     // The non-temporal headline pass (fp64) loads its packs ahead into a per-wave LDS ring instead of two register stages
     // (k_fused_compact<..., LQ = 1>): the LDS read one pack ahead of use, 246 VGPRs instead of 256 + 18 AGPRs.
-    bool lds_ring(bool nt, bool table) const { return sizeof(T) == 8 && nt && !table && ldsq_env_ != 0; }
+    bool lds_ring(bool nt, bool table) const { return sizeof(T) == 8 && nt && !table && env_.ldsq != 0; }
     // The early launch goes on the OTHER of two streams, so that it is dispatched (and, registers permitting, resident)
     // while the current pass still runs instead of queueing behind the read-back kernel; when it is released the
     // solver's launches move over to that stream (everything on the old one has completed by then: the host has the
@@ -1038,89 +1084,104 @@ template <class T> class Solver final : public SolverBase {
         gate_abort();
         if (cur_ != ctx->stream) { BZ_HIP(hipStreamSynchronize(cur_)); cur_ = ctx->stream; }
     }
-    // the plan of the iterate-history launch at ring position xc_ with m_now stored pairs (false: that form does not apply)
-    bool gate_make_plan(int xc_, int m_now, const double* gring, int xr_run, GatePlan& pl) const {
+    // (per-stream offsets of the one-pass kernels in 32 bits while every vector is shorter than 4 GB)
+    bool small_vectors() const { return env_.off32 && (double)vcap * sizeof(T) < 4.0e9; }
+    // streams of the iterate-history pass without z: the m_now + 1 distinct iterates (x among them), the family's parameter
+    // vectors (mu / mu*y unless passed as numbers), x_d
+    int xr2_streams(int m_now) const { return (m_now + 1) + pstreams(true, true, true) + 1; }
+    // The plan of the iterate-history pass (k_fused_compact<XR=2>) at ring position xc_ with m_now stored pairs, the ring's
+    // gammas gring, a run of xr_run pairs that are ring differences, and z stored or not (false: that form does not apply).
+    // The step plans the pass it runs here and the gated pre-launch plans the next iteration's: a pre-launched pass is
+    // released only if the two plans are equal.
+    bool xr2_plan(int xc_, int m_now, const double* gring, int xr_run, bool zstore, GatePlan& pl) const {
         const int fam = fused_family();
-        static const int spec_env = std::getenv("BZ_SPEC") ? std::atoi(std::getenv("BZ_SPEC")) : 1;
-        static const int off32_env = std::getenv("BZ_OFF32") ? std::atoi(std::getenv("BZ_OFF32")) : 1;
-        const int nt_env = nt_env_;
-        const bool small = off32_env && (double)vcap * sizeof(T) < 4.0e9;
-        if (!(xr_env_ >= 2 && small && fam >= 0 && xr_run >= m_now)) return false;
+        if (!(env_.xr >= 2 && small_vectors() && fam >= 0 && xr_run >= m_now)) return false;
+        // (only the oldest stored iterate may carry another gamma — see CompactCoef::gam0)
         for (int i = 1; i < m_now; ++i)
             if (gring[(xc_ - m_now + i + NXR) % NXR] != (double)gamma) return false;
         std::memset(&pl, 0, sizeof(pl));
         for (int i = 0; i < CM; ++i) {
-            const int slot = (xc_ - std::max(0, m_now - i) + NXR) % NXR;
+            const int slot = (xc_ - std::max(0, m_now - i) + NXR) % NXR;      // (beyond m: x itself)
             pl.S[i] = X_[slot].p;
             if (i == 0) pl.gam0 = gring[slot];
         }
         pl.x = X_[xc_].p; pl.xd = X_[(xc_ + 1) % NXR].p;
         pl.gamma = (double)gamma; pl.uni = uni_; pl.fam = fam; pl.m_now = m_now;
-        pl.gfc = gfc_env_ > 0 ? std::min(grid, gfc_env_ * std::max(1, num_cus)) : std::min(grid, std::max(1, num_cus));
-        const int streams = (m_now + 1) + pstreams(true, true, true) + 1;      // (uniform penalties / zero multipliers are not streams)
-        pl.nt = nt_env >= 0 ? nt_env != 0 : (double)n * sizeof(T) * streams > 340e6;
-        pl.table = !(spec_env && fam == FAM_HEADLINE) || famrt_env_;
+        // (one wave per SIMD, see trial_onepass)
+        pl.gfc = env_.gfc > 0 ? std::min(grid, env_.gfc * std::max(1, num_cus)) : std::min(grid, std::max(1, num_cus));
+        pl.nt = env_.nt >= 0 ? env_.nt != 0 : (double)n * sizeof(T) * (xr2_streams(m_now) + (zstore ? 1 : 0)) > 340e6;
+        // (the headline family with everything uniform fixed at compile time, see the kernel; the table otherwise)
+        pl.table = !(env_.spec && fam == FAM_HEADLINE) || env_.famrt;
         pl.keep_params = keep_params(pl.nt, pl.table, fam);
         pl.lds_ring = lds_ring(pl.nt, pl.table);
         return true;
     }
-    void gate_launch(const GatePlan& pl, CompactCoef<CM> C2, T* zarg, bool trial_unused = false) {
+    // k_fused_compact<XR=2> as planned: the plain pass (trial = 0: x_d = x + d formed into xd, z into zarg unless null) or
+    // the trial-given pass (trial = 1: the point given in xd, its z and res into zarg, resarg).  form_[C_FUSED_IT] names
+    // the instantiation that the same values select (tests assert it, bench.py matches profiles on it).
+    void launch_xr2(const GatePlan& pl, CompactCoef<CM> C, int trial, T* xd, T* zarg, T* resarg) {
         CompactVecs<T, CM> XV;
         XV.m = CM;
         for (int i = 0; i < CM; ++i) { XV.S[i] = pl.S[i]; XV.Y[i] = nullptr; }
-        C2.gam0 = pl.gam0;
+        C.gam0 = pl.gam0;
         const T gam = (T)pl.gamma;
+        auto go = [&](auto kernel) {
+            launch(C_FUSED_IT, kernel, pl.gfc, XV, C, pl.x, (const T*)nullptr, P, gam, xd, zarg, resarg, (T*)nullptr,
+                   (T*)nullptr, n, parts_.p, (int)SL_TRIAL);
+        };
         if (pl.table) {
-            C2.uni_rt = pl.uni; C2.trial_rt = 0;
+            C.uni_rt = pl.uni; C.trial_rt = trial;
             // the plain pass with uniform penalties has compile-time instantiations (fp64); run-time UNI / TRIAL otherwise
-            static const int famct_env = std::getenv("BZ_FAMCT") ? std::atoi(std::getenv("BZ_FAMCT")) : 1;
-            FusedFn<T> fn = (famct_env && !famrt_env_) ? family_kernel<T>(pl.fam, pl.nt, pl.uni) : nullptr;
+            FusedFn<T> fn = (trial == 0 && env_.famct && !env_.famrt) ? family_kernel<T>(pl.fam, pl.nt, pl.uni) : nullptr;
             const bool ct = fn != nullptr;
             if (!fn) fn = family_kernel<T>(pl.fam, pl.nt, -1);
             if (!fn) throw Error(BZ_ERR_STATE, "no one-pass kernel instantiation for this oracle family");
             form_[C_FUSED_IT] = std::string("k_fused_compact<XR=2,UNI=") + (ct ? std::to_string(pl.uni) : std::string("-1")) + ",NT=" +
                                 std::to_string(pl.nt ? 1 : 0) + ",TRIAL=" + (ct ? "0" : "-1") + ",FAM=" + std::to_string(pl.fam) + ">";
-            launch(C_FUSED_IT, fn, pl.gfc, XV, C2, pl.x, (const T*)nullptr, P, gam, pl.xd, zarg, (T*)nullptr, (T*)nullptr,
-                   (T*)nullptr, n, parts_.p, (int)SL_TRIAL);
-        } else {
-            form_[C_FUSED_IT] = std::string("k_fused_compact<XR=2,UNI=") + char('0' + pl.uni) + (pl.nt ? ",NT=1" : ",NT=0") + ",TRIAL=0" +
-                                (pl.keep_params ? ",PP=1" : "") + (pl.lds_ring ? ",LQ=1>" : ">");
-#define BZ_LAUNCH_G(NT_, UNI_, PP_, ...)                                                                          \
-    launch(C_FUSED_IT, k_fused_compact<T, CM, NT_, true, true, 2, UNI_, 0, FAM_HEADLINE, PP_, ##__VA_ARGS__>, pl.gfc, XV, C2, \
-           pl.x, (const T*)nullptr, P, gam, pl.xd, zarg, (T*)nullptr, (T*)nullptr, (T*)nullptr, n, parts_.p, (int)SL_TRIAL)
-            if (pl.lds_ring) {      // (fp64 only: lds_ring)
-                if constexpr (sizeof(T) == 8) {
-                    if (pl.keep_params) { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 1, 1); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 1, 1); else BZ_LAUNCH_G(true, 0, 1, 1); }
-                    else { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 0, 1); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 0, 1); else BZ_LAUNCH_G(true, 0, 0, 1); }
-                }
-            }
-            else if (pl.nt && pl.keep_params) { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 1); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 1); else BZ_LAUNCH_G(true, 0, 1); }
-            else if (pl.nt) { if (pl.uni == 2) BZ_LAUNCH_G(true, 2, 0); else if (pl.uni == 1) BZ_LAUNCH_G(true, 1, 0); else BZ_LAUNCH_G(true, 0, 0); }
-            else { if (pl.uni == 2) BZ_LAUNCH_G(false, 2, 0); else if (pl.uni == 1) BZ_LAUNCH_G(false, 1, 0); else BZ_LAUNCH_G(false, 0, 0); }
-#undef BZ_LAUNCH_G
+            go(fn);
+            return;
         }
+        form_[C_FUSED_IT] = std::string("k_fused_compact<XR=2,UNI=") + char('0' + pl.uni) + (pl.nt ? ",NT=1" : ",NT=0") +
+                            (trial ? ",TRIAL=1" : ",TRIAL=0") + (pl.keep_params ? ",PP=1" : "") + (pl.lds_ring ? ",LQ=1>" : ">");
+        with_bool(trial != 0, [&](auto tr) {
+            with_uni(pl.uni, [&](auto un) {
+                constexpr int TR = decltype(tr)::value, UNI = decltype(un)::value;
+                if (pl.lds_ring) {      // (fp64 only: lds_ring)
+                    if constexpr (sizeof(T) == 8) {
+                        if (pl.keep_params) go(k_fused_compact<T, CM, true, true, true, 2, UNI, TR, FAM_HEADLINE, 1, 1>);
+                        else go(k_fused_compact<T, CM, true, true, true, 2, UNI, TR, FAM_HEADLINE, 0, 1>);
+                    }
+                } else if (pl.nt && pl.keep_params) go(k_fused_compact<T, CM, true, true, true, 2, UNI, TR, FAM_HEADLINE, 1>);
+                else if (pl.nt) go(k_fused_compact<T, CM, true, true, true, 2, UNI, TR, FAM_HEADLINE, 0>);
+                else go(k_fused_compact<T, CM, false, true, true, 2, UNI, TR, FAM_HEADLINE, 0>);
+            });
+        });
     }
-    // launch the NEXT iteration's pass now, gated on the host record
-    void gate_prelaunch(const GatePlan& pl) {
+    // launch the NEXT iteration's pass now, gated on the host record, planned for this one (x_d at ring position xd, m_now
+    // pairs) ending the plain way: trial accepted, pair inserted, same gamma — the ring one step on, one more pair — and (not
+    // known yet) no z store
+    void gate_prelaunch(int xd, int m_now) {
+        double gr[NXR];
+        for (int i = 0; i < NXR; ++i) gr[i] = gring_[i];
+        gr[xd] = (double)gamma;
+        GatePlan pl;
+        if (!xr2_plan(xd, std::min(m_now + 1, M), gr, xr_run_ + 1, false, pl)) return;
         gate_alloc();
         CompactCoef<CM> C2;
         std::memset(&C2, 0, sizeof(C2));
-        static const int glate_env = std::getenv("BZ_GATELATE") ? std::atoi(std::getenv("BZ_GATELATE")) : 1;
-        C2.gate_late = glate_env;
+        C2.gate_late = env_.gatelate;
         // (BZ_GATE_SPIN: the poll bounds, for the test of the fall-back)
-        static const unsigned spin_env = std::getenv("BZ_GATE_SPIN") ? (unsigned)std::atoll(std::getenv("BZ_GATE_SPIN")) : 0u;
-        C2.gate_spin_host = spin_env ? spin_env : GATE_SPIN_HOST;
-        C2.gate_spin_dev = spin_env ? 8u * spin_env : GATE_SPIN_DEV;
+        C2.gate_spin_host = env_.gate_spin ? env_.gate_spin : GATE_SPIN_HOST;
+        C2.gate_spin_dev = env_.gate_spin ? 8u * env_.gate_spin : GATE_SPIN_DEV;
         C2.gate_seq = ++gate_seq_; C2.gate_host = gate_host_dev_; C2.gate_dev = gate_dev_.p; C2.gate_timeout = ptimeout_dev_;
-        const int streams = (pl.m_now + 1) + pstreams(true, true, true) + 1;
-        mv(streams);
+        mv(xr2_streams(pl.m_now));
         gate_bytes_ = pending_bytes_;
         hipStream_t here = cur_;
         gate_on_ = gate_env_ != 2 ? cur_ : ((cur_ == ctx->stream) ? gate_stream_ : ctx->stream);
         C2.gate_other_stream = gate_on_ != cur_ ? 1 : 0;
         cur_ = gate_on_;
         try {
-            gate_launch(pl, C2, (T*)nullptr);
+            launch_xr2(pl, C2, 0, pl.xd, (T*)nullptr, (T*)nullptr);
         } catch (...) {
             cur_ = here;
             throw;
@@ -1221,32 +1282,21 @@ template <class T> class Solver final : public SolverBase {
     template <class K, class... A> void launch(int cat, K kernel, int g, A... args) {
         launch_b(cat, kernel, g, BLOCK, args...);
     }
-    template <class K, class... A> void launch_b(int cat, K kernel, int g, int block, A... args) {
+    template <class K, class... A> void launch2d(int cat, K kernel, int gx, int gy, A... args) {
+        launch_b(cat, kernel, dim3(gx, gy), BLOCK, args...);
+    }
+    template <class K, class... A> void launch_b(int cat, K kernel, dim3 g, int block, A... args) {
         ProfRec r{cat, nullptr, nullptr, 0.0};
         const bool prof_on = prof_pick(cat);
         account(cat, prof_on ? &r : nullptr);
         if (prof_on) {
             // start/stop events bound to the dispatch itself: kernel time without the launch gap
             r.a = get_event(); r.b = get_event();
-            hipExtLaunchKernelGGL(kernel, dim3(g), dim3(block), 0, cur_, r.a, r.b, 0, args...);
+            hipExtLaunchKernelGGL(kernel, g, dim3(block), 0, cur_, r.a, r.b, 0, args...);
             prof_recs.push_back(r);
             if (prof_recs.size() > 8192) drain_prof();
         } else {
-            hipLaunchKernelGGL(kernel, dim3(g), dim3(block), 0, cur_, args...);
-        }
-        BZ_HIP(hipGetLastError());
-    }
-
-    template <class K, class... A> void launch2d(int cat, K kernel, int gx, int gy, A... args) {
-        ProfRec r{cat, nullptr, nullptr, 0.0};
-        const bool prof_on = prof_pick(cat);
-        account(cat, prof_on ? &r : nullptr);
-        if (prof_on) {
-            r.a = get_event(); r.b = get_event();
-            hipExtLaunchKernelGGL(kernel, dim3(gx, gy), dim3(BLOCK), 0, cur_, r.a, r.b, 0, args...);
-            prof_recs.push_back(r);
-        } else {
-            hipLaunchKernelGGL(kernel, dim3(gx, gy), dim3(BLOCK), 0, cur_, args...);
+            hipLaunchKernelGGL(kernel, g, dim3(block), 0, cur_, args...);
         }
         BZ_HIP(hipGetLastError());
     }
@@ -1346,9 +1396,6 @@ template <class T> class Solver final : public SolverBase {
     }
     void dense_fused_plan() {
         df_kp_ = 0;
-        df_env_ = std::getenv("BZ_DENSE_FUSED") ? std::atoi(std::getenv("BZ_DENSE_FUSED")) : 1;
-        df_sabotage_ = std::getenv("BZ_TEST_DENSE_TIMEOUT") ? std::atoi(std::getenv("BZ_TEST_DENSE_TIMEOUT")) : 0;
-        df_spin_ = std::getenv("BZ_DENSE_SPIN") ? (unsigned)std::atoll(std::getenv("BZ_DENSE_SPIN")) : 0u;
         constexpr int N = PackN<T>::N;
         if (desc.c_kind != BZ_C_DENSE_AFFINE || x_replicated || slack || (n % N) != 0) return;
         if (desc.D_kind >= BZ_D_VC_PAIRS) return;
@@ -1358,7 +1405,7 @@ template <class T> class Solver final : public SolverBase {
         // measured 20-60 % slower on cfg 4); the narrower forms serve matrices with few columns
         const int kp_full = std::is_same<T, float>::value ? 4 : 2;
         int kp = kp_full;
-        if (const char* e = std::getenv("BZ_DENSE_KP")) kp = std::max(1, std::min(kp_full, std::atoi(e)));
+        if (cenv_.dense_kp) kp = std::max(1, std::min(kp_full, *cenv_.dense_kp));
         while (kp > 1 && kp != 2 && kp != 4) --kp;
         while (kp > 1 && (int64_t)FBLOCK * (kp / 2) >= npk) kp /= 2;       // (a matrix narrower than one slice: more row groups instead)
         while (kp < kp_full && (npk + (int64_t)FBLOCK * kp - 1) / ((int64_t)FBLOCK * kp) > FG_MAX) kp *= 2;
@@ -1379,9 +1426,7 @@ template <class T> class Solver final : public SolverBase {
         df_kp_ = kp; df_G_ = (int)G; df_groups_ = (int)groups; df_rpg_ = rpg;
         df_mail_.alloc((size_t)groups * FMS * FG_MAX * FT * 2);
     }
-    bool dense_fused_on() const { return df_env_ && df_kp_ > 0 && !dense_fused_broken_; }
-    int df_env_ = 1, df_sabotage_ = 0;       // BZ_DENSE_FUSED / BZ_TEST_DENSE_TIMEOUT, read when the problem is created
-    unsigned df_spin_ = 0;                   // BZ_DENSE_SPIN
+    bool dense_fused_on() const { return cenv_.dense_fused && df_kp_ > 0 && !dense_fused_broken_; }
     // gradient!'s dense part in one pass over A: c(point) -> CX_ (and cx_keep_), the row-group partials of A'yhat -> GT_,
     // the penalty partials -> slot_pen
     void dense_fused_launch(const T* x, int slot_pen) {
@@ -1390,12 +1435,12 @@ template <class T> class Solver final : public SolverBase {
         a.A = A_.p; a.x = x; a.b = cb_.p; a.cx = CX_.p; a.cx2 = cx_keep_; a.part = GT_.p; a.pstride = npad;
         a.ny = ny; a.n = n; a.G = df_G_; a.ngroups = df_groups_; a.rows_per_group = df_rpg_;
         a.seq0 = df_seq_; a.mail = df_mail_.p; a.timeout = ptimeout_dev_;
-        a.spin = df_spin_ ? df_spin_ : FSPIN_LIMIT;
+        a.spin = cenv_.dense_spin ? cenv_.dense_spin : FSPIN_LIMIT;
         a.parts = parts_.p; a.slot_pen = slot_pen;
         df_seq_ += (unsigned long long)(df_rpg_ / FT) + 2ull * FNB;      // (every step posts, the padding steps of the last ring turn too)
         // (test) slice 0 of every group posts under tags nobody waits for: the polls give up
-        if (df_sabotage_ > 0 && ++dense_sabotage_count_ == df_sabotage_) a.sabotage = 1;
-        if (df_sabotage_ == -2) a.sabotage = 2;      // (timing experiment: no exchange)
+        if (cenv_.test_dense_timeout > 0 && ++dense_sabotage_count_ == cenv_.test_dense_timeout) a.sabotage = 1;
+        if (cenv_.test_dense_timeout == -2) a.sabotage = 2;      // (timing experiment: no exchange)
         // the matrix once; x, b and the penalty vectors over the rows; c(x) out; the row-group partials
         mv((double)ny, n); mv(1, n); mv(2 + pstreams(false, true, false) + (cx_keep_ ? 1 : 0), ny); mv(df_groups_, npad);
         const int g = df_groups_ * df_G_;
@@ -1485,9 +1530,7 @@ template <class T> class Solver final : public SolverBase {
     // enough, whatever the state of res (the iterate-history passes never write it)
     void ensure_z(bool need_res = true) {
         if (z_valid && (res_valid || !need_res)) return;
-        const int fb_env = fused_begin_env_;
-        if (fb_env && desc.c_kind == BZ_C_IDENTITY && !slack && !dense_f && !lp_g &&
-            (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC)) {
+        if (begin_fb_ok()) {
             mv(1 + pstreams(true, true, true) + 1 + (res_valid ? 0 : 1));
             launch(C_FB, k_zres_elem<T>, grid, (const T*)X_[xc].p, P, gamma, Z_[zc].p,
                    res_valid ? (T*)nullptr : RES_[rc].p, n);      // the two kernels below in one pass
@@ -1564,18 +1607,13 @@ template <class T> class Solver final : public SolverBase {
     }
     // fold the listed slots (bit i of maxmask: i-th listed slot is a max) and read them back
     std::vector<double> collect_range(int first, int cnt, unsigned maxmask) {
-        CollectArgs a;
-        a.n = cnt; a.maxmask = maxmask;
-        for (int i = 0; i < cnt; ++i) a.src[i] = src(first + i);
-        return collect_run(a);
+        const unsigned long long ticket = collect_launch_range(first, cnt, maxmask);
+        return wait_host(cnt, ticket);
     }
     std::vector<double> collect(std::initializer_list<int> slots, unsigned maxmask) {
         CollectArgs a;
         a.n = 0; a.maxmask = maxmask;
-        for (int s : slots) {
-            a.src[a.n] = src(s);
-            ++a.n;
-        }
+        for (int s : slots) a.src[a.n++] = src(s);
         return collect_run(a);
     }
     // launch the read-back of slots [first, first + cnt) without waiting; wait_host(cnt, ticket) later
@@ -1583,22 +1621,19 @@ template <class T> class Solver final : public SolverBase {
         CollectArgs a;
         a.n = cnt; a.maxmask = maxmask;
         for (int i = 0; i < cnt; ++i) a.src[i] = src(first + i);
-        a.ticket = ++collect_seq;
-        static const int wave_env = std::getenv("BZ_COLLECT_WAVE") ? std::atoi(std::getenv("BZ_COLLECT_WAVE")) : 1;
-        bool unit = wave_env != 0;
-        for (int i = 0; i < a.n; ++i) unit = unit && a.src[i].stride == 1;
-        if (unit) launch_b(C_COLLECT, k_collect_w, a.n, 64, a, host_out_dev_);
-        else launch(C_COLLECT, k_collect, a.n, a, host_out_dev_);
+        collect_launch(a);
         return a.ticket;
     }
     std::vector<double> collect_run(CollectArgs& a) {
+        collect_launch(a);
+        return wait_host(a.n, a.ticket);
+    }
+    void collect_launch(CollectArgs& a) {
         a.ticket = ++collect_seq;
-        static const int wave_env = std::getenv("BZ_COLLECT_WAVE") ? std::atoi(std::getenv("BZ_COLLECT_WAVE")) : 1;
-        bool unit = wave_env != 0;
+        bool unit = env_.collect_wave != 0;
         for (int i = 0; i < a.n; ++i) unit = unit && a.src[i].stride == 1;
         if (unit) launch_b(C_COLLECT, k_collect_w, a.n, 64, a, host_out_dev_);
         else launch(C_COLLECT, k_collect, a.n, a, host_out_dev_);
-        return wait_host(a.n, a.ticket);
     }
     // what a kernel's bounded poll reported in *ptimeout_ (read once the stream has run): cleared, and thrown as the error
     // that names it
@@ -1736,7 +1771,7 @@ template <class T> class Solver final : public SolverBase {
     // (v_mfma_f32_16x16x4_f32), everything else on the vector ALUs; both are bound by the bytes of M.
     void gemv_cols(const T* M, int64_t rows, const T* v, int rpc, int nch) {
         if constexpr (std::is_same<T, float>::value) {
-            if (n % 64 == 0 && !getenv("BZ_GEMV_VALU")) {
+            if (n % 64 == 0 && !env_.gemv_valu) {
                 mv((double)rows, n); mv(1, rows); mv(nch, npad);      // the matrix once, v, the row-chunk partials
                 nm("k_gemv_t_mfma");
                 launch2d(C_GEMV_MFMA, k_gemv_t_mfma, (int)((n / 64 + WAVES - 1) / WAVES), nch, (const float*)M,
@@ -1869,7 +1904,7 @@ template <class T> class Solver final : public SolverBase {
         // number and does not stream mu (nor mu*y).  alps.jl:42 gives every constraint the same mu when c(x0) is
         // in D, alps.jl:97 scales them alike, and y0 = 0 holds through the first subproblem — the longest one.
         uni_ = 0;
-        const int uni_env = std::getenv("BZ_UNI") ? std::atoi(std::getenv("BZ_UNI")) : 2;      // (tests toggle it)
+        const int uni_env = read_uni_knob();
         const bool probe = uni_env && (fused_family() >= 0 || (slack && !lp_g) ||
                                        (desc.f_kind == BZ_F_STENCIL5 && desc.c_kind == BZ_C_IDENTITY && !slack && !lp_g));
         for (int k = 0; k < 3; ++k) slot_n[SL_GP + k] = grid_y;
@@ -2027,8 +2062,7 @@ template <class T> class Solver final : public SolverBase {
             mv(2 * m + 1);
             launch(C_DOT, k_gram_dots<T, CM>, grid, V, (const T*)RES_[rc].p, n, parts_.p, (int)SL_GP);
             gather(SL_GP, 2 * CM, 0u);
-            auto pv = collect({SL_GP + 0, SL_GP + 1, SL_GP + 2, SL_GP + 3, SL_GP + 4, SL_GP + 5, SL_GP + 6,
-                               SL_GP + 7, SL_GP + 8, SL_GP + 9}, 0u);
+            auto pv = collect_range(SL_GP, 2 * CM, 0u);
             for (int i = 0; i < CM; ++i) { hp_[i] = i < m ? pv[i] : 0.0; hw_[i] = i < m ? pv[CM + i] : 0.0; }
             pw_valid = true;
         }
@@ -2084,7 +2118,7 @@ template <class T> class Solver final : public SolverBase {
         a.res = RES_[rc].p;
         for (int j = 0; j < m; ++j) { a.S[j] = S_[order[j]].p; a.Y[j] = Y_[order[j]].p; a.ys[j] = ys_[order[j]]; }
         a.H = H; a.m = m; a.d_out = D_.p; a.n = n; a.parts = parts_.p; a.alphas = alphas_.p;
-        a.counter = pcounter_.p; a.base = pbase + (persist_sabotage_ ? 1ull : 0ull); a.timeout = ptimeout_dev_;
+        a.counter = pcounter_.p; a.base = pbase + (env_.test_persist_timeout ? 1ull : 0ull); a.timeout = ptimeout_dev_;
         a.abort_flag = pgflag_.p + 1;
         a.slot_loop1 = SL_LOOP1; a.slot_loop2 = SL_LOOP2;
         a.nb = persist_blocks();
@@ -2213,7 +2247,56 @@ template <class T> class Solver final : public SolverBase {
             begin_impl(o, X_[0].p);
         }
     }
+    // which forms a solve takes (begin_impl): the one-pass kernels, the stencil fast path, the affine images, the compact
+    // representation, the persistent two-loop kernel
+    void select_paths(const bz_panoc_opts& o) {
+        // (the slack form of ALS too: x_i couples with s_i only — k_fused_slack; no pairwise D there, it needs the partner)
+        fused_ok = o.fuse && desc.c_kind == BZ_C_IDENTITY && !lp_g && (!slack || desc.D_kind < BZ_D_VC_PAIRS) &&
+                   (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
+        // auto: the compact representation where it makes the whole iteration one pass (the fused separable
+        // path, memory within its capacity), the two-loop recursion everywhere else
+        // (... and the stencil path: x_d, k_stencil_fb, k_stencil_update_c with ONE reduction phase per iteration
+        // instead of the persistent two-loop kernel's 2m - 1 grid barriers, or 2m + 1 exchanges when sharded)
+        stencil_fast_ = desc.f_kind == BZ_F_STENCIL5 && o.fuse && !lp_g && !slack;
+        if (o.affine_refresh < 0) throw Error(BZ_ERR_ARG, "affine_refresh must be >= 0");
+        aff_refresh_ = o.affine_refresh;
+        if (env_.affine >= 0) aff_refresh_ = env_.affine;
+        aff_track_ = affine_ok_ && aff_refresh_ > 0 && o.lbfgs_compact != 0 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS;
+        compact_ok = M >= 1 && (o.lbfgs_compact == 1 || dir_kind_ == BZ_DIR_ANDERSON ||
+                                (o.lbfgs_compact == 2 && (fused_ok || stencil_fast_ || aff_track_) && M <= CM));
+        // persistent two-loop: d must fit the register files (<= 40 packs per thread, one 512-thread
+        // block per CU) and the vector must be long enough for 2m-1 grid barriers to beat 2m launches;
+        // with several ranks the phases need the p2p mailboxes (RCCL cannot be called from a kernel)
+        persist_ok = o.persist && (!ctx->multi() || ctx->p2p_on) && persist_kr > 0 && n >= env_.persist_min_n && !x_replicated &&
+                     !persist_broken_;
+        if (ctx->nranks > 1 && !ctx->multi())
+            throw Error(BZ_ERR_STATE, "nranks > 1 needs an RCCL communicator or connected p2p mailboxes");
+        if (ctx->nranks > 1 && o.persist && M >= 1) {
+            // the shards may straddle a threshold (length, register budget): the phases of the persistent kernel
+            // and the exchanges of the kernel chain do not talk to each other, so all ranks must take the same
+            // form — the persistent one only if every rank can
+            launch_b(C_MISC, k_fill_slot, 1, 64, parts_.p, (int)SL_AUX, persist_ok ? 0.0 : 1.0);
+            slot_n[SL_AUX] = 1;
+            gather(SL_AUX, 1, 1u);
+            if (collect({SL_AUX}, 1u)[0] > 0.0) persist_ok = false;
+        }
+        // auto (lbfgs_compact = 2), one rank: wherever the two-loop would run as a CHAIN of 2m kernels (a vector beyond the
+        // persistent kernel's register capacity — e.g. the lifted vector [x; s] of ALS at n = 1e7 — or too short for its
+        // grid barriers) the compact form does the same work in two launches and 4m + 11 passes instead of 8m + 1
+        // (ALS at n = 1e7: 741 against 519 it/s).  Several ranks keep the rule above: they must agree on one form.
+        if (!compact_ok && o.lbfgs_compact == 2 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS && !ctx->multi() && !persist_ok &&
+            !generic_)
+            compact_ok = true;
+    }
+    // the start of a solve (and the re-materialised z) in one element-wise pass: k_begin_lip, and k_begin_fb / k_zres_elem
+    // unless g is an Lp power
+    bool begin_lip_ok() const {
+        return env_.fused_begin && desc.c_kind == BZ_C_IDENTITY && !slack && !dense_f &&
+               (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
+    }
+    bool begin_fb_ok() const { return begin_lip_ok() && !lp_g; }
     void begin_impl(const bz_panoc_opts& o, const T* x0_dev) {
+        env_ = BeginKnobs(ctx->nranks);
         opt = o;
         if (o.lbfgs_memory < 0 || o.lbfgs_memory > MAX_MEM)
             throw Error(BZ_ERR_ARG, "lbfgs_memory must be in 0..16 (0 = NoAcceleration)");
@@ -2248,80 +2331,22 @@ template <class T> class Solver final : public SolverBase {
         // (upstream tests `iter.gamma === nothing || iter.adaptive == true` at both halving sites: without a given step
         // size the estimate is always backtracked, whatever `adaptive` says)
         adaptive_ = !(gamma_given_ > T(0)) || o.adaptive == 1;
-        // (the slack form of ALS too: x_i couples with s_i only — k_fused_slack; no pairwise D there, it needs the partner)
-        fused_ok = o.fuse && desc.c_kind == BZ_C_IDENTITY && !lp_g && (!slack || desc.D_kind < BZ_D_VC_PAIRS) &&
-                   (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
-        // auto: the compact representation where it makes the whole iteration one pass (the fused separable
-        // path, memory within its capacity), the two-loop recursion everywhere else
-        // (... and the stencil path: x_d, k_stencil_fb, k_stencil_update_c with ONE reduction phase per iteration
-        // instead of the persistent two-loop kernel's 2m - 1 grid barriers, or 2m + 1 exchanges when sharded)
-        stencil_fast_ = desc.f_kind == BZ_F_STENCIL5 && o.fuse && !lp_g && !slack;
-        if (o.affine_refresh < 0) throw Error(BZ_ERR_ARG, "affine_refresh must be >= 0");
-        aff_refresh_ = o.affine_refresh;
-        static const int aff_env = std::getenv("BZ_AFFINE") ? std::atoi(std::getenv("BZ_AFFINE")) : -1;
-        if (aff_env >= 0) aff_refresh_ = aff_env;
-        aff_track_ = affine_ok_ && aff_refresh_ > 0 && o.lbfgs_compact != 0 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS;
+        select_paths(o);
         aff_count_ = 0; n_affine_ = 0; n_affine_blends_ = 0; n_gated_ = 0; n_gate_aborts_ = 0; n_dense_onepass_ = 0;
-        compact_ok = M >= 1 && (o.lbfgs_compact == 1 || dir_kind_ == BZ_DIR_ANDERSON ||
-                                (o.lbfgs_compact == 2 && (fused_ok || stencil_fast_ || aff_track_) && M <= CM));
-        {
-            // persistent two-loop: d must fit the register files (<= 40 packs per thread, one 512-thread
-            // block per CU) and the vector must be long enough for 2m-1 grid barriers to beat 2m launches
-            int64_t min_n = 300000;      // below this 2m short launches beat 2m-1 grid barriers (~5 us each)
-            if (const char* e = getenv("BZ_PERSIST_MIN_N")) min_n = atoll(e);
-            // with several ranks the phases need the p2p mailboxes (RCCL cannot be called from a kernel)
-            persist_ok = o.persist && (!ctx->multi() || ctx->p2p_on) && persist_kr > 0 && n >= min_n && !x_replicated &&
-                         !persist_broken_;
-            if (ctx->nranks > 1 && !ctx->multi())
-                throw Error(BZ_ERR_STATE, "nranks > 1 needs an RCCL communicator or connected p2p mailboxes");
-            persist_sabotage_ = std::getenv("BZ_TEST_PERSIST_TIMEOUT") && std::atoi(std::getenv("BZ_TEST_PERSIST_TIMEOUT")) != 0;
-            if (ctx->nranks > 1 && o.persist && M >= 1) {
-                // the shards may straddle a threshold (length, register budget): the phases of the persistent kernel
-                // and the exchanges of the kernel chain do not talk to each other, so all ranks must take the same
-                // form — the persistent one only if every rank can
-                launch_b(C_MISC, k_fill_slot, 1, 64, parts_.p, (int)SL_AUX, persist_ok ? 0.0 : 1.0);
-                slot_n[SL_AUX] = 1;
-                gather(SL_AUX, 1, 1u);
-                if (collect({SL_AUX}, 1u)[0] > 0.0) persist_ok = false;
-            }
-            // auto (lbfgs_compact = 2), one rank: wherever the two-loop would run as a CHAIN of 2m kernels (a vector beyond the
-            // persistent kernel's register capacity — e.g. the lifted vector [x; s] of ALS at n = 1e7 — or too short for its
-            // grid barriers) the compact form does the same work in two launches and 4m + 11 passes instead of 8m + 1
-            // (ALS at n = 1e7: 741 against 519 it/s).  Several ranks keep the rule above: they must agree on one form.
-            if (!compact_ok && o.lbfgs_compact == 2 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS && !ctx->multi() && !persist_ok &&
-                !generic_)
-                compact_ok = true;
-        }
         t_begin = std::chrono::steady_clock::now();
         k_ = 1; n_grad = n_prox = n_bt = n_halv = n_fused = n_skips = 0;
         last_nbt = 0; last_fused = false; tau = T(0); last_ys = T(0); fbe_last = T(0);
         xc = 0; rc = 0; zc = 0; z_valid = true; xr_run_ = 0; sy_stale_ = false; rh_stale_ = false; res_valid = true;
-        xr_env_ = std::getenv("BZ_XR") ? std::atoi(std::getenv("BZ_XR")) : 2;
-        gfc_env_ = std::getenv("BZ_GFC") ? std::atoi(std::getenv("BZ_GFC")) : 0;
-        trialfuse_env_ = std::getenv("BZ_TRIALFUSE") ? std::atoi(std::getenv("BZ_TRIALFUSE")) : 1;
-        fused_begin_env_ = std::getenv("BZ_FUSED_BEGIN") ? std::atoi(std::getenv("BZ_FUSED_BEGIN")) : 1;
-        skipz_env_ = std::getenv("BZ_SKIPZ") ? std::atoi(std::getenv("BZ_SKIPZ")) : 1;
-        famrt_env_ = std::getenv("BZ_FAMRT") ? std::atoi(std::getenv("BZ_FAMRT")) : 0;
-        nt_env_ = std::getenv("BZ_NT") ? std::atoi(std::getenv("BZ_NT")) : -1;
-        keepp_env_ = std::getenv("BZ_KEEPP") ? std::atoi(std::getenv("BZ_KEEPP")) : -1;
-        ldsq_env_ = std::getenv("BZ_LDSQ") ? std::atoi(std::getenv("BZ_LDSQ")) : -1;
-        slackfast_env_ = std::getenv("BZ_SLACKFAST") ? std::atoi(std::getenv("BZ_SLACKFAST")) : 1;
-        slackkind_env_ = std::getenv("BZ_SLACKKIND") ? std::atoi(std::getenv("BZ_SLACKKIND")) : 1;
-        densesmall_env_ = std::getenv("BZ_DENSESMALL") ? std::atoi(std::getenv("BZ_DENSESMALL")) : 1;
-        affblend_env_ = std::getenv("BZ_AFFINE_BLEND") ? std::atoi(std::getenv("BZ_AFFINE_BLEND")) : 1;
-        stencil_regx_env_ = std::getenv("BZ_STENCIL_REGX") ? std::atoi(std::getenv("BZ_STENCIL_REGX")) : 1;
-        suc_grid_env_ = std::getenv("BZ_SUC_GRID") ? std::atoi(std::getenv("BZ_SUC_GRID")) : 1;
-        slackdepth_env_ = std::getenv("BZ_SLACKDEPTH") ? std::atoi(std::getenv("BZ_SLACKDEPTH")) : 1;
         // BZ_GATE: 0 off; 1 (default) the early launch queues behind the read-back on the solver's own stream; 2 on the other
         // stream (resident while the previous pass runs: measured slower, kept for the record)
         // Several ranks: off unless asked for (BZ_GATE=1).  A launch that misses its gate cannot be redone there (the peers
         // have consumed this rank's scalars: BZ_ERR_COMM), and gated launches on distinct devices have never run on
         // hardware — bench.py asks for them after checking, on the node it runs on, that they reproduce the plain launches.
-        gate_env_ = std::getenv("BZ_GATE") ? std::atoi(std::getenv("BZ_GATE")) : (ctx->nranks > 1 ? 0 : 1);
+        gate_env_ = env_.gate;
         // a resident launch polling at its gate holds its CUs: with another tenant on the GPU (a rank of this very job in
         // a one-GPU rehearsal, or whoever made an earlier launch of this problem miss its gate) the two starve each other
         if (ctx->shared_device || gate_broken_) gate_env_ = 0;
-        gate_sabotage_ = std::getenv("BZ_TEST_GATE_TIMEOUT") ? std::atoi(std::getenv("BZ_TEST_GATE_TIMEOUT")) : 0;
+        gate_sabotage_ = env_.test_gate_timeout;
         if (gate_env_ && fused_ok) gate_alloc();      // (pinned record, device copy, second stream: not inside an iteration)
         gate_quiesce();
         if (x0_dev != X_[0].p)
@@ -2329,9 +2354,7 @@ template <class T> class Solver final : public SolverBase {
         const T eps = std::numeric_limits<T>::epsilon();
         T* x = X_[xc].p;
         // grad_f_x, f_x = gradient(f, x)
-        const int lip_env = fused_begin_env_;
-        if (lip_env && desc.c_kind == BZ_C_IDENTITY && !slack && !dense_f &&
-            (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC)) {
+        if (begin_lip_ok()) {
             // gradient at x and the Lipschitz estimate in one pass (k_begin_lip)
             slot_n[SL_FXD] = slot_n[SL_FXD + 1] = grid;
             mv(2 + pstreams(true, true, false));
@@ -2367,8 +2390,7 @@ template <class T> class Solver final : public SolverBase {
         }
         // y = x - gamma grad ; z, g_z = prox(g, y, gamma) ; res = x - z ; backtrack_stepsize!
         T f_z = T(0);
-        const bool fused_fb = lip_env && desc.c_kind == BZ_C_IDENTITY && !slack && !dense_f && !lp_g &&
-                              (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
+        const bool fused_fb = begin_fb_ok();
         double stop0 = 0.0;
         for (;;) {
             std::vector<double> v;
@@ -2573,507 +2595,505 @@ template <class T> class Solver final : public SolverBase {
         // without images the attempt wrote grad L at its trial points into GX_ and GZ_ themselves (the redo evaluates them)
         gx_valid = aff_track_ && st.gx_valid; gz_valid = aff_track_ && st.gz_valid;
     }
+    // ---- one iteration (step_impl), stage by stage.  Iter holds what lives inside the iteration only: the state it changes
+    // is in members, which save_state / load_state cover.
+    static constexpr int NFC = 10 + 4 * CM + 2;                          // slots of k_fused_compact
+    static_assert(SL_TRIAL + NFC <= SL_AUX, "k_fused_compact's slots overlap the next group");
+    struct Iter {
+        T nr0, FBE_x;                            // ||res|| and the FBE at the current state
+        bool stencil_fast_now, use_compact;
+        CompactVecs<T, CM> CV;                   // the direction: compact coefficients ...
+        CompactCoef<CM> CC;
+        TailArgs<T> tail;                        // ... or the last axpy of the two-loop recursion / Broyden
+        int m_at_trial;
+        int xp, xd, xb, rp, rn, zp, zn;          // rings: the state's x, x_d, the tau blend; res; z
+        int xcur, nbt = 0;                       // the trial point (x_d or the blend) ; tau backtracks so far
+        bool have_trial = false, fused_this = false, reset_this = false, sep_trial = false;
+        bool img_trial = false;      // grad L (and f) at the trial point x + d are affine images, not evaluations
+        bool z_skipped = false, res_skipped = false, gram_from_trial = false;
+        bool tail_used = false; unsigned long long tail_ticket = 0;      // the trial's scalars come back through the ticket
+        bool head_on = false, head_fb = false;   // cfg 4: k_dense_head serves this iteration ; ... and has made the FB step of its first trial
+        bool state_imgs = false, halved_here = false;      // cfg 4: the state's images are valid ; gamma was halved inside this step
+        // a backtracked trial point can go through the one-pass kernel too ("trial given" variant) when this iteration's
+        // first trial did: that launch's plan and coefficients
+        bool trial_ok = false; GatePlan trial_plan; CompactCoef<CM> trial_coef;
+        double sep_p = 0.0, sep_w = 0.0;         // <s_new, -res>, <y_new, -res> as measured by a k_fused_sep trial
+        double gsy[CM] = {0}, gyy[CM] = {0};
+        double tp[CM] = {0}, tw[CM] = {0}, tpn = 0.0, twn = 0.0;      // next p, w as measured by the fused trial
+        std::vector<double> v;                   // the accepted trial's scalars
+        bool gen_gram = false;       // the generic trial just launched carried the compact form's products (k_update_c)
+        int m_gram;                  // ... measured against a memory of this many pairs
+    };
     void step_impl() {
         ++k_;
-        const T eps = std::numeric_limits<T>::epsilon();
-        const int max_bt = opt.max_backtracks;
-        // FBE at the current state
-        const T nr0 = std::sqrt(ss_res);
-        const T FBE_x = (f_x - dot_gr + ((alpha / gamma) / T(2)) * (nr0 * nr0)) + g_z;
-        fbe_last = FBE_x;
-        // direction d = H(-res): all but the last axpy
+        Iter it;
+        open_iteration(it);
+        if (fused_ok && it.use_compact) trial_onepass(it);
+        else if (fused_ok && !slack) trial_sep(it);
+        else trial_chain(it);
+        step_size_test(it);
+        commit(it);
+    }
+    // the FBE at the current state, which paths apply, the direction d = H(-res) (all but the last axpy), the ring indices
+    void open_iteration(Iter& it) {
+        it.nr0 = std::sqrt(ss_res);
+        it.FBE_x = (f_x - dot_gr + ((alpha / gamma) / T(2)) * (it.nr0 * it.nr0)) + g_z;
+        fbe_last = it.FBE_x;
         // (headline family: the one-pass kernel also serves an EMPTY memory — d = H0 (-res), all coefficients zero —
         // so the first iteration of a solve is a 3..5-stream pass too instead of k_fused_sep's 12)
         // (the stencil fast path also serves a row-sharded grid: the halo rows of x_d and of z travel before the two
         // passes, and with the compact form the iteration has ONE scalar exchange — the 32 slots of k_stencil_update_c)
-        const bool stencil_fast_now = stencil_fast_ && (!ctx->multi() || (ctx->p2p_on && compact_ok));
-        const bool use_compact = compact_ok && (!order.empty() || (fused_ok && fused_family() >= 0) ||
-                                                stencil_fast_now || aff_track_);
-        const bool use_persist = persist_ok && !order.empty() && !use_compact;
-        CompactVecs<T, CM> CV;
-        CompactCoef<CM> CC;
-        TailArgs<T> tail;
-        if (use_compact) { CV = compact_vecs(); CC = compact_prepare(CV); std::memset(&tail, 0, sizeof(tail)); }
-        else if (dir_kind_ == BZ_DIR_BROYDEN) { if (!res_valid) ensure_z(); tail = broyden_dir(); }
-        else tail = use_persist ? two_loop_persist() : two_loop();
-        double gsy[CM] = {0}, gyy[CM] = {0};
-        double tp[CM] = {0}, tw[CM] = {0}, tpn = 0.0, twn = 0.0;      // next p, w as measured by the fused trial
-        constexpr int NFC = 10 + 4 * CM + 2;                          // slots of k_fused_compact
-        static_assert(SL_TRIAL + NFC <= SL_AUX, "k_fused_compact's slots overlap the next group");
-        const int m_at_trial = (int)order.size();
-        bool tail_used = false, z_skipped = false, res_skipped = false;
-        unsigned long long tail_ticket = 0;
-        bool gram_from_trial = false;
+        it.stencil_fast_now = stencil_fast_ && (!ctx->multi() || (ctx->p2p_on && compact_ok));
+        it.use_compact = compact_ok && (!order.empty() || (fused_ok && fused_family() >= 0) || it.stencil_fast_now || aff_track_);
+        const bool use_persist = persist_ok && !order.empty() && !it.use_compact;
+        if (it.use_compact) { it.CV = compact_vecs(); it.CC = compact_prepare(it.CV); std::memset(&it.tail, 0, sizeof(it.tail)); }
+        else if (dir_kind_ == BZ_DIR_BROYDEN) { if (!res_valid) ensure_z(); it.tail = broyden_dir(); }
+        else it.tail = use_persist ? two_loop_persist() : two_loop();
+        it.m_at_trial = it.m_gram = (int)order.size();
         tau = T(1);
-        const int xp = xc, xd = (xc + 1) % NXR, xb = (xc + 2) % NXR;
-        const int rp = rc, rn = (rc + 1) % NRR, zp = zc, zn = 1 - zc;
-        int xcur = xd;
-        bool have_trial = false, fused_this = false, reset_this = false, sep_trial = false;
-        bool img_trial = false;      // grad L (and f) at the trial point x + d are affine images, not evaluations
-        // a backtracked trial point can go through the one-pass kernel too ("trial given" variant) when this
-        // iteration's first trial did: what that launch used is kept here
-        bool trial_ok = false, trial_nt = false, trial_keep = false, trial_lq = false;
-        bool head_on = false, head_fb = false;      // cfg 4: k_dense_head serves this iteration ; ... and has made the FB step of its first trial
-        bool state_imgs = false, halved_here = false;      // cfg 4: the state's images are valid ; gamma was halved inside this step
-        int trial_uni = 0, trial_gfc = 0, trial_fam = -1;
-        bool trial_table = false;
-        CompactVecs<T, CM> trial_XV;
-        CompactCoef<CM> trial_CC;
-        double sep_p = 0.0, sep_w = 0.0;      // <s_new, -res>, <y_new, -res> as measured by a k_fused_sep trial
-        if (fused_ok && use_compact) {
-            // 176 VGPRs -> two 256-thread blocks per CU: one resident round of blocks (each block pays the
-            // coefficient prologue and a 20-slot reduction epilogue once)
-            const int gfc_env = gfc_env_;
-            int gfc = std::min(grid, (gfc_env > 0 ? gfc_env : 2) * std::max(1, num_cus));
-            // non-temporal loads/stores once the working set (2M + 11 vectors) no longer fits the 256 MB Infinity
-            // Cache.  Measured fused-pass times, default policy vs non-temporal: n = 1.25e6 (210 MB) 39.0 / 44.5 us,
-            // 1.8e6 (302 MB) 51.0 / 60.4, 2.5e6 (420 MB) 90.1 / 81.5, 5e6 (840 MB) 171 / 159, 1e7 322 / 314.
-            const int nt_env = nt_env_;      // (BZ_NT, read at every bz_panoc_begin: the tests run both instantiations)
-            // headline family with everything uniform fixed at compile time (see the kernel)
-            static const int spec_env = std::getenv("BZ_SPEC") ? std::atoi(std::getenv("BZ_SPEC")) : 1;
-            const int fam = fused_family();
-            const bool headline = spec_env && fam == FAM_HEADLINE;
-            const bool spec = headline && CV.m == CM;
-#define BZ_LAUNCH_FC(NT_, SPEC_)                                                                                  \
-    launch(C_FUSED, k_fused_compact<T, CM, NT_, SPEC_>, gfc, CV, CC, (const T*)X_[xp].p, (const T*)RES_[rp].p, P, \
-           gamma, X_[xd].p, zstore, RES_[rn].p, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL)
-            // z is the solution the caller reads when the solve stops: once the stop norm is within a factor 10 of
-            // the tolerance, store it (one more write stream for the last iteration or two) rather than
-            // re-materialise it afterwards with two generic kernels (the same bits either way)
-            // ... and during the first 20 iterations of a solve: ALPS subproblems are often that short (13 of them
-            // with 180 inner iterations in all on cfg 2), and a stored z costs a tenth of re-materialising one
-            // (tol = 0: the caller has said the solve never stops by itself — bench.py's timed region, the step-wise parity
-            // tests — so no early stop is being prepared for; whoever asks for z gets it re-materialised, same bits)
-            const bool near_stop = (double)stop_norm_ <= 10.0 * opt.tol || (k_ <= 20 && opt.tol > 0.0);
-            T* const zstore = (skipz_env_ && !near_stop) ? (T*)nullptr : Z_[zn].p;
-            z_skipped = zstore == nullptr;
-            static const int off32_env = std::getenv("BZ_OFF32") ? std::atoi(std::getenv("BZ_OFF32")) : 1;
-            const bool small = off32_env && (double)vcap * sizeof(T) < 4.0e9;
-            const bool off32 = small && spec;
-            // 0: stored pairs; 1: pairs re-formed from the iterate / residual rings (full memory only); 2: residuals
-            // re-evaluated too — possible as soon as every stored pair is a difference of ring neighbours, also
-            // with a partial memory (the absent pairs are x - x = 0 with zero coefficients)
-            const int m_now = (int)order.size();
-            int xr = 0;
-            // (the slack form of ALS has its own iterate-history kernel, k_fused_slack_xr: BZ_XR >= 2, any element-wise kinds)
-            if (xr_env_ && small && (fam >= 0 || slack) && xr_run_ >= m_now) {
-                if (xr_env_ >= 2) xr = 2;
-                else if (headline && m_now == CM && !rh_stale_) xr = 1;
-                // (only the oldest stored iterate may carry another gamma — see CompactCoef::gam0)
-                for (int i = 1; i < m_now; ++i)
-                    if (gring_[(xc - m_now + i + NXR) % NXR] != (double)gamma) xr = 0;
-                if (xr == 1 && gring_[(xc - m_now + NXR) % NXR] != (double)gamma) xr = 0;
-            }
-            if (sy_stale_ && !xr) materialize_pairs();
-            if (xr != 2 && !res_valid) ensure_z();
-            const int uni = xr == 2 ? uni_ : 0;
-            // the iterate-history form keeps two packs of loads in flight per wave and runs best with ONE wave per
-            // SIMD (n = 1e7: 134 vs 140 us; 1.25e6: 28.5 vs 30.2 us): the wave has the vector ALU to itself and
-            // the 32-scalar epilogue runs half as often.  (A different grid is a different summation tree: the
-            // forms then agree to rounding, not bit for bit — BZ_GFC pins one grid for all of them.)
-            // (the slack form's fast instantiations: a full memory, f = DiagQuadratic, no vector-valued parameters of g or D —
-            // pipelined like the headline kernel, 256 VGPRs + spill AGPRs: one workgroup per CU there too)
-            const bool slack_fast = slack && xr == 2 && slackfast_env_ && m_now == CM && desc.f_kind == BZ_F_DIAG_QUADRATIC &&
-                                    pstreams(false, true, true) == 2 - std::min(2, (int)P.uni) &&
-                                    !(P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX));
-            // ... with the kinds fixed too (g = NormL1, D = Box: the ALS form of cfg 2), one pack of loads ahead
-            const bool slack_hk = slack_fast && slackkind_env_ && P.g_kind == BZ_G_NORM_L1 && P.D_kind == BZ_D_BOX;
-            if (xr == 2 && gfc_env <= 0 && (!slack || (slack_hk && slackdepth_env_ > 0))) gfc = std::min(grid, std::max(1, num_cus));
-            for (int k = 0; k < NFC; ++k) slot_n[SL_TRIAL + k] = gfc;
-            // (the vectors this pass touches: history + x_d + z + the parameter vectors (+ res, s, y))
-            const int xr2_streams = (m_now + 1) + pstreams(true, true, true) + 1;      // (pstreams leaves out what travels as numbers)
-            const int nvec = (xr == 2 ? xr2_streams : 2 * CM + 5 + pstreams(true, true, true)) + (zstore ? 1 : 0);
-            const bool nt = nt_env >= 0 ? nt_env != 0 : (double)n * sizeof(T) * nvec > 340e6;
-            if (gate_pending_ && xr != 2) gate_abort();
-            if (xr == 2 && slack) {
-                // the m + 1 last iterates of the lifted vector (both halves), the parameter vectors, y ; xs_d (z) out
-                SlackIterates<T, CM> SV;
-                std::memset(&SV, 0, sizeof(SV));
-                SV.m = m_now;
-                for (int i = 0; i <= m_now; ++i) SV.XH[i] = X_[(xc - (m_now - i) + NXR) % NXR].p;
-                CC.gam0 = gring_[(xc - m_now + NXR) % NXR];
-                const int slack_streams = 2 * (m_now + 1) + pstreams(true, true, true) + (P.uni >= 2 ? 0 : 1) + 2;      // (pstreams counts D's vector bounds)
-                const bool snt = nt_env_ >= 0 ? nt_env_ != 0 : (double)nx * sizeof(T) * (slack_streams + (zstore ? 2 : 0)) > 340e6;
-                mv(slack_streams + (zstore ? 2 : 0), nx);
-                form_[C_FUSED_IT] = std::string("k_fused_slack_xr") + (snt ? "<NT=1>" : "<NT=0>");
-#define BZ_LAUNCH_SXR(NT_, FULL_, UNI_, KIND_, DEPTH_)                                                             \
-    launch(C_FUSED_IT, k_fused_slack_xr<T, CM, NT_, FULL_, UNI_, KIND_, DEPTH_>, gfc, SV, CC, P, (const T*)ymul_.p, gamma, X_[xd].p, zstore, nx, \
-           parts_.p, (int)SL_TRIAL)
-#define BZ_LAUNCH_SXR_U(NT_, KIND_, DEPTH_)                                                                        \
-    do { if (P.uni >= 2) BZ_LAUNCH_SXR(NT_, true, 2, KIND_, DEPTH_); else if (P.uni == 1) BZ_LAUNCH_SXR(NT_, true, 1, KIND_, DEPTH_); \
-         else BZ_LAUNCH_SXR(NT_, true, 0, KIND_, DEPTH_); } while (0)
-                // (the fast instantiations: a full memory, f = DiagQuadratic, no vector-valued parameters of g or D)
-                const bool fast = slack_fast;
-                if (fast) {
-                    const int sdepth = slackdepth_env_;
-                    const bool hk = slack_hk;
-                    form_[C_FUSED_IT] += hk ? "(fast,l1-box)" : "(fast)";
-                    if (hk && sdepth >= 1) { if (snt) BZ_LAUNCH_SXR_U(true, 1, 1); else BZ_LAUNCH_SXR_U(false, 1, 1); }
-                    else if (hk) { if (snt) BZ_LAUNCH_SXR_U(true, 1, 0); else BZ_LAUNCH_SXR_U(false, 1, 0); }
-                    else { if (snt) BZ_LAUNCH_SXR_U(true, 0, 0); else BZ_LAUNCH_SXR_U(false, 0, 0); }
-                } else if (m_now == CM) { if (snt) BZ_LAUNCH_SXR(true, true, -1, 0, 0); else BZ_LAUNCH_SXR(false, true, -1, 0, 0); }
-                else { if (snt) BZ_LAUNCH_SXR(true, false, -1, 0, 0); else BZ_LAUNCH_SXR(false, false, -1, 0, 0); }
-#undef BZ_LAUNCH_SXR_U
-#undef BZ_LAUNCH_SXR
-                sy_stale_ = true; rh_stale_ = true; res_skipped = true;
-                trial_ok = false;      // (a tau-backtracked point finishes in the generic chain, after the pairs are re-materialised)
-            } else if (xr == 2) {
-                CompactVecs<T, CM> XV;
-                XV.m = CM;
-                for (int i = 0; i < CM; ++i) {
-                    const int slot = (xc - std::max(0, m_now - i) + NXR) % NXR;      // (beyond m: x itself)
-                    XV.S[i] = X_[slot].p;
-                    XV.Y[i] = nullptr;
-                    if (i == 0) CC.gam0 = gring_[slot];
-                }
-                const bool table = !headline || famrt_env_;
-                GatePlan cur;
-                std::memset(&cur, 0, sizeof(cur));
-                for (int i = 0; i < CM; ++i) cur.S[i] = XV.S[i];
-                cur.x = X_[xp].p; cur.xd = X_[xd].p; cur.gam0 = CC.gam0; cur.gamma = (double)gamma; cur.uni = uni; cur.gfc = gfc;
-                cur.fam = fam; cur.m_now = m_now; cur.nt = nt; cur.table = table;
-                cur.keep_params = keep_params(nt, table, fam);
-                cur.lds_ring = lds_ring(nt, table);
-                if (gate_pending_ && cur == gate_plan_) {
-                    // this very launch was made early, behind the previous iteration's read-back: hand it its coefficients
-                    gate_release(CC, zstore);
-                } else {
-                    gate_abort();
-                    // streams: the m_now + 1 distinct iterates (x among them), the family's parameter vectors (mu / mu*y
-                    // unless passed as numbers); x_d (z)
-                    mv(xr2_streams + (zstore ? 1 : 0));
-                    CompactCoef<CM> C2 = CC;
-                    C2.gate_seq = 0ull;
-                    gate_launch(cur, C2, zstore);
-                }
-                sy_stale_ = true; rh_stale_ = true; res_skipped = true;
-                const int tf_now = trialfuse_env_;
-                trial_ok = tf_now != 0; trial_nt = nt; trial_uni = uni; trial_gfc = gfc; trial_XV = XV; trial_CC = CC;
-                trial_table = table; trial_fam = fam; trial_keep = cur.keep_params; trial_lq = cur.lds_ring;
-            } else if (xr) {
-                CompactVecs<T, CM> XV;
-                XV.m = CM;
-                for (int i = 0; i < CM; ++i) {
-                    XV.S[i] = X_[(xc - CM + i + NXR) % NXR].p;
-                    XV.Y[i] = RES_[(rc - CM + i + NRR) % NRR].p;
-                }
-                mv(2 * (CM + 1) + pstreams(true, true, true) + 2 + (zstore ? 1 : 0));
-                form_[C_FUSED] = std::string("k_fused_compact<XR=1") + (nt ? ",NT=1>" : ",NT=0>");
-                if (nt)
-                    launch(C_FUSED, k_fused_compact<T, CM, true, true, true, 1>, gfc, XV, CC, (const T*)X_[xp].p,
-                           (const T*)RES_[rp].p, P, gamma, X_[xd].p, zstore, RES_[rn].p, (T*)nullptr, (T*)nullptr, n, parts_.p,
-                           (int)SL_TRIAL);
-                else
-                    launch(C_FUSED, k_fused_compact<T, CM, false, true, true, 1>, gfc, XV, CC, (const T*)X_[xp].p,
-                           (const T*)RES_[rp].p, P, gamma, X_[xd].p, zstore, RES_[rn].p, (T*)nullptr, (T*)nullptr, n, parts_.p,
-                           (int)SL_TRIAL);
-                sy_stale_ = true;
-            } else
-#define BZ_LAUNCH_FC3(NT_)                                                                                        \
-    launch(C_FUSED, k_fused_compact<T, CM, NT_, true, true>, gfc, CV, CC, (const T*)X_[xp].p, (const T*)RES_[rp].p, P, \
-           gamma, X_[xd].p, zstore, RES_[rn].p, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL)
-            if (slack) {
-                // the lifted vector [x; s]: res, S[m], Y[m], xs ; xs_d, res, s_new, y_new (z) — both halves — and over n the
-                // parameter vectors and the multipliers y
-                mv(2 * (2 + 2 * CV.m + 4 + (zstore ? 1 : 0)) + pstreams(true, true, true) + (P.uni >= 2 ? 0 : 1), nx);
-                form_[C_FUSED] = std::string("k_fused_slack") + (nt ? "<NT=1>" : "<NT=0>");
-                if (nt)
-                    launch(C_FUSED, k_fused_slack<T, CM, true>, gfc, CV, CC, (const T*)X_[xp].p, (const T*)RES_[rp].p, P,
-                           (const T*)ymul_.p, gamma, X_[xd].p, zstore, RES_[rn].p, S_[spare].p, Y_[spare].p, nx, parts_.p,
-                           (int)SL_TRIAL);
-                else
-                    launch(C_FUSED, k_fused_slack<T, CM, false>, gfc, CV, CC, (const T*)X_[xp].p, (const T*)RES_[rp].p, P,
-                           (const T*)ymul_.p, gamma, X_[xd].p, zstore, RES_[rn].p, S_[spare].p, Y_[spare].p, nx, parts_.p,
-                           (int)SL_TRIAL);
-            } else {
-                // stored pairs: res, S[m], Y[m], x + the parameter vectors ; x_d, res, s_new, y_new (z)
-                mv(2 + 2 * CV.m + pstreams(true, true, true) + 4 + (zstore ? 1 : 0));
-                form_[C_FUSED] = std::string("k_fused_compact<XR=0") + (spec ? ",SPEC=1" : ",SPEC=0") + (nt ? ",NT=1>" : ",NT=0>");
-                if (off32 && nt) BZ_LAUNCH_FC3(true);
-                else if (off32) BZ_LAUNCH_FC3(false);
-                else if (nt && spec) BZ_LAUNCH_FC(true, true);
-                else if (nt) BZ_LAUNCH_FC(true, false);
-                else if (spec) BZ_LAUNCH_FC(false, true);
-                else BZ_LAUNCH_FC(false, false);
-            }
-#undef BZ_LAUNCH_FC3
-#undef BZ_LAUNCH_FC
-            // the NEXT iteration's pass, assuming this one ends the plain way (trial accepted, pair inserted, same gamma):
-            // ring one step on, one more pair
-            GatePlan nxt;
-            bool have_plan = false;
-            if (xr == 2 && gate_env_ && more_coming_ && !opt.verbose && !prof_would_pick(C_FUSED_IT)) {
-                double gr[NXR];
-                for (int i = 0; i < NXR; ++i) gr[i] = gring_[i];
-                gr[xd] = (double)gamma;
-                have_plan = gate_make_plan(xd, std::min(m_now + 1, M), gr, xr_run_ + 1, nxt);
-            }
-            if (ctx->p2p_on) {
-                // exchange + fold over the ranks + read-back in one launch (no k_collect)
-                tail_ticket = exchange_collect(SL_TRIAL, NFC, 1u << 9);
-                tail_used = true;
-            } else {
-                gather(SL_TRIAL, NFC, 1u << 9);
-                if (xr == 2 && gate_env_) {      // the read-back kernel now, so that the next pass can queue right behind it
-                    tail_ticket = collect_launch_range(SL_TRIAL, NFC, 1u << 9);
-                    tail_used = true;
-                }
-            }
-            if (have_plan) gate_prelaunch(nxt);
-            have_trial = true; fused_this = true; gx_valid = false; gz_valid = false; gram_from_trial = true;
-            n_grad += 2; n_prox += 1;
-        } else if (fused_ok && !slack) {
-            if (!res_valid) ensure_z();
-            for (int k = 0; k < 12; ++k) slot_n[SL_TRIAL + k] = grid;
-            mv((tail.mode != 2 ? 2 : 1) + 2 + pstreams(true, true, true) + 5);
-            form_[C_FUSED] = "k_fused_sep";
-            launch(C_FUSED, k_fused_sep<T>, grid, tail, (const T*)X_[xp].p, (const T*)RES_[rp].p, P, gamma,
-                   X_[xd].p, Z_[zn].p, RES_[rn].p, S_[spare].p, Y_[spare].p, (T*)nullptr, (T*)nullptr, n,
-                   parts_.p, (int)SL_TRIAL);
-            gather(SL_TRIAL, 12, 1u << 9);
-            sep_trial = true;
-            have_trial = true; fused_this = true; gx_valid = false; gz_valid = false;
-            n_grad += 2; n_prox += 1;
-        } else {
-            if (!res_valid) ensure_z();
-            // cfg 4 with images: x_d, its images under grad L and c, L(x_d) and the forward-backward step in ONE launch
-            // (k_dense_head; single rank, element-wise f, the common prox kinds)
-            head_on = densesmall_env_ && use_compact && aff_track_ && !stencil_fast_now && !generic_ && !ctx->multi() && !lp_g &&
-                      !dense_f && gx_valid && gz_valid && aff_count_ + 1 < aff_refresh_ &&
-                      (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
-            // x_d = x + d ; gradient at x_d ; state.x = x_d
-            if (head_on) {
-            } else if (use_compact) {
-                mv(2 * CV.m + 3);
-                // (full memory + a history beyond the Infinity Cache: compile-time trip counts, non-temporal history loads)
-                static const int xdnt_env = std::getenv("BZ_XDNT") ? std::atoi(std::getenv("BZ_XDNT")) : 1;
-                const bool hist_nt = xdnt_env && (double)n * sizeof(T) * (2 * CV.m + 3) > 340e6;
-                // (the template form in the name: a hardware-counter profile is matched to the instantiation that ran)
-                nm(CV.m == CM ? (hist_nt ? "k_compact_xd<FULL=1,NT=1>" : "k_compact_xd<FULL=1,NT=0>") : "k_compact_xd<FULL=0,NT=0>");
-                if (CV.m == CM && hist_nt)
-                    launch(C_XD, k_compact_xd<T, CM, true, true>, grid, CV, CC, (const T*)RES_[rp].p, (const T*)X_[xp].p, X_[xd].p, n);
-                else if (CV.m == CM)
-                    launch(C_XD, k_compact_xd<T, CM, true, false>, grid, CV, CC, (const T*)RES_[rp].p, (const T*)X_[xp].p, X_[xd].p, n);
-                else
-                launch(C_XD, k_compact_xd<T, CM>, grid, CV, CC, (const T*)RES_[rp].p, (const T*)X_[xp].p,
-                       X_[xd].p, n);
-            } else {
-                mv((tail.mode != 2 ? 2 : 1) + 2); nm("k_axpy_dot(x_d)");
-                launch(C_XD, k_axpy_dot<T>, grid, tail, (const T*)nullptr, (const T*)X_[xp].p, X_[xd].p, n,
-                       parts_.p, 0);
-            }
-            if (stencil_fast_now) {
-                // stencil fast path: {AL gradient at x_d + FB step} and {AL gradient at z + pair + stop norm}
-                // as two passes; same partial sums as the four generic kernels of the first trial
-                for (int sidx = SL_FXD; sidx <= SL_STOP; ++sidx) slot_n[sidx] = grid;
-                // (uniform penalties / zero multipliers travel as numbers, P.uni: the two stencil passes stream mu and mu*y
-                // otherwise — 4 of the iteration's 43 passes)
-                // (r03: with the compact form the second pass re-forms grad L(x_d) and res from x_d and z — k_stencil_update_c<REGX> —
-                // so this pass does not write the gradient and that one reads neither: 39 -> 36 passes over n per iteration)
-                const int regx = use_compact ? std::max(0, std::min(2, stencil_regx_env_)) : 0;
-                mv(2 + pstreams(false, true, true) + (regx >= 2 ? 2 : 3));        // x_d, b + parameters ; (grad,) z, res
-                const StencilHalo<T> halo_x = halo_exchange(X_[xd].p);
-                static const int fbnt_env = std::getenv("BZ_XDNT") ? std::atoi(std::getenv("BZ_XDNT")) : 1;
-                nm(fbnt_env && (double)n * sizeof(T) * 12 > 340e6 ? "k_stencil_fb<NT=1>" : "k_stencil_fb<NT=0>");
-                if (fbnt_env && (double)n * sizeof(T) * 12 > 340e6)
-                    launch(C_STENCIL_FB, k_stencil_fb<T, true>, grid, (const T*)X_[xd].p, P, (int64_t)desc.f_grid_nx,
-                           (int64_t)desc.f_grid_ny, gamma, regx >= 2 ? (T*)nullptr : GX_.p, Z_[zn].p, RES_[rn].p, n, parts_.p, (int)SL_FXD,
-                           (int)SL_GSUM, halo_x);
-                else
-                launch(C_STENCIL_FB, k_stencil_fb<T>, grid, (const T*)X_[xd].p, P, (int64_t)desc.f_grid_nx,
-                       (int64_t)desc.f_grid_ny, gamma, regx >= 2 ? (T*)nullptr : GX_.p, Z_[zn].p, RES_[rn].p, n, parts_.p, (int)SL_FXD,
-                       (int)SL_GSUM, halo_x);
-                const StencilHalo<T> halo_z = halo_exchange(Z_[zn].p);
-                if (use_compact) {
-                    // ... with the Gram products of the new pair and the next application's p, w in the same pass
-                    // (r03: this pass — 19 streams, 27 accumulators — runs best with ONE workgroup per CU, one resident round and a
-                    // 27-slot epilogue per CU: 102 us against 108 with two or four and 114 on the problem's grid of 2048, at 2048^2 ;
-                    // the other two passes want the largest grid.  BZ_SUC_GRID=k: k per CU, 0: `grid`.)
-                    const int g_upd = suc_grid_env_ > 0 ? std::min(grid, suc_grid_env_ * std::max(1, num_cus)) : grid;
-                    for (int sidx = 0; sidx < NFC; ++sidx) slot_n[SL_TRIAL + sidx] = sidx < 5 ? grid : g_upd;      // (slots 0..4: k_stencil_fb's)
-                    mv(2 + pstreams(false, true, false) + (5 - regx) + 2 + 2 * CV.m);
-#define BZ_LAUNCH_SUC_R(FULL_, NT_, REGX_)                                                                        \
-    launch(C_STENCIL_UPD, k_stencil_update_c<T, CM, FULL_, NT_, REGX_>, g_upd, CV, (const T*)Z_[zn].p, P, (int64_t)desc.f_grid_nx, \
-           (int64_t)desc.f_grid_ny, (const T*)X_[xd].p, (const T*)X_[xp].p, (const T*)RES_[rn].p, (const T*)RES_[rp].p, \
-           (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL, halo_z, halo_x)
-#define BZ_LAUNCH_SUC(FULL_, NT_)                                                                                 \
-    do { if (regx >= 2) BZ_LAUNCH_SUC_R(FULL_, NT_, 2); else if (regx == 1) BZ_LAUNCH_SUC_R(FULL_, NT_, 1);      \
-         else BZ_LAUNCH_SUC_R(FULL_, NT_, 0); } while (0)
-                    {
-                        static const int xdnt_env = std::getenv("BZ_XDNT") ? std::atoi(std::getenv("BZ_XDNT")) : 1;
-                        const bool hist_nt = xdnt_env && (double)n * sizeof(T) * (2 * CV.m + 12) > 340e6;
-                        if (regx >= 2) nm(CV.m == CM ? (hist_nt ? "k_stencil_update_c<FULL=1,NT=1,REGX=2>" : "k_stencil_update_c<FULL=1,NT=0,REGX=2>")
-                                                     : "k_stencil_update_c<FULL=0,NT=0,REGX=2>");
-                        else if (regx == 1) nm(CV.m == CM ? (hist_nt ? "k_stencil_update_c<FULL=1,NT=1,REGX=1>" : "k_stencil_update_c<FULL=1,NT=0,REGX=1>")
-                                                          : "k_stencil_update_c<FULL=0,NT=0,REGX=1>");
-                        else nm(CV.m == CM ? (hist_nt ? "k_stencil_update_c<FULL=1,NT=1>" : "k_stencil_update_c<FULL=1,NT=0>")
-                                           : "k_stencil_update_c<FULL=0,NT=0>");
-                        if (CV.m == CM && hist_nt) BZ_LAUNCH_SUC(true, true);
-                        else if (CV.m == CM) BZ_LAUNCH_SUC(true, false);
-                        else BZ_LAUNCH_SUC(false, false);
-                    }
-#undef BZ_LAUNCH_SUC
-#undef BZ_LAUNCH_SUC_R
-                    if (ctx->p2p_on) {
-                        // exchange + fold over the ranks + read-back of all 32 slots in one launch
-                        tail_ticket = exchange_collect(SL_TRIAL, NFC, 1u << 9);
-                        tail_used = true;
-                    }
-                    gram_from_trial = true;
-                } else {
-                mv(2 + pstreams(false, true, false) + 5 + 2);   // z, b + parameters, x_d, x, res, res_prev, grad ; s, y
-                nm("k_stencil_update");
-                launch(C_STENCIL_UPD, k_stencil_update<T>, grid, (const T*)Z_[zn].p, P, (int64_t)desc.f_grid_nx,
-                       (int64_t)desc.f_grid_ny, (const T*)X_[xd].p, (const T*)X_[xp].p, (const T*)RES_[rn].p,
-                       (const T*)RES_[rp].p, (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, (T*)nullptr, n, parts_.p,
-                       (int)SL_FZ, (int)SL_YS, halo_z);
-                }
-                have_trial = true; gx_valid = regx < 2; gz_valid = false;
-                n_grad += 2; n_prox += 1;
-            } else if (aff_track_) {
-                // gradient (and c) at x_d into the candidate buffers, then trade: GX_ = grad L(x_d), GXN_ = grad L(x_prev)
-                state_imgs = gx_valid && gz_valid;      // (the images of this state's x and z are what GX_, GZ_, CXS_, CZS_ hold)
-                if (use_compact && gx_valid && gz_valid && aff_count_ + 1 < aff_refresh_) {
-                    ++aff_count_; ++n_affine_; img_trial = true;
-                    CompactVecs<T, CM> VA = image_vecs(true), VG = image_vecs(false);
-                    if (head_on) {
-                        DenseHeadArgs<T, CM> a;
-                        std::memset(&a, 0, sizeof(a));
-                        a.V = CV; a.VG = VG; a.VA = VA; a.C = CC;
-                        a.res = RES_[rp].p; a.x = X_[xp].p; a.x_d = X_[xd].p;
-                        a.gbase = GX_.p; a.gzimg = GZ_.p; a.gout = GXN_.p;
-                        a.cbase = CXS_.p; a.czimg = CZS_.p; a.cout = CXD_.p; a.yupd = YU_.p;
-                        a.z = Z_[zn].p; a.res_new = RES_[rn].p; a.gamma = gamma;
-                        a.n = n; a.ny = ny; a.parts = parts_.p;
-                        a.slot_f = SL_FXD; a.slot_pen = SL_PXD; a.slot_fb = SL_GSUM; a.gn = grid; a.gy = grid_y;
-                        slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
-                        for (int kk = 0; kk < 3; ++kk) slot_n[SL_GSUM + kk] = grid;
-                        // (what the six kernels move: k_compact_xd, the two images, f, yupd, the FB step)
-                        mv(2 * CV.m + 3); mv(2 * VA.m + 3, ny); mv(2 * VG.m + 3); mv(1 + pstreams(true, false, false));
-                        mv(2 + pstreams(false, true, false), ny); mv(4 + pstreams(false, false, true));
-                        nm("k_dense_head");
-                        launch(C_MISC, k_dense_head<T, CM>, grid + grid_y, a, P);
-                        head_fb = true;
-                    } else {
-                    mv(2 * VA.m + 3, ny); nm("k_affine_image");
-                    launch(C_MISC, k_affine_image<T, CM>, grid_y, VA, CC, (const T*)CXS_.p, (const T*)CZS_.p, CXD_.p, ny);
-                    mv(2 * VG.m + 3);
-                    launch(C_MISC, k_affine_image<T, CM>, grid, VG, CC, (const T*)GX_.p, (const T*)GZ_.p, GXN_.p, n);
-                    // the value L(x_d): f element-wise, the penalty from the image of c
-                    slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
-                    mv(1 + pstreams(true, false, false));
-                    launch(C_MISC, k_fvalue_elem<T>, grid, (const T*)X_[xd].p, P, n, parts_.p, (int)SL_FXD, (const T*)nullptr);
-                    mv(2 + pstreams(false, true, false), ny);
-                    launch(C_MISC, k_yupd<T>, grid_y, (const T*)CXD_.p, P, YU_.p, ny, parts_.p, (int)SL_PXD);
-                    }
-                } else {
-                    aff_count_ = 0;
-                    cx_keep_ = CXD_.p;
-                    algrad(X_[xd].p, GXN_.p, SL_FXD);
-                    cx_keep_ = nullptr;
-                }
-                std::swap(GX_.p, GXN_.p); std::swap(GX_.n, GXN_.n);
-                ++n_grad; gx_valid = true;
-            } else {
-                algrad(X_[xd].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
-            }
+        it.xp = xc; it.xd = (xc + 1) % NXR; it.xb = (xc + 2) % NXR;
+        it.rp = rc; it.rn = (rc + 1) % NRR; it.zp = zc; it.zn = 1 - zc;
+        it.xcur = it.xd;
+    }
+
+    // ---- the first trial, one function per path
+    // one-pass kernels with the compact form: x_d, the FB step, grad L at z, the pair and its products in one launch
+    void trial_onepass(Iter& it) {
+        // 176 VGPRs -> two 256-thread blocks per CU: one resident round of blocks (each block pays the
+        // coefficient prologue and a 20-slot reduction epilogue once)
+        int gfc = std::min(grid, (env_.gfc > 0 ? env_.gfc : 2) * std::max(1, num_cus));
+        // non-temporal loads/stores once the working set (2M + 11 vectors) no longer fits the 256 MB Infinity
+        // Cache.  Measured fused-pass times, default policy vs non-temporal: n = 1.25e6 (210 MB) 39.0 / 44.5 us,
+        // 1.8e6 (302 MB) 51.0 / 60.4, 2.5e6 (420 MB) 90.1 / 81.5, 5e6 (840 MB) 171 / 159, 1e7 322 / 314.
+        // headline family with everything uniform fixed at compile time (see the kernel)
+        const int fam = fused_family();
+        const bool headline = env_.spec && fam == FAM_HEADLINE;
+        const bool spec = headline && it.CV.m == CM;
+        // z is the solution the caller reads when the solve stops: once the stop norm is within a factor 10 of
+        // the tolerance, store it (one more write stream for the last iteration or two) rather than
+        // re-materialise it afterwards with two generic kernels (the same bits either way)
+        // ... and during the first 20 iterations of a solve: ALPS subproblems are often that short (13 of them
+        // with 180 inner iterations in all on cfg 2), and a stored z costs a tenth of re-materialising one
+        // (tol = 0: the caller has said the solve never stops by itself — bench.py's timed region, the step-wise parity
+        // tests — so no early stop is being prepared for; whoever asks for z gets it re-materialised, same bits)
+        const bool near_stop = (double)stop_norm_ <= 10.0 * opt.tol || (k_ <= 20 && opt.tol > 0.0);
+        T* const zstore = (env_.skipz && !near_stop) ? (T*)nullptr : Z_[it.zn].p;
+        it.z_skipped = zstore == nullptr;
+        const bool small = small_vectors();
+        // 0: stored pairs; 1: pairs re-formed from the iterate / residual rings (full memory only); 2: residuals
+        // re-evaluated too — possible as soon as every stored pair is a difference of ring neighbours, also
+        // with a partial memory (the absent pairs are x - x = 0 with zero coefficients)
+        const int m_now = (int)order.size();
+        int xr = 0;
+        // (the slack form of ALS has its own iterate-history kernel, k_fused_slack_xr: BZ_XR >= 2, any element-wise kinds)
+        if (env_.xr && small && (fam >= 0 || slack) && xr_run_ >= m_now) {
+            if (env_.xr >= 2) xr = 2;
+            else if (headline && m_now == CM && !rh_stale_) xr = 1;
+            // (only the oldest stored iterate may carry another gamma — see CompactCoef::gam0)
+            for (int i = 1; i < m_now; ++i)
+                if (gring_[(xc - m_now + i + NXR) % NXR] != (double)gamma) xr = 0;
+            if (xr == 1 && gring_[(xc - m_now + NXR) % NXR] != (double)gamma) xr = 0;
         }
-        T sigma = beta * (T(0.5) / gamma) * (T(1) - alpha);
-        const T tol0 = T(10) * eps * (T(1) + std::abs(FBE_x));
-        const T threshold = FBE_x - sigma * (nr0 * nr0) + tol0;
-        std::vector<double> v;
-        int nbt = 0;
-        bool gen_gram = false;      // the generic trial just launched carried the compact form's products (k_update_c)
-        int m_gram = m_at_trial;    // ... measured against a memory of this many pairs
-        for (int k = 1; k <= max_bt; ++k) {
-            if (!have_trial) {
-                if (!gx_valid) { algrad(X_[xcur].p, GX_.p, SL_FXD); gx_valid = true; }
-                if (head_fb) head_fb = false;      // (k_dense_head made this step already)
-                else fbstep(X_[xcur].p, GX_.p, gamma, Z_[zn].p, RES_[rn].p, SL_GSUM);
-                gather(SL_GSUM, 3, 0u);
-                ++n_prox;
-                T* const gz_dst = aff_track_ ? GZN_.p : GZ_.p;      // (affine images: grad L(z_prev) is still needed)
-                if (aff_track_) cx_keep_ = CZN_.p;
-                // cfg 4: the fold of the row-group partials, the pair with its products and the pair's images in ONE launch
-                // behind the pass over A (k_dense_tail)
-                const bool tail_on = densesmall_env_ && aff_track_ && compact_ok && !generic_ && !ctx->multi() &&
-                                     desc.c_kind == BZ_C_DENSE_AFFINE && dense_fused_on();
-                if (tail_on) {
-                    slot_n[SL_FZ] = grid;
-                    dense_fused_launch(Z_[zn].p, SL_FZ + 1);
-                    ++n_grad; gz_valid = true;
-                    cx_keep_ = nullptr;
-                    const CompactVecs<T, CM> VG = compact_vecs();
-                    DenseTailArgs<T, CM> a;
-                    std::memset(&a, 0, sizeof(a));
-                    a.V = VG; a.part = GT_.p; a.nchunks = df_groups_; a.pstride = npad;
-                    a.z = Z_[zn].p; a.gz = gz_dst;
-                    a.x = X_[xcur].p; a.x_prev = X_[xp].p; a.res = RES_[rn].p; a.res_prev = RES_[rp].p; a.gx = GX_.p;
-                    a.gamma = gamma; a.s_new = S_[spare].p; a.y_new = Y_[spare].p;
-                    a.gx_prev = GXN_.p; a.gz_prev = GZ_.p; a.gs_img = GS_[spare].p; a.gy_img = GY_[spare].p;
-                    a.cx = CXD_.p; a.cx_prev = CXS_.p; a.cz = CZN_.p; a.cz_prev = CZS_.p;
-                    a.cs_img = AS_[spare].p; a.cy_img = AY_[spare].p;
-                    a.n = n; a.ny = ny; a.parts = parts_.p; a.slot_fz = SL_FZ; a.slot_upd = SL_YS; a.gn = grid; a.gy = grid_y;
-                    for (int kk = 0; kk < 3 + 4 * CM + 2; ++kk) slot_n[SL_YS + kk] = grid;
-                    // (what the four kernels move: the fold + f terms, k_update_c, the two image pairs)
-                    mv(df_groups_ + 2 + pstreams(true, false, false)); mv(8 + 2 * VG.m); mv(6, ny); mv(6);
-                    nm("k_dense_tail");
-                    launch(C_UPDATE, k_dense_tail<T, CM>, grid + grid_y, a, P);
-                    gather(SL_FZ, 2, 0u, 2u);
-                    gather(SL_YS, 3 + 4 * CM + 2, 4u);
-                    gen_gram = true; m_gram = VG.m; tail_used = false;
-                } else {
-                algrad(Z_[zn].p, gz_dst, SL_FZ); ++n_grad; gz_valid = true;
-                cx_keep_ = nullptr;
-                if (compact_ok) {
-                    // the pair, the stop norm AND the compact form's products (Gram products of the candidate pair, the
-                    // next application's p, w) in one pass and one read-back — against the memory as it is NOW
-                    const CompactVecs<T, CM> VG = compact_vecs();
-                    for (int kk = 0; kk < 3 + 4 * CM + 2; ++kk) slot_n[SL_YS + kk] = grid;
-                    mv(8 + 2 * VG.m); nm("k_update_c");
-                    launch(C_UPDATE, k_update_c<T, CM>, grid, VG, (const T*)X_[xcur].p, (const T*)X_[xp].p,
-                           (const T*)RES_[rn].p, (const T*)RES_[rp].p, (const T*)GX_.p, (const T*)gz_dst, gamma,
-                           S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL);
-                    gather(SL_YS, 3 + 4 * CM + 2, 4u);
-                    gen_gram = true; m_gram = VG.m; tail_used = false;
-                } else {
-                for (int kk = 0; kk < 3; ++kk) slot_n[SL_YS + kk] = grid;
-                mv(8);
-                launch(C_UPDATE, k_update<T>, grid, (const T*)X_[xcur].p, (const T*)X_[xp].p,
-                       (const T*)RES_[rn].p, (const T*)RES_[rp].p, (const T*)GX_.p, (const T*)gz_dst, gamma,
-                       S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_YS);
-                gather(SL_YS, 3, 4u);
-                }
-                if (aff_track_) {
-                    // images of the candidate pair (s = x - x_prev, y = res - res_prev) under c and grad L
-                    mv(6, ny);
-                    launch(C_MISC, k_image_pair<T>, grid_y, (const T*)CXD_.p, (const T*)CXS_.p, (const T*)CZN_.p,
-                           (const T*)CZS_.p, AS_[spare].p, AY_[spare].p, ny);
-                    mv(6);
-                    launch(C_MISC, k_image_pair<T>, grid, (const T*)GX_.p, (const T*)GXN_.p, (const T*)GZN_.p,
-                           (const T*)GZ_.p, GS_[spare].p, GY_[spare].p, n);
-                }
-                }
+        if (sy_stale_ && !xr) materialize_pairs();
+        if (xr != 2 && !res_valid) ensure_z();
+        // the iterate-history form keeps two packs of loads in flight per wave and runs best with ONE wave per
+        // SIMD (n = 1e7: 134 vs 140 us; 1.25e6: 28.5 vs 30.2 us): the wave has the vector ALU to itself and
+        // the 32-scalar epilogue runs half as often.  (A different grid is a different summation tree: the
+        // forms then agree to rounding, not bit for bit — BZ_GFC pins one grid for all of them.)
+        // (the slack form's fast instantiations: a full memory, f = DiagQuadratic, no vector-valued parameters of g or D —
+        // pipelined like the headline kernel, 256 VGPRs + spill AGPRs: one workgroup per CU there too)
+        const bool slack_fast = slack && xr == 2 && env_.slackfast && m_now == CM && desc.f_kind == BZ_F_DIAG_QUADRATIC &&
+                                pstreams(false, true, true) == 2 - std::min(2, (int)P.uni) &&
+                                !(P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX));
+        // ... with the kinds fixed too (g = NormL1, D = Box: the ALS form of cfg 2), one pack of loads ahead
+        const bool slack_hk = slack_fast && env_.slackkind && P.g_kind == BZ_G_NORM_L1 && P.D_kind == BZ_D_BOX;
+        if (xr == 2 && env_.gfc <= 0 && (!slack || (slack_hk && env_.slackdepth > 0))) gfc = std::min(grid, std::max(1, num_cus));
+        for (int k = 0; k < NFC; ++k) slot_n[SL_TRIAL + k] = gfc;
+        // (the vectors this pass touches: history + x_d + z + the parameter vectors (+ res, s, y))
+        const int nvec = (xr == 2 ? xr2_streams(m_now) : 2 * CM + 5 + pstreams(true, true, true)) + (zstore ? 1 : 0);
+        const bool nt = env_.nt >= 0 ? env_.nt != 0 : (double)n * sizeof(T) * nvec > 340e6;
+        if (gate_pending_ && xr != 2) gate_abort();
+        if (xr == 2 && slack) onepass_slack_xr(it, gfc, zstore, slack_fast, slack_hk);
+        else if (xr == 2) onepass_xr2(it, zstore);
+        else if (xr) onepass_xr1(it, gfc, zstore, nt);
+        else onepass_stored(it, gfc, zstore, nt, spec, small && spec);
+        // (XR = 2 with the gate: the read-back kernel now, so that the next iteration's pass can queue right behind it)
+        onepass_scalars(it, xr == 2 && gate_env_);
+        if (xr == 2 && gate_env_ && more_coming_ && !opt.verbose && !prof_would_pick(C_FUSED_IT)) gate_prelaunch(it.xd, m_now);
+        it.have_trial = true; it.fused_this = true; gx_valid = false; gz_valid = false; it.gram_from_trial = true;
+        n_grad += 2; n_prox += 1;
+    }
+    // the one-pass trial's scalars: exchanged, folded over the ranks and read back in one launch (p2p, no k_collect), or
+    // gathered and, with launch_now, their read-back launched at once (wait_host later)
+    void onepass_scalars(Iter& it, bool launch_now) {
+        it.tail_used = ctx->p2p_on || launch_now;
+        if (ctx->p2p_on) {
+            it.tail_ticket = exchange_collect(SL_TRIAL, NFC, 1u << 9);
+        } else {
+            gather(SL_TRIAL, NFC, 1u << 9);
+            if (launch_now) it.tail_ticket = collect_launch_range(SL_TRIAL, NFC, 1u << 9);
+        }
+    }
+    // ALS: the iterate-history pass of the lifted vector (k_fused_slack_xr)
+    void onepass_slack_xr(Iter& it, int gfc, T* zstore, bool fast, bool hk) {
+        // the m + 1 last iterates of the lifted vector (both halves), the parameter vectors, y ; xs_d (z) out
+        const int m_now = (int)order.size();
+        SlackIterates<T, CM> SV;
+        std::memset(&SV, 0, sizeof(SV));
+        SV.m = m_now;
+        for (int i = 0; i <= m_now; ++i) SV.XH[i] = X_[(xc - (m_now - i) + NXR) % NXR].p;
+        it.CC.gam0 = gring_[(xc - m_now + NXR) % NXR];
+        const int slack_streams = 2 * (m_now + 1) + pstreams(true, true, true) + (P.uni >= 2 ? 0 : 1) + 2;      // (pstreams counts D's vector bounds)
+        const bool snt = env_.nt >= 0 ? env_.nt != 0 : (double)nx * sizeof(T) * (slack_streams + (zstore ? 2 : 0)) > 340e6;
+        mv(slack_streams + (zstore ? 2 : 0), nx);
+        form_[C_FUSED_IT] = std::string("k_fused_slack_xr") + (snt ? "<NT=1>" : "<NT=0>");
+        // (the fast instantiations: a full memory, f = DiagQuadratic, no vector-valued parameters of g or D)
+        if (fast) form_[C_FUSED_IT] += hk ? "(fast,l1-box)" : "(fast)";
+        auto go = [&](auto kernel) {
+            launch(C_FUSED_IT, kernel, gfc, SV, it.CC, P, (const T*)ymul_.p, gamma, X_[it.xd].p, zstore, nx, parts_.p, (int)SL_TRIAL);
+        };
+        with_bool(snt, [&](auto nt_) {
+            constexpr bool NT = decltype(nt_)::value;
+            if (fast) {
+                with_uni(P.uni, [&](auto un) {
+                    constexpr int UNI = decltype(un)::value;
+                    if (hk && env_.slackdepth >= 1) go(k_fused_slack_xr<T, CM, NT, true, UNI, 1, 1>);
+                    else if (hk) go(k_fused_slack_xr<T, CM, NT, true, UNI, 1, 0>);
+                    else go(k_fused_slack_xr<T, CM, NT, true, UNI, 0, 0>);
+                });
+            } else if (m_now == CM) go(k_fused_slack_xr<T, CM, NT, true, -1, 0, 0>);
+            else go(k_fused_slack_xr<T, CM, NT, false, -1, 0, 0>);
+        });
+        sy_stale_ = true; rh_stale_ = true; it.res_skipped = true;
+        it.trial_ok = false;      // (a tau-backtracked point finishes in the generic chain, after the pairs are re-materialised)
+    }
+    // the headline or family-table pass on the iterate history (k_fused_compact<XR=2>): released if it was pre-launched
+    void onepass_xr2(Iter& it, T* zstore) {
+        GatePlan cur;
+        if (!xr2_plan(xc, (int)order.size(), gring_, xr_run_, zstore != nullptr, cur))
+            throw Error(BZ_ERR_STATE, "the iterate-history pass does not apply");
+        it.CC.gam0 = cur.gam0;
+        if (gate_pending_ && cur == gate_plan_) {
+            // this very launch was made early, behind the previous iteration's read-back: hand it its coefficients
+            gate_release(it.CC, zstore);
+        } else {
+            gate_abort();
+            mv(xr2_streams(cur.m_now) + (zstore ? 1 : 0));
+            launch_xr2(cur, it.CC, 0, cur.xd, zstore, (T*)nullptr);
+        }
+        sy_stale_ = true; rh_stale_ = true; it.res_skipped = true;
+        it.trial_ok = env_.trialfuse != 0; it.trial_plan = cur; it.trial_coef = it.CC;
+    }
+    // pairs re-formed from the iterate and residual rings (k_fused_compact<XR=1>)
+    void onepass_xr1(Iter& it, int gfc, T* zstore, bool nt) {
+        CompactVecs<T, CM> XV;
+        XV.m = CM;
+        for (int i = 0; i < CM; ++i) {
+            XV.S[i] = X_[(xc - CM + i + NXR) % NXR].p;
+            XV.Y[i] = RES_[(rc - CM + i + NRR) % NRR].p;
+        }
+        mv(2 * (CM + 1) + pstreams(true, true, true) + 2 + (zstore ? 1 : 0));
+        form_[C_FUSED] = std::string("k_fused_compact<XR=1") + (nt ? ",NT=1>" : ",NT=0>");
+        with_bool(nt, [&](auto nt_) {
+            launch(C_FUSED, k_fused_compact<T, CM, decltype(nt_)::value, true, true, 1>, gfc, XV, it.CC, (const T*)X_[it.xp].p,
+                   (const T*)RES_[it.rp].p, P, gamma, X_[it.xd].p, zstore, RES_[it.rn].p, (T*)nullptr, (T*)nullptr, n, parts_.p,
+                   (int)SL_TRIAL);
+        });
+        sy_stale_ = true;
+    }
+    // the stored pairs S, Y (k_fused_slack for the lifted vector of ALS, k_fused_compact<XR=0>)
+    void onepass_stored(Iter& it, int gfc, T* zstore, bool nt, bool spec, bool off32) {
+        if (slack) {
+            // the lifted vector [x; s]: res, S[m], Y[m], xs ; xs_d, res, s_new, y_new (z) — both halves — and over n the
+            // parameter vectors and the multipliers y
+            mv(2 * (2 + 2 * it.CV.m + 4 + (zstore ? 1 : 0)) + pstreams(true, true, true) + (P.uni >= 2 ? 0 : 1), nx);
+            form_[C_FUSED] = std::string("k_fused_slack") + (nt ? "<NT=1>" : "<NT=0>");
+            with_bool(nt, [&](auto nt_) {
+                launch(C_FUSED, k_fused_slack<T, CM, decltype(nt_)::value>, gfc, it.CV, it.CC, (const T*)X_[it.xp].p,
+                       (const T*)RES_[it.rp].p, P, (const T*)ymul_.p, gamma, X_[it.xd].p, zstore, RES_[it.rn].p, S_[spare].p,
+                       Y_[spare].p, nx, parts_.p, (int)SL_TRIAL);
+            });
+            return;
+        }
+        // res, S[m], Y[m], x + the parameter vectors ; x_d, res, s_new, y_new (z)
+        mv(2 + 2 * it.CV.m + pstreams(true, true, true) + 4 + (zstore ? 1 : 0));
+        form_[C_FUSED] = std::string("k_fused_compact<XR=0") + (spec ? ",SPEC=1" : ",SPEC=0") + (nt ? ",NT=1>" : ",NT=0>");
+        auto go = [&](auto kernel) {
+            launch(C_FUSED, kernel, gfc, it.CV, it.CC, (const T*)X_[it.xp].p, (const T*)RES_[it.rp].p, P, gamma, X_[it.xd].p,
+                   zstore, RES_[it.rn].p, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL);
+        };
+        if (off32 && nt) go(k_fused_compact<T, CM, true, true, true>);
+        else if (off32) go(k_fused_compact<T, CM, false, true, true>);
+        else if (nt && spec) go(k_fused_compact<T, CM, true, true>);
+        else if (nt) go(k_fused_compact<T, CM, true, false>);
+        else if (spec) go(k_fused_compact<T, CM, false, true>);
+        else go(k_fused_compact<T, CM, false, false>);
+    }
+    // k_fused_sep: the one-pass kernel of the element-wise kinds with the two-loop / Broyden direction
+    void trial_sep(Iter& it) {
+        if (!res_valid) ensure_z();
+        for (int k = 0; k < 12; ++k) slot_n[SL_TRIAL + k] = grid;
+        mv((it.tail.mode != 2 ? 2 : 1) + 2 + pstreams(true, true, true) + 5);
+        form_[C_FUSED] = "k_fused_sep";
+        launch(C_FUSED, k_fused_sep<T>, grid, it.tail, (const T*)X_[it.xp].p, (const T*)RES_[it.rp].p, P, gamma,
+               X_[it.xd].p, Z_[it.zn].p, RES_[it.rn].p, S_[spare].p, Y_[spare].p, (T*)nullptr, (T*)nullptr, n,
+               parts_.p, (int)SL_TRIAL);
+        gather(SL_TRIAL, 12, 1u << 9);
+        it.sep_trial = true;
+        it.have_trial = true; it.fused_this = true; gx_valid = false; gz_valid = false;
+        n_grad += 2; n_prox += 1;
+    }
+    // the kernel chain: x_d = x + d (k_dense_head, k_compact_xd or k_axpy_dot), then the stencil passes, or grad L at x_d
+    // (affine images or an evaluation); the FB step and the rest follow in finish_chain_trial
+    void trial_chain(Iter& it) {
+        if (!res_valid) ensure_z();
+        // cfg 4 with images: x_d, its images under grad L and c, L(x_d) and the forward-backward step in ONE launch
+        // (k_dense_head; single rank, element-wise f, the common prox kinds)
+        it.head_on = env_.densesmall && it.use_compact && aff_track_ && !it.stencil_fast_now && !generic_ && !ctx->multi() && !lp_g &&
+                     !dense_f && gx_valid && gz_valid && aff_count_ + 1 < aff_refresh_ &&
+                     (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
+        // x_d = x + d ; gradient at x_d ; state.x = x_d
+        const T *res = RES_[it.rp].p, *x = X_[it.xp].p;
+        if (it.head_on) {
+        } else if (it.use_compact) {
+            const CompactVecs<T, CM>& CV = it.CV;
+            mv(2 * CV.m + 3);
+            // (full memory + a history beyond the Infinity Cache: compile-time trip counts, non-temporal history loads)
+            const bool hist_nt = env_.xdnt && (double)n * sizeof(T) * (2 * CV.m + 3) > 340e6;
+            // (the template form in the name: a hardware-counter profile is matched to the instantiation that ran)
+            nm(CV.m == CM ? (hist_nt ? "k_compact_xd<FULL=1,NT=1>" : "k_compact_xd<FULL=1,NT=0>") : "k_compact_xd<FULL=0,NT=0>");
+            if (CV.m == CM && hist_nt) launch(C_XD, k_compact_xd<T, CM, true, true>, grid, CV, it.CC, res, x, X_[it.xd].p, n);
+            else if (CV.m == CM) launch(C_XD, k_compact_xd<T, CM, true, false>, grid, CV, it.CC, res, x, X_[it.xd].p, n);
+            else launch(C_XD, k_compact_xd<T, CM>, grid, CV, it.CC, res, x, X_[it.xd].p, n);
+        } else {
+            mv((it.tail.mode != 2 ? 2 : 1) + 2); nm("k_axpy_dot(x_d)");
+            launch(C_XD, k_axpy_dot<T>, grid, it.tail, (const T*)nullptr, x, X_[it.xd].p, n, parts_.p, 0);
+        }
+        if (it.stencil_fast_now) {
+            chain_stencil(it);
+        } else if (aff_track_) {
+            chain_images(it);
+        } else {
+            algrad(X_[it.xd].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
+        }
+    }
+    // Stencil5pt: {AL gradient at x_d + FB step} and {AL gradient at z + pair + stop norm} as two passes; same partial
+    // sums as the four generic kernels of the first trial
+    void chain_stencil(Iter& it) {
+        const int xd = it.xd, zn = it.zn;
+        for (int sidx = SL_FXD; sidx <= SL_STOP; ++sidx) slot_n[sidx] = grid;
+        // (uniform penalties / zero multipliers travel as numbers, P.uni: the two stencil passes stream mu and mu*y
+        // otherwise — 4 of the iteration's 43 passes)
+        // (r03: with the compact form the second pass re-forms grad L(x_d) and res from x_d and z — k_stencil_update_c<REGX> —
+        // so this pass does not write the gradient and that one reads neither: 39 -> 36 passes over n per iteration)
+        const int regx = it.use_compact ? std::max(0, std::min(2, env_.stencil_regx)) : 0;
+        mv(2 + pstreams(false, true, true) + (regx >= 2 ? 2 : 3));        // x_d, b + parameters ; (grad,) z, res
+        const StencilHalo<T> halo_x = halo_exchange(X_[xd].p);
+        const bool fb_nt = env_.xdnt && (double)n * sizeof(T) * 12 > 340e6;
+        nm(fb_nt ? "k_stencil_fb<NT=1>" : "k_stencil_fb<NT=0>");
+        with_bool(fb_nt, [&](auto nt_) {
+            launch(C_STENCIL_FB, k_stencil_fb<T, decltype(nt_)::value>, grid, (const T*)X_[xd].p, P, (int64_t)desc.f_grid_nx,
+                   (int64_t)desc.f_grid_ny, gamma, regx >= 2 ? (T*)nullptr : GX_.p, Z_[zn].p, RES_[it.rn].p, n, parts_.p,
+                   (int)SL_FXD, (int)SL_GSUM, halo_x);
+        });
+        const StencilHalo<T> halo_z = halo_exchange(Z_[zn].p);
+        if (it.use_compact) {
+            // ... with the Gram products of the new pair and the next application's p, w in the same pass
+            // (r03: this pass — 19 streams, 27 accumulators — runs best with ONE workgroup per CU, one resident round and a
+            // 27-slot epilogue per CU: 102 us against 108 with two or four and 114 on the problem's grid of 2048, at 2048^2 ;
+            // the other two passes want the largest grid.  BZ_SUC_GRID=k: k per CU, 0: `grid`.)
+            const CompactVecs<T, CM>& CV = it.CV;
+            const int g_upd = env_.suc_grid > 0 ? std::min(grid, env_.suc_grid * std::max(1, num_cus)) : grid;
+            for (int sidx = 0; sidx < NFC; ++sidx) slot_n[SL_TRIAL + sidx] = sidx < 5 ? grid : g_upd;      // (slots 0..4: k_stencil_fb's)
+            mv(2 + pstreams(false, true, false) + (5 - regx) + 2 + 2 * CV.m);
+            const bool hist_nt = env_.xdnt && (double)n * sizeof(T) * (2 * CV.m + 12) > 340e6;
+            static const char* const forms[3][3] = {
+                {"k_stencil_update_c<FULL=0,NT=0>", "k_stencil_update_c<FULL=1,NT=0>", "k_stencil_update_c<FULL=1,NT=1>"},
+                {"k_stencil_update_c<FULL=0,NT=0,REGX=1>", "k_stencil_update_c<FULL=1,NT=0,REGX=1>", "k_stencil_update_c<FULL=1,NT=1,REGX=1>"},
+                {"k_stencil_update_c<FULL=0,NT=0,REGX=2>", "k_stencil_update_c<FULL=1,NT=0,REGX=2>", "k_stencil_update_c<FULL=1,NT=1,REGX=2>"}};
+            nm(forms[regx][CV.m == CM ? 1 + hist_nt : 0]);
+            auto go = [&](auto full_, auto nt_) {
+                constexpr bool FULL = decltype(full_)::value, NT = decltype(nt_)::value;
+                auto run = [&](auto kernel) {
+                    launch(C_STENCIL_UPD, kernel, g_upd, CV, (const T*)Z_[zn].p, P, (int64_t)desc.f_grid_nx, (int64_t)desc.f_grid_ny,
+                           (const T*)X_[xd].p, (const T*)X_[it.xp].p, (const T*)RES_[it.rn].p, (const T*)RES_[it.rp].p,
+                           (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL, halo_z, halo_x);
+                };
+                if (regx >= 2) run(k_stencil_update_c<T, CM, FULL, NT, 2>);
+                else if (regx == 1) run(k_stencil_update_c<T, CM, FULL, NT, 1>);
+                else run(k_stencil_update_c<T, CM, FULL, NT, 0>);
+            };
+            if (CV.m == CM && hist_nt) go(std::true_type{}, std::true_type{});
+            else if (CV.m == CM) go(std::true_type{}, std::false_type{});
+            else go(std::false_type{}, std::false_type{});
+            if (ctx->p2p_on) {
+                // exchange + fold over the ranks + read-back of all 32 slots in one launch
+                it.tail_ticket = exchange_collect(SL_TRIAL, NFC, 1u << 9);
+                it.tail_used = true;
             }
-            if ((have_trial && gram_from_trial) || gen_gram) {
-                v = (have_trial && tail_used) ? wait_host(NFC, tail_ticket) : collect_range(SL_TRIAL, NFC, 1u << 9);
-                gram_from_trial = true; gen_gram = false;
+            it.gram_from_trial = true;
+        } else {
+            mv(2 + pstreams(false, true, false) + 5 + 2);   // z, b + parameters, x_d, x, res, res_prev, grad ; s, y
+            nm("k_stencil_update");
+            launch(C_STENCIL_UPD, k_stencil_update<T>, grid, (const T*)Z_[zn].p, P, (int64_t)desc.f_grid_nx,
+                   (int64_t)desc.f_grid_ny, (const T*)X_[xd].p, (const T*)X_[it.xp].p, (const T*)RES_[it.rn].p,
+                   (const T*)RES_[it.rp].p, (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, (T*)nullptr, n, parts_.p,
+                   (int)SL_FZ, (int)SL_YS, halo_z);
+        }
+        it.have_trial = true; gx_valid = regx < 2; gz_valid = false;
+        n_grad += 2; n_prox += 1;
+    }
+    // cfg 4: gradient (and c) at x_d into the candidate buffers — the same combination of the held images that forms x_d
+    // (k_dense_head, or k_affine_image and the value L(x_d)), or an evaluation — then trade: GX_ = grad L(x_d),
+    // GXN_ = grad L(x_prev)
+    void chain_images(Iter& it) {
+        it.state_imgs = gx_valid && gz_valid;      // (the images of this state's x and z are what GX_, GZ_, CXS_, CZS_ hold)
+        if (it.use_compact && gx_valid && gz_valid && aff_count_ + 1 < aff_refresh_) {
+            ++aff_count_; ++n_affine_; it.img_trial = true;
+            CompactVecs<T, CM> VA = image_vecs(true), VG = image_vecs(false);
+            if (it.head_on) {
+                DenseHeadArgs<T, CM> a;
+                std::memset(&a, 0, sizeof(a));
+                a.V = it.CV; a.VG = VG; a.VA = VA; a.C = it.CC;
+                a.res = RES_[it.rp].p; a.x = X_[it.xp].p; a.x_d = X_[it.xd].p;
+                a.gbase = GX_.p; a.gzimg = GZ_.p; a.gout = GXN_.p;
+                a.cbase = CXS_.p; a.czimg = CZS_.p; a.cout = CXD_.p; a.yupd = YU_.p;
+                a.z = Z_[it.zn].p; a.res_new = RES_[it.rn].p; a.gamma = gamma;
+                a.n = n; a.ny = ny; a.parts = parts_.p;
+                a.slot_f = SL_FXD; a.slot_pen = SL_PXD; a.slot_fb = SL_GSUM; a.gn = grid; a.gy = grid_y;
+                slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
+                for (int kk = 0; kk < 3; ++kk) slot_n[SL_GSUM + kk] = grid;
+                // (what the six kernels move: k_compact_xd, the two images, f, yupd, the FB step)
+                mv(2 * it.CV.m + 3); mv(2 * VA.m + 3, ny); mv(2 * VG.m + 3); mv(1 + pstreams(true, false, false));
+                mv(2 + pstreams(false, true, false), ny); mv(4 + pstreams(false, false, true));
+                nm("k_dense_head");
+                launch(C_MISC, k_dense_head<T, CM>, grid + grid_y, a, P);
+                it.head_fb = true;
+            } else {
+                mv(2 * VA.m + 3, ny); nm("k_affine_image");
+                launch(C_MISC, k_affine_image<T, CM>, grid_y, VA, it.CC, (const T*)CXS_.p, (const T*)CZS_.p, CXD_.p, ny);
+                mv(2 * VG.m + 3);
+                launch(C_MISC, k_affine_image<T, CM>, grid, VG, it.CC, (const T*)GX_.p, (const T*)GZ_.p, GXN_.p, n);
+                // the value L(x_d): f element-wise, the penalty from the image of c
+                slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
+                mv(1 + pstreams(true, false, false));
+                launch(C_MISC, k_fvalue_elem<T>, grid, (const T*)X_[it.xd].p, P, n, parts_.p, (int)SL_FXD, (const T*)nullptr);
+                mv(2 + pstreams(false, true, false), ny);
+                launch(C_MISC, k_yupd<T>, grid_y, (const T*)CXD_.p, P, YU_.p, ny, parts_.p, (int)SL_PXD);
+            }
+        } else {
+            aff_count_ = 0;
+            cx_keep_ = CXD_.p;
+            algrad(X_[it.xd].p, GXN_.p, SL_FXD);
+            cx_keep_ = nullptr;
+        }
+        std::swap(GX_.p, GXN_.p); std::swap(GX_.n, GXN_.n);
+        ++n_grad; gx_valid = true;
+    }
+
+    // a trial of the kernel chain from grad L at the trial point on: the FB step, grad L at z, then k_dense_tail, or
+    // k_update_c / k_update and the pair's images
+    void finish_chain_trial(Iter& it) {
+        const int zn = it.zn, rn = it.rn, xcur = it.xcur;
+        if (!gx_valid) { algrad(X_[xcur].p, GX_.p, SL_FXD); gx_valid = true; }
+        if (it.head_fb) it.head_fb = false;      // (k_dense_head made this step already)
+        else fbstep(X_[xcur].p, GX_.p, gamma, Z_[zn].p, RES_[rn].p, SL_GSUM);
+        gather(SL_GSUM, 3, 0u);
+        ++n_prox;
+        T* const gz_dst = aff_track_ ? GZN_.p : GZ_.p;      // (affine images: grad L(z_prev) is still needed)
+        if (aff_track_) cx_keep_ = CZN_.p;
+        // cfg 4: the fold of the row-group partials, the pair with its products and the pair's images in ONE launch
+        // behind the pass over A (k_dense_tail)
+        const bool tail_on = env_.densesmall && aff_track_ && compact_ok && !generic_ && !ctx->multi() &&
+                             desc.c_kind == BZ_C_DENSE_AFFINE && dense_fused_on();
+        if (tail_on) {
+            slot_n[SL_FZ] = grid;
+            dense_fused_launch(Z_[zn].p, SL_FZ + 1);
+            ++n_grad; gz_valid = true;
+            cx_keep_ = nullptr;
+            const CompactVecs<T, CM> VG = compact_vecs();
+            DenseTailArgs<T, CM> a;
+            std::memset(&a, 0, sizeof(a));
+            a.V = VG; a.part = GT_.p; a.nchunks = df_groups_; a.pstride = npad;
+            a.z = Z_[zn].p; a.gz = gz_dst;
+            a.x = X_[xcur].p; a.x_prev = X_[it.xp].p; a.res = RES_[rn].p; a.res_prev = RES_[it.rp].p; a.gx = GX_.p;
+            a.gamma = gamma; a.s_new = S_[spare].p; a.y_new = Y_[spare].p;
+            a.gx_prev = GXN_.p; a.gz_prev = GZ_.p; a.gs_img = GS_[spare].p; a.gy_img = GY_[spare].p;
+            a.cx = CXD_.p; a.cx_prev = CXS_.p; a.cz = CZN_.p; a.cz_prev = CZS_.p;
+            a.cs_img = AS_[spare].p; a.cy_img = AY_[spare].p;
+            a.n = n; a.ny = ny; a.parts = parts_.p; a.slot_fz = SL_FZ; a.slot_upd = SL_YS; a.gn = grid; a.gy = grid_y;
+            for (int kk = 0; kk < 3 + 4 * CM + 2; ++kk) slot_n[SL_YS + kk] = grid;
+            // (what the four kernels move: the fold + f terms, k_update_c, the two image pairs)
+            mv(df_groups_ + 2 + pstreams(true, false, false)); mv(8 + 2 * VG.m); mv(6, ny); mv(6);
+            nm("k_dense_tail");
+            launch(C_UPDATE, k_dense_tail<T, CM>, grid + grid_y, a, P);
+            gather(SL_FZ, 2, 0u, 2u);
+            gather(SL_YS, 3 + 4 * CM + 2, 4u);
+            it.gen_gram = true; it.m_gram = VG.m; it.tail_used = false;
+            return;
+        }
+        algrad(Z_[zn].p, gz_dst, SL_FZ); ++n_grad; gz_valid = true;
+        cx_keep_ = nullptr;
+        if (compact_ok) {
+            // the pair, the stop norm AND the compact form's products (Gram products of the candidate pair, the
+            // next application's p, w) in one pass and one read-back — against the memory as it is NOW
+            const CompactVecs<T, CM> VG = compact_vecs();
+            for (int kk = 0; kk < 3 + 4 * CM + 2; ++kk) slot_n[SL_YS + kk] = grid;
+            mv(8 + 2 * VG.m); nm("k_update_c");
+            launch(C_UPDATE, k_update_c<T, CM>, grid, VG, (const T*)X_[xcur].p, (const T*)X_[it.xp].p,
+                   (const T*)RES_[rn].p, (const T*)RES_[it.rp].p, (const T*)GX_.p, (const T*)gz_dst, gamma,
+                   S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL);
+            gather(SL_YS, 3 + 4 * CM + 2, 4u);
+            it.gen_gram = true; it.m_gram = VG.m; it.tail_used = false;
+        } else {
+            for (int kk = 0; kk < 3; ++kk) slot_n[SL_YS + kk] = grid;
+            mv(8);
+            launch(C_UPDATE, k_update<T>, grid, (const T*)X_[xcur].p, (const T*)X_[it.xp].p,
+                   (const T*)RES_[rn].p, (const T*)RES_[it.rp].p, (const T*)GX_.p, (const T*)gz_dst, gamma,
+                   S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_YS);
+            gather(SL_YS, 3, 4u);
+        }
+        if (aff_track_) {
+            // images of the candidate pair (s = x - x_prev, y = res - res_prev) under c and grad L
+            mv(6, ny);
+            launch(C_MISC, k_image_pair<T>, grid_y, (const T*)CXD_.p, (const T*)CXS_.p, (const T*)CZN_.p,
+                   (const T*)CZS_.p, AS_[spare].p, AY_[spare].p, ny);
+            mv(6);
+            launch(C_MISC, k_image_pair<T>, grid, (const T*)GX_.p, (const T*)GXN_.p, (const T*)GZN_.p,
+                   (const T*)GZ_.p, GS_[spare].p, GY_[spare].p, n);
+        }
+    }
+
+    // the step-size test on the trial's scalars: gamma halvings (a failing test on images is re-run on evaluations
+    // first), tau backtracks
+    void step_size_test(Iter& it) {
+        const T eps = std::numeric_limits<T>::epsilon();
+        const int max_bt = opt.max_backtracks;
+        T sigma = beta * (T(0.5) / gamma) * (T(1) - alpha);
+        const T tol0 = T(10) * eps * (T(1) + std::abs(it.FBE_x));
+        const T threshold = it.FBE_x - sigma * (it.nr0 * it.nr0) + tol0;
+        std::vector<double>& v = it.v;
+        for (int k = 1; k <= max_bt; ++k) {
+            if (!it.have_trial) finish_chain_trial(it);
+            if ((it.have_trial && it.gram_from_trial) || it.gen_gram) {
+                v = (it.have_trial && it.tail_used) ? wait_host(NFC, it.tail_ticket) : collect_range(SL_TRIAL, NFC, 1u << 9);
+                it.gram_from_trial = true; it.gen_gram = false;
                 for (int i = 0; i < CM; ++i) {
-                    gsy[i] = v[10 + i]; gyy[i] = v[10 + CM + i];
-                    tp[i] = v[10 + 2 * CM + i]; tw[i] = v[10 + 3 * CM + i];
+                    it.gsy[i] = v[10 + i]; it.gyy[i] = v[10 + CM + i];
+                    it.tp[i] = v[10 + 2 * CM + i]; it.tw[i] = v[10 + 3 * CM + i];
                 }
-                tpn = v[10 + 4 * CM]; twn = v[10 + 4 * CM + 1];
-            } else if (have_trial && sep_trial) {
+                it.tpn = v[10 + 4 * CM]; it.twn = v[10 + 4 * CM + 1];
+            } else if (it.have_trial && it.sep_trial) {
                 static_assert(SL_TRIAL == SL_FXD && SL_STOP == SL_TRIAL + 9 && SL_GU == SL_TRIAL + 10, "k_fused_sep's slots");
                 v = collect_range(SL_TRIAL, 12, 1u << 9);
-                sep_p = v[10]; sep_w = v[11];
-                gram_from_trial = false;
+                it.sep_p = v[10]; it.sep_w = v[11];
+                it.gram_from_trial = false;
             } else {
                 v = collect({SL_FXD, SL_PXD, SL_GSUM, SL_DOT, SL_SS, SL_FZ, SL_PZ, SL_YS, SL_YTY, SL_STOP},
                             1u << 9);
-                gram_from_trial = false;
+                it.gram_from_trial = false;
             }
-            have_trial = false;
+            it.have_trial = false;
             f_x = al_value(v[0], v[1]);
             g_z = g_value(v[2]); dot_gr = T(v[3]); ss_res = T(v[4]);
             const T f_z = al_value(v[5], v[6]);
@@ -3082,15 +3102,15 @@ template <class T> class Solver final : public SolverBase {
             const T f_z_upp = f_x - dot_gr + ((alpha / gamma) / T(2)) * (nr * nr);
             const T tol = T(10) * eps * (T(1) + std::abs(f_z));
             const bool halve = adaptive_ && std::isfinite((double)gamma) && f_z > f_z_upp + tol && gamma >= min_gamma;
-            if (halve && img_trial) {
+            if (halve && it.img_trial) {
                 // The step-size test compares f(z) with a model built on f(x) and grad L(x) to within 10 eps: an image
                 // (a linear combination, not an evaluation) is not consistent with f(z) to that level near convergence,
                 // and a value a few ulps low would halve gamma again and again at the same point.  A FAILING test is
                 // therefore never trusted on images: evaluate f and grad L at this x with the two passes over A and
                 // run the trial again (this does not consume one of the max_backtracks trials).
-                img_trial = false; aff_count_ = 0; ++n_affine_verify_;
+                it.img_trial = false; aff_count_ = 0; ++n_affine_verify_;
                 cx_keep_ = CXD_.p;
-                algrad(X_[xcur].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
+                algrad(X_[it.xcur].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
                 cx_keep_ = nullptr;
                 --k;
                 continue;
@@ -3102,92 +3122,73 @@ template <class T> class Solver final : public SolverBase {
             // that state) as vectors
             // a pass pre-launched for the next iteration assumed this trial is accepted and its pair inserted
             if (gate_pending_ && !(k == 1 && !halve && (FBE_new <= threshold || k >= max_bt) && T(v[7]) > T(0))) gate_abort();
-            if (halve) trial_ok = false;
-            if (sy_stale_ && !trial_ok && (halve || !(FBE_new <= threshold || k >= max_bt))) materialize_pairs();
+            if (halve) it.trial_ok = false;
+            if (sy_stale_ && !it.trial_ok && (halve || !(FBE_new <= threshold || k >= max_bt))) materialize_pairs();
             if ((!z_valid || !res_valid) && (halve || !(FBE_new <= threshold || k >= max_bt))) ensure_z();
             if (halve) {
-                halved_here = true;
+                it.halved_here = true;
                 gamma = gamma * T(0.5); ++n_halv;
                 if (gamma < min_gamma)
                     std::fprintf(stderr, "Warning: stepsize `gamma` became too small (%g)\n", (double)gamma);
                 sigma = sigma * T(2);   // (as upstream: sigma is updated, the threshold is kept)
                 lbfgs_reset();
-                fused_this = false; reset_this = true;
+                it.fused_this = false; it.reset_this = true;
                 continue;
             }
             if (FBE_new <= threshold || k >= max_bt) break;
             tau = (k >= max_bt - 1) ? T(0) : tau / T(2);
-            ++nbt; ++n_bt;
-            mv(3);
-            launch(C_MISC, k_blend<T>, grid, (const T*)X_[xd].p, (const T*)Z_[zp].p, tau, T(1) - tau,
-                   X_[xb].p, n);
-            xcur = xb;
-            fused_this = false;
-            if (trial_ok) {
-                // the blended point through the one-pass kernel: given in X_[xb], evaluated against the same ring
-                // of iterates; z and res of the new state are stored (Z_[zn], RES_[rn])
-                for (int kk = 0; kk < NFC; ++kk) slot_n[SL_TRIAL + kk] = trial_gfc;
-#define BZ_LAUNCH_FCT(NT_, UNI_, PP_, ...)                                                                        \
-    launch(C_FUSED_IT, k_fused_compact<T, CM, NT_, true, true, 2, UNI_, 1, FAM_HEADLINE, PP_, ##__VA_ARGS__>, trial_gfc, trial_XV, \
-           trial_CC, (const T*)X_[xp].p, (const T*)nullptr, P, gamma, X_[xb].p, Z_[zn].p, RES_[rn].p, (T*)nullptr,         \
-           (T*)nullptr, n, parts_.p, (int)SL_TRIAL)
-                // the iterates, the parameter vectors (mu, mu*y unless numbers), the trial point ; z, res
-                mv((m_at_trial + 1) + pstreams(true, true, true) + 1 + 2);
-                if (trial_table) {
-                    trial_CC.uni_rt = trial_uni; trial_CC.trial_rt = 1;
-                    FusedFn<T> fn = family_kernel<T>(trial_fam, trial_nt);
-                    form_[C_FUSED_IT] = "k_fused_compact<XR=2,UNI=-1,NT=" + std::to_string(trial_nt ? 1 : 0) + ",TRIAL=-1,FAM=" + std::to_string(trial_fam) + ">";
-                    launch(C_FUSED_IT, fn, trial_gfc, trial_XV, trial_CC, (const T*)X_[xp].p, (const T*)nullptr, P, gamma,
-                           X_[xb].p, Z_[zn].p, RES_[rn].p, (T*)nullptr, (T*)nullptr, n, parts_.p, (int)SL_TRIAL);
-                } else {
-                form_[C_FUSED_IT] = std::string("k_fused_compact<XR=2,UNI=") + char('0' + trial_uni) + (trial_nt ? ",NT=1" : ",NT=0") + ",TRIAL=1" +
-                                    (trial_keep ? ",PP=1" : "") + (trial_lq ? ",LQ=1>" : ">");
-                if (trial_lq) {      // (fp64 only: lds_ring)
-                    if constexpr (sizeof(T) == 8) {
-                        if (trial_keep) { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 1, 1); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 1, 1); else BZ_LAUNCH_FCT(true, 0, 1, 1); }
-                        else { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 0, 1); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 0, 1); else BZ_LAUNCH_FCT(true, 0, 0, 1); }
-                    }
-                }
-                else if (trial_nt && trial_keep) { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 1); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 1); else BZ_LAUNCH_FCT(true, 0, 1); }
-                else if (trial_nt) { if (trial_uni == 2) BZ_LAUNCH_FCT(true, 2, 0); else if (trial_uni == 1) BZ_LAUNCH_FCT(true, 1, 0); else BZ_LAUNCH_FCT(true, 0, 0); }
-                else { if (trial_uni == 2) BZ_LAUNCH_FCT(false, 2, 0); else if (trial_uni == 1) BZ_LAUNCH_FCT(false, 1, 0); else BZ_LAUNCH_FCT(false, 0, 0); }
-                }
-#undef BZ_LAUNCH_FCT
-                if (ctx->p2p_on) {
-                    tail_ticket = exchange_collect(SL_TRIAL, NFC, 1u << 9);
-                    tail_used = true;
-                } else {
-                    gather(SL_TRIAL, NFC, 1u << 9);
-                    tail_used = false;
-                }
-                have_trial = true; gram_from_trial = true; gx_valid = false; gz_valid = false;
-                n_grad += 2; n_prox += 1;
-            } else if (affblend_env_ && aff_track_ && state_imgs && gx_valid && nbt == 1 && !halved_here && compact_ok && !generic_ &&
-                       !ctx->multi() && aff_count_ + 1 < aff_refresh_) {
-                // cfg 4, first tau backtrack of an iteration: the blended point is an affine combination of x_d and the state's z,
-                // whose images under c and grad L are at hand — its images are the same combination (k_blend's operations), no
-                // pass over A.  (As for x_d: a failing step-size test on images is re-run on evaluations, img_trial.)  The rejected
-                // trial's z images (CZN_, GZN_) are dead: they take the results and trade places.
-                ++aff_count_; img_trial = true;      // (n_affine_images counts iterations whose trial point x + d went on images)
-                ++n_affine_blends_;
-                mv(3, ny);
-                launch(C_MISC, k_blend<T>, grid_y, (const T*)CXD_.p, (const T*)CZS_.p, tau, T(1) - tau, CZN_.p, ny);
-                std::swap(CXD_.p, CZN_.p); std::swap(CXD_.n, CZN_.n);
-                mv(3);
-                launch(C_MISC, k_blend<T>, grid, (const T*)GX_.p, (const T*)GZ_.p, tau, T(1) - tau, GZN_.p, n);
-                std::swap(GX_.p, GZN_.p); std::swap(GX_.n, GZN_.n);
-                slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
-                mv(1 + pstreams(true, false, false));
-                launch(C_MISC, k_fvalue_elem<T>, grid, (const T*)X_[xb].p, P, n, parts_.p, (int)SL_FXD, (const T*)nullptr);
-                mv(2 + pstreams(false, true, false), ny);
-                launch(C_MISC, k_yupd<T>, grid_y, (const T*)CXD_.p, P, YU_.p, ny, parts_.p, (int)SL_PXD);
-                ++n_grad; gx_valid = true;
-            } else {
-                if (aff_track_) { cx_keep_ = CXD_.p; aff_count_ = 0; img_trial = false; }
-                algrad(X_[xb].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
-                cx_keep_ = nullptr;
-            }
+            ++it.nbt; ++n_bt;
+            retrial(it);
         }
+    }
+    // the tau-backtracked point x_d tau + z (1 - tau) into the blend buffer, and its trial: through the one-pass kernel
+    // (trial given), on the blended images (cfg 4), or with an evaluation of grad L
+    void retrial(Iter& it) {
+        const int xb = it.xb;
+        mv(3);
+        launch(C_MISC, k_blend<T>, grid, (const T*)X_[it.xd].p, (const T*)Z_[it.zp].p, tau, T(1) - tau, X_[xb].p, n);
+        it.xcur = xb;
+        it.fused_this = false;
+        if (it.trial_ok) {
+            // the blended point through the one-pass kernel: given in X_[xb], evaluated against the same ring
+            // of iterates; z and res of the new state are stored (Z_[zn], RES_[rn])
+            for (int kk = 0; kk < NFC; ++kk) slot_n[SL_TRIAL + kk] = it.trial_plan.gfc;
+            // the iterates, the parameter vectors (mu, mu*y unless numbers), the trial point ; z, res
+            mv(xr2_streams(it.m_at_trial) + 2);
+            launch_xr2(it.trial_plan, it.trial_coef, 1, X_[xb].p, Z_[it.zn].p, RES_[it.rn].p);
+            onepass_scalars(it, false);
+            it.have_trial = true; it.gram_from_trial = true; gx_valid = false; gz_valid = false;
+            n_grad += 2; n_prox += 1;
+        } else if (env_.affine_blend && aff_track_ && it.state_imgs && gx_valid && it.nbt == 1 && !it.halved_here && compact_ok &&
+                   !generic_ && !ctx->multi() && aff_count_ + 1 < aff_refresh_) {
+            // cfg 4, first tau backtrack of an iteration: the blended point is an affine combination of x_d and the state's z,
+            // whose images under c and grad L are at hand — its images are the same combination (k_blend's operations), no
+            // pass over A.  (As for x_d: a failing step-size test on images is re-run on evaluations, img_trial.)  The rejected
+            // trial's z images (CZN_, GZN_) are dead: they take the results and trade places.
+            ++aff_count_; it.img_trial = true;      // (n_affine_images counts iterations whose trial point x + d went on images)
+            ++n_affine_blends_;
+            mv(3, ny);
+            launch(C_MISC, k_blend<T>, grid_y, (const T*)CXD_.p, (const T*)CZS_.p, tau, T(1) - tau, CZN_.p, ny);
+            std::swap(CXD_.p, CZN_.p); std::swap(CXD_.n, CZN_.n);
+            mv(3);
+            launch(C_MISC, k_blend<T>, grid, (const T*)GX_.p, (const T*)GZ_.p, tau, T(1) - tau, GZN_.p, n);
+            std::swap(GX_.p, GZN_.p); std::swap(GX_.n, GZN_.n);
+            slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
+            mv(1 + pstreams(true, false, false));
+            launch(C_MISC, k_fvalue_elem<T>, grid, (const T*)X_[xb].p, P, n, parts_.p, (int)SL_FXD, (const T*)nullptr);
+            mv(2 + pstreams(false, true, false), ny);
+            launch(C_MISC, k_yupd<T>, grid_y, (const T*)CXD_.p, P, YU_.p, ny, parts_.p, (int)SL_PXD);
+            ++n_grad; gx_valid = true;
+        } else {
+            if (aff_track_) { cx_keep_ = CXD_.p; aff_count_ = 0; it.img_trial = false; }
+            algrad(X_[xb].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
+            cx_keep_ = nullptr;
+        }
+    }
+
+    // the accepted trial becomes the state: image trade, pair insertion (or k_gram_pair), the x_b swap, the ring counters
+    // and the validity flags
+    void commit(Iter& it) {
         if (aff_track_) {
             // the accepted state's images become the current ones
             std::swap(GZ_.p, GZN_.p); std::swap(GZ_.n, GZN_.n);
@@ -3195,24 +3196,24 @@ template <class T> class Solver final : public SolverBase {
             std::swap(CXS_.p, CXD_.p); std::swap(CXS_.n, CXD_.n);
         }
         // update!(H, x - x_prev, res - res_prev): the pair sits in the spare slot
-        const T ys = T(v[7]), yty = T(v[8]);
+        const T ys = T(it.v[7]), yty = T(it.v[8]);
         last_ys = ys;
         // p, w for the next application: valid iff the accepted point is the one the fused trial measured
         // and the memory was not reset meanwhile (gram_insert shifts them along with the Gram matrices)
-        pw_valid = compact_ok && gram_from_trial && (int)order.size() == m_gram;
+        pw_valid = compact_ok && it.gram_from_trial && (int)order.size() == it.m_gram;
         if (pw_valid) {
-            for (int i = 0; i < CM; ++i) { hp_[i] = i < m_gram ? tp[i] : 0.0; hw_[i] = i < m_gram ? tw[i] : 0.0; }
-            p_new_ = tpn; w_new_ = twn;
-        } else if (compact_ok && sep_trial && fused_this && m_at_trial == 0 && order.empty()) {
+            for (int i = 0; i < CM; ++i) { hp_[i] = i < it.m_gram ? it.tp[i] : 0.0; hw_[i] = i < it.m_gram ? it.tw[i] : 0.0; }
+            p_new_ = it.tpn; w_new_ = it.twn;
+        } else if (compact_ok && it.sep_trial && it.fused_this && it.m_at_trial == 0 && order.empty()) {
             // first iteration of a solve (empty memory): the k_fused_sep pass measured the new pair's p and w
             pw_valid = true;
             for (int i = 0; i < CM; ++i) { hp_[i] = 0.0; hw_[i] = 0.0; }
-            p_new_ = sep_p; w_new_ = sep_w;
+            p_new_ = it.sep_p; w_new_ = it.sep_w;
         }
         if (dir_kind_ == BZ_DIR_BROYDEN) {
             broyden_update();                    // (no curvature test: every pair updates the operator)
         } else if (ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON) {
-            if (compact_ok && !gram_from_trial && !order.empty()) {
+            if (compact_ok && !it.gram_from_trial && !order.empty()) {
                 // the accepted pair is not the one the fused trial measured: its Gram products with the
                 // stored pairs come from their own pass
                 for (int k = 0; k < 2 * CM; ++k) slot_n[SL_GU + k] = grid;
@@ -3220,11 +3221,10 @@ template <class T> class Solver final : public SolverBase {
                 launch(C_DOT, k_gram_pair<T, CM>, grid, compact_vecs(), (const T*)Y_[spare].p, n, parts_.p,
                        (int)SL_GU);
                 gather(SL_GU, 2 * CM, 0u);
-                auto gv = collect({SL_GU + 0, SL_GU + 1, SL_GU + 2, SL_GU + 3, SL_GU + 4, SL_GU + 5, SL_GU + 6,
-                                   SL_GU + 7, SL_GU + 8, SL_GU + 9}, 0u);
-                for (int i = 0; i < CM; ++i) { gsy[i] = gv[i]; gyy[i] = gv[CM + i]; }
+                auto gv = collect_range(SL_GU, 2 * CM, 0u);
+                for (int i = 0; i < CM; ++i) { it.gsy[i] = gv[i]; it.gyy[i] = gv[CM + i]; }
             }
-            lbfgs_insert(ys, yty, gsy, gyy);
+            lbfgs_insert(ys, yty, it.gsy, it.gyy);
         } else {
             ++n_skips;
             materialize_pairs();         // (history as iterates: the window stops being contiguous here)
@@ -3232,27 +3232,26 @@ template <class T> class Solver final : public SolverBase {
         // A tau-backtracked point sits in the blend buffer: trade the two buffers so that the accepted iterate is
         // the next one of the ring whatever produced it — the stored pairs stay the successive differences of
         // the ring's last iterates (and residuals), and the run below goes on through backtracks
-        if (xcur == xb && fused_ok && compact_ok) {
-            std::swap(X_[xd].p, X_[xb].p);
-            std::swap(X_[xd].n, X_[xb].n);
-            xcur = xd;
+        if (it.xcur == it.xb && fused_ok && compact_ok) {
+            std::swap(X_[it.xd].p, X_[it.xb].p);
+            std::swap(X_[it.xd].n, X_[it.xb].n);
+            it.xcur = it.xd;
         }
         // history as iterates is possible after CM iterations in a row that each inserted their pair, with no
         // change of gamma (which resets the memory) in between
         // (xr_run_: how many of the newest stored pairs are differences of ring neighbours.  The pair of an
         // iteration that halved gamma is one too — y = res_new(gamma/2) - res_prev(gamma), as upstream has it —
         // because every iterate in the ring remembers the gamma of its residual, gring_)
-        xr_run_ = (fused_ok && compact_ok && (ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON) && xcur == xd) ? (reset_this ? 1 : xr_run_ + 1) : 0;
-        gring_[xcur] = (double)gamma;
+        xr_run_ = (fused_ok && compact_ok && (ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON) && it.xcur == it.xd) ? (it.reset_this ? 1 : xr_run_ + 1) : 0;
+        gring_[it.xcur] = (double)gamma;
         if (xr_run_ == 0) rh_stale_ = false;       // (whatever broke the run has materialised the pairs above)
-        stop_norm_ = v[9];
-        xc = xcur; rc = rn; zc = zn;
-        z_valid = !(z_skipped && fused_this);      // the generic trial writes z; an accepted fused one may not have
-        res_valid = !(res_skipped && fused_this);  // ... nor res
-        last_nbt = nbt; last_fused = fused_this;
-        if (fused_this) ++n_fused;
+        stop_norm_ = it.v[9];
+        xc = it.xcur; rc = it.rn; zc = it.zn;
+        z_valid = !(it.z_skipped && it.fused_this);      // the generic trial writes z; an accepted fused one may not have
+        res_valid = !(it.res_skipped && it.fused_this);  // ... nor res
+        last_nbt = it.nbt; last_fused = it.fused_this;
+        if (it.fused_this) ++n_fused;
     }
-
    private:
     void fill_stats(bz_panoc_stats* st) {
         std::memset(st, 0, sizeof(*st));

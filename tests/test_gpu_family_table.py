@@ -160,7 +160,7 @@ FEW_ONE_PASS = {("zero", "l1box", D) for D in FAM_D}
 
 # The headline family's plain passes take the specialised headline kernel (test_gpu_lds_ring, test_gpu_param_residency);
 # its table entry is reached through BZ_FAMRT=1, in the run-time UNI / TRIAL instantiation.  (Its compile-time UNI
-# entries serve BZ_SPEC=0 only, a knob read once per process.)
+# entries serve BZ_SPEC=0 only.)
 HEADLINE = ("diag", "l1", "box")
 
 
