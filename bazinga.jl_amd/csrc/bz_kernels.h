@@ -64,7 +64,7 @@ template <class T> struct ElemParams {
     T D_lo, D_hi;
     const T* D_lo_vec;
     const T* D_hi_vec;
-    T mu_uniform;          // the value of every mu[i] when the penalties are uniform (k_uniform_probe), else unused
+    T mu_uniform;          // the value of every mu[i] when the penalties are uniform (k_muy's probe), else unused
 };
 
 // ---------------------------------------------------------------------------
@@ -439,7 +439,7 @@ __device__ __forceinline__ float clamp_mm(float v, float lo, float hi) { return 
 // the hardware division sequence (v_div_scale/rcp/5 fma/v_div_fmas/v_div_fixup) in half the instructions.
 // Holds for finite a and quotients in the normal range, which is where the solver works (an infinite a gives
 // NaN instead of inf: either way the iterate is lost).  The forms with and without it are compared bit for
-// bit in test_history_as_iterates_and_lazy_z_are_bitwise_neutral.
+// bit in test_iterate_history_and_lazy_z_are_bitwise_neutral.
 __device__ __forceinline__ double div_u(double a, double b, double rb) {
     double q = a * rb;
     double e = __builtin_fma(-b, q, a);
@@ -936,7 +936,7 @@ k_stencil_fb(const T* __restrict__ x, ElemParams<T> P, int64_t nx, int64_t ny, T
                 accG[2] += (double)(r * r);
             }
         }
-        if (grad) st(grad, i0, cnt, pg);      // (null: the pass that follows re-forms it, k_stencil_update_c<REGX>)
+        st(grad, i0, cnt, pg);
         st(z, i0, cnt, pz);
         st(res, i0, cnt, pr);
     });
@@ -2465,9 +2465,7 @@ template <int MM> struct CompactCoef {
     const GateRec* gate_host;  // pinned host memory (device address)
     GateRec* gate_dev;
     int* gate_timeout;
-    int gate_other_stream;     // launched on another stream than the pass before it (may be resident while that one runs)
     unsigned gate_spin_host, gate_spin_dev;      // poll bounds of workgroup 0 (host record) and of the others (device flag)
-    int gate_late;             // the pipelined form goes to its gate AFTER issuing the loads of its first packs
 };
 
 // K1: p_i = <s_i, -res>, w_i = <y_i, -res>   slots: slot0 + i (p), slot0 + MM + i (w)
@@ -2889,32 +2887,14 @@ k_dense_tail(DenseTailArgs<T, MM> A, ElemParams<T> P) {
     }
 }
 
-// history as iterates -> history as pairs: S[i] = XH[i+1] - XH[i], Y[i] = RH[i+1] - RH[i] for the MM stored pairs
-// (run when an iteration leaves the plain path and the classic kernels need the difference vectors)
+// history as iterates -> history as pairs (run when an iteration leaves the plain path and the classic kernels need the
+// difference vectors): the iterates XH, the pair vectors S, Y to fill
 template <class T, int MM> struct SnapVecs {
     const T* XH[MM + 1];
-    const T* RH[MM + 1];
     T* S[MM];
     T* Y[MM];
-    double gam[MM + 1];      // k_pairs_from_iterates: gamma of each iterate's residual (the last one: the current gamma)
+    double gam[MM + 1];      // gamma of each iterate's residual (the last one: the current gamma)
 };
-template <class T, int MM>
-__global__ void __launch_bounds__(BLOCK) k_pairs_from_snapshots(SnapVecs<T, MM> V, int64_t n) {
-    bz_for_chunks<T>(n, [&](const int64_t i0, const auto cnt_) {
-        const int cnt = cnt_;
-        Pack<T> xh[MM + 1], rh[MM + 1];
-#pragma unroll
-        for (int i = 0; i <= MM; ++i) { xh[i] = ld(V.XH[i], i0, cnt); rh[i] = ld(V.RH[i], i0, cnt); }
-#pragma unroll
-        for (int i = 0; i < MM; ++i) {
-            Pack<T> s, y;
-#pragma unroll
-            for (int e = 0; e < PackN<T>::N; ++e) { s.v[e] = xh[i + 1].v[e] - xh[i].v[e]; y.v[e] = rh[i + 1].v[e] - rh[i].v[e]; }
-            st(V.S[i], i0, cnt, s);
-            st(V.Y[i], i0, cnt, y);
-        }
-    });
-}
 
 // fixed-point residual of one element at a stored iterate:  z = prox_{gamma g}(x - gamma grad L(x)), res = x - z —
 // operation for operation what the fused passes (and k_algrad_elem + k_fbstep) do at a trial point, so
@@ -3033,19 +3013,17 @@ k_update_c(CompactVecs<T, MM> V, const T* __restrict__ x, const T* __restrict__ 
 //   then <s_new, -res>, <y_new, -res>
 // (slots slot0 + 0..4 are k_stencil_fb's).  With it the iteration has ONE reduction phase and no persistent
 // two-loop kernel with its 2m-1 grid barriers: x_d (k_compact_xd), k_stencil_fb, this.
-// REGX (r03): grad L(x_d) and res are not read but re-formed here — res = x_d - z from the two packs this pass loads anyway, and
-// grad L(x_d) by the stencil on x_d (its north / south / west / east re-reads are cache hits: the pass streams x_d already) —
-// the operations of k_stencil_fb on the same operands, so the same bits, for two read streams less here and one write stream
-// less there (k_stencil_fb with grad = null): 39 -> 36 passes over n per iteration.  halo_x: x_d's halo rows (sharded grid).
-// (measured on cfg 3: REGX = 2, both re-formed: 126 us against 117 us for this pass — the second stencil costs more than the two
-// streams it saves ; REGX = 1, res only — a subtraction of two packs the pass holds anyway: the default)
+// REGX = 1 (r03): res is not read but re-formed here — res = x_d - z from the two packs this pass loads anyway, the operation
+// of k_stencil_fb on the same operands, so the same bits, for one read stream less.  (Measured on cfg 3, and retired since:
+// grad L(x_d) re-formed too, by a second stencil on x_d — 126 us against 117 us for this pass, the second stencil costs more
+// than the streams it saves.)
 template <class T, int MM, bool FULL = false, bool NT = false, int REGX = 0>
 __global__ void __launch_bounds__(BLOCK)
 k_stencil_update_c(CompactVecs<T, MM> V, const T* __restrict__ zp, ElemParams<T> P, int64_t nx, int64_t ny,
                    const T* __restrict__ x, const T* __restrict__ x_prev, const T* __restrict__ res,
                    const T* __restrict__ res_prev, const T* __restrict__ gx, T gamma,
                    T* __restrict__ s_new, T* __restrict__ y_new, int64_t n,
-                   double* __restrict__ parts, int slot0, StencilHalo<T> halo, StencilHalo<T> halo_x = StencilHalo<T>()) {
+                   double* __restrict__ parts, int slot0, StencilHalo<T> halo) {
     constexpr int NS = 5 + 4 * MM + 2;
     double accF[2] = {0.0, 0.0}, acc[NS];
 #pragma unroll
@@ -3063,12 +3041,7 @@ k_stencil_update_c(CompactVecs<T, MM> V, const T* __restrict__ zp, ElemParams<T>
         } else {
             pr = ld(res, i0, cnt);
         }
-        if constexpr (REGX >= 2) {
-            double dump0 = 0.0, dump1 = 0.0;      // (the value terms at x_d were summed by k_stencil_fb)
-            pgx = stencil_al_pack<T, NT>(x, P, nx, ny, 0, i0, cnt, px, dump0, dump1, halo_x);
-        } else {
-            pgx = ld(gx, i0, cnt);
-        }
+        pgx = ld(gx, i0, cnt);
 #pragma unroll
         for (int i = 0; i < MM; ++i)
             if (i < m) { hs[i] = ldp<T, NT>(V.S[i], i0, cnt); hy[i] = ldp<T, NT>(V.Y[i], i0, cnt); }
@@ -3112,9 +3085,8 @@ k_stencil_update_c(CompactVecs<T, MM> V, const T* __restrict__ zp, ElemParams<T>
 //           + 10 + 2MM + i: <s_i, -res> ; + 10 + 3MM + i: <y_i, -res> ; then <s_new, -res>, <y_new, -res>
 //           with res the NEW residual: the p and w of the next application, whichever pairs it keeps —
 //           so the whole iteration is this one pass (S and Y are in registers here anyway)
-//   XR = 1: V.S / V.Y are the last MM iterates / residuals before (x, res_prev) and the pairs are re-formed
-//           in registers (s_new, y_new not written)
-//   XR = 2: as 1, and the residuals are not read either but re-evaluated from the iterates (resid_elem):
+//   XR = 2: V.S are the last MM iterates before x and the pairs are re-formed in registers (s_new, y_new not
+//           written); the residuals are not read either but re-evaluated from the iterates (resid_elem):
 //           reads the MM+1 iterates, q, b, mu, mu*y ; writes x_d only (res too if `res` is not null)
 //   UNI = 1: every mu[i] is the same number (P.mu_uniform; alps.jl:42 from a start with c(x0) in D, and
 //            alps.jl:97 scales all of them alike) -> not streamed ; UNI = 2: and mu*y = 0 (first subproblem from
@@ -3207,8 +3179,7 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
                     for (;;) {
                         sq = __hip_atomic_load(&C.gate_dev->seq, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                         if ((sq & ~GATE_ABORT) == C.gate_seq) break;
-                        // (other stream: ~0.7 us between polls — 255 pollers must not load the fabric while a pass streams)
-                        if (C.gate_other_stream) __builtin_amdgcn_s_sleep(24); else __builtin_amdgcn_s_sleep(2);
+                        __builtin_amdgcn_s_sleep(2);
                         if (++spins > C.gate_spin_dev) { sq = C.gate_seq | GATE_ABORT; *C.gate_timeout = 7; break; }
                     }
                 }
@@ -3216,9 +3187,6 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
             }
             __syncthreads();
             if (gate_sh & GATE_ABORT) return false;
-            // this kernel may have been resident while the previous pass (another stream) was still writing what it
-            // is about to read: every wave takes an agent-scope acquire before its first load
-            if (C.gate_other_stream) __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
 #pragma unroll
             for (int i = 0; i < MM; ++i) {
                 u1[i] = (T)__hip_atomic_load(&C.gate_dev->val[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -3230,12 +3198,10 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
         }
         return true;
     };
-    // the pipelined form issues the loads of its first packs BEFORE it goes to the gate (they do not depend on the
-    // coefficients): the gate wait hides their latency.  Not when the launch may be resident while the previous pass
-    // still writes (other stream): its first load must come after the acquire.
-    constexpr bool PIPE_ = SPEC && OFF32 && XR == 2;
-    const bool gate_late = PIPE_ && !C.gate_other_stream && C.gate_late;
-    if (!gate_late) { if (!gate_wait()) return; }
+    // (the gate belongs to the pipelined form, which issues the loads of its first packs BEFORE it goes to the gate — they
+    // do not depend on the coefficients: the gate wait hides their latency)
+    static_assert(XR == 0 || XR == 2, "XR: stored pairs (0) or iterates with re-evaluated residuals (2)");
+    static_assert(XR != 2 || (SPEC && OFF32), "the iterate-history form is pipelined");
     if (SPEC && !OFF32) {      // keep the per-application coefficients in vector registers: scalar ones are the scarce kind here
 #pragma unroll
         for (int i = 0; i < MM; ++i) { asm volatile("" : "+v"(u1[i])); asm volatile("" : "+v"(u2h[i])); }
@@ -3348,9 +3314,12 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
                 }
         }
         if constexpr (XR == 2) {
-            // ... and the residuals re-evaluated at those iterates instead of read: the same operations on the
-            // same inputs as when they were first computed (gamma, mu, mu*y have not changed since: any
-            // iteration that changes them leaves this mode), so again the same bits
+            // history kept as ITERATES: V.S[i] is the snapshot x_{k-MM+i} (x the newest), and the pairs are their
+            // successive differences — the very subtractions that produced the stored s and y (s = x_d - x,
+            // y = res - res_prev), so the same bits, for two write streams less.  The residuals are re-evaluated at
+            // those iterates instead of read: the same operations on the same inputs as when they were first computed
+            // (gamma, mu, mu*y have not changed since: any iteration that changes them leaves this mode), so again
+            // the same bits
             Pack<T> rr[MM + 1];
 #pragma unroll
             for (int e = 0; e < N; ++e) {
@@ -3372,19 +3341,6 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
                     const T nx = (i + 1 < MM) ? ps[i + 1].v[e] : px.v[e];
                     ps[i].v[e] = nx - ps[i].v[e];
                     py[i].v[e] = rr[i + 1].v[e] - rr[i].v[e];
-                }
-        } else if constexpr (XR == 1) {
-            // history kept as ITERATES: V.S[i], V.Y[i] are the snapshots x_{k-MM+i}, res_{k-MM+i} (x and res_prev the
-            // newest), and the pairs are their successive differences — the very subtractions that produced the
-            // stored s and y (s = x_d - x, y = res - res_prev), so the same bits, for two write streams less
-#pragma unroll
-            for (int i = 0; i < MM; ++i)
-#pragma unroll
-                for (int e = 0; e < N; ++e) {
-                    const T nx = (i + 1 < MM) ? ps[i + 1].v[e] : px.v[e];
-                    const T nr = (i + 1 < MM) ? py[i + 1].v[e] : prp.v[e];
-                    ps[i].v[e] = nx - ps[i].v[e];
-                    py[i].v[e] = nr - py[i].v[e];
                 }
         }
         if (!trial) compact_d<T, MM>(m, H0, u1, u2h, prp, ps, py, d);
@@ -3527,9 +3483,7 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
 #pragma unroll
                 for (int r = 0; r < LQ_R - 1; ++r) lq_fetch(r * SLOTB, c + r * stride);
             }
-            if (gate_late) {
-                if (!gate_wait()) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
-            }
+            if (!gate_wait()) { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); return; }
             // sc: the slot of chunk c (already in registers), sn: the slot chunk c + (LQ_R - 1) stride is loaded into
             unsigned sc = 0, sn = (LQ_R - 1) * SLOTB;
             if (c < nfull) { lq_wait(); lq_read(sa, sc); }
@@ -3553,7 +3507,7 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
             // (three stages used in rotation, the loop unrolled by three: no register copies between iterations)
             Stage sc;
             if (c < nfull) { fetch(sa, c); fetch(sb, c + stride); }
-            if (gate_late) { if (!gate_wait()) return; }
+            if (!gate_wait()) return;
             for (;;) {
                 if (c >= nfull) break;
                 fetch(sc, c + 2 * stride); use(sa, c); c += stride;
@@ -3564,7 +3518,7 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
             }
         } else {
             if (c < nfull) fetch(sa, c);
-            if (gate_late) { if (!gate_wait()) return; }
+            if (!gate_wait()) return;
             for (;;) {
                 if (c >= nfull) break;
                 fetch(sb, c + stride); use(sa, c); c += stride;
@@ -3766,6 +3720,7 @@ __device__ __forceinline__ void slack_resid(const ElemParams<T>& P, T x, T sv, c
 // KIND = 1 (fast only): g = NormL1 and D = Box as compile-time facts too (the ALS form of cfg 2: with run-time kinds the
 // seven evaluations of prox_g / proj_D per index are ladders of wave-uniform branches, a third of the pass's instructions).
 // DEPTH: packs of loads kept in flight ahead of the one being consumed (0: none, the loads of a pack issue at its start).
+// KIND = 1 runs with DEPTH = 1 (cfg 2's ALS form: 227 us per pass, 232 without the pipeline).
 template <class T, int MM, bool NT, bool FULL = false, int UNI = -1, int KIND = 0, int DEPTH = 0>
 __global__ void __launch_bounds__(BLOCK)
 k_fused_slack_xr(SlackIterates<T, MM> V, CompactCoef<MM> C, ElemParams<T> P, const T* __restrict__ yv, T gamma,
@@ -3957,25 +3912,13 @@ k_fused_slack_xr(SlackIterates<T, MM> V, CompactCoef<MM> C, ElemParams<T> P, con
         auto fetch = [&](Stage& S, int64_t k) { load_stage(S, (unsigned)((k < nfull ? k : nfull - 1) * N * (int64_t)sizeof(T))); };
         auto use = [&](const Stage& S, int64_t k) { body(k * N, std::integral_constant<int, N>{}, std::true_type{}, S); };
         Stage sa, sb;
-        if constexpr (DEPTH == 2) {
-            Stage sc;
-            if (c < nfull) { fetch(sa, c); fetch(sb, c + stride); }
-            for (;;) {      // three stages in rotation, the loop unrolled by three: no register copies between iterations
-                if (c >= nfull) break;
-                fetch(sc, c + 2 * stride); use(sa, c); c += stride;
-                if (c >= nfull) break;
-                fetch(sa, c + 2 * stride); use(sb, c); c += stride;
-                if (c >= nfull) break;
-                fetch(sb, c + 2 * stride); use(sc, c); c += stride;
-            }
-        } else {
-            if (c < nfull) fetch(sa, c);
-            for (;;) {
-                if (c >= nfull) break;
-                fetch(sb, c + stride); use(sa, c); c += stride;
-                if (c >= nfull) break;
-                fetch(sa, c + stride); use(sb, c); c += stride;
-            }
+        static_assert(DEPTH == 1, "one pack of loads ahead");
+        if (c < nfull) fetch(sa, c);
+        for (;;) {
+            if (c >= nfull) break;
+            fetch(sb, c + stride); use(sa, c); c += stride;
+            if (c >= nfull) break;
+            fetch(sa, c + stride); use(sb, c); c += stride;
         }
         if (c == nfull && nfull * N < nx) body(c * N, (int)(nx - nfull * N), std::false_type{}, sa);
     } else {
@@ -4094,7 +4037,8 @@ k_diff_ss2(const T* __restrict__ a, const T* __restrict__ b, const T* __restrict
 // ---------------------------------------------------------------------------
 // AugLagUpdate!: muy = mu.*y ; slots +0 sum muy*y, +1 max(mu<=0)
 //   do_clamp: first y = clamp(y, -1e20, 1e20), stored back (default_dual_safeguard!, alps.jl:62 — k_clamp_scale's
-//             arithmetic) ; slot_probe >= 0: also k_uniform_probe's three maxima (mu and mu*y are in registers here)
+//             arithmetic) ; slot_probe >= 0: also three maxima (mu and mu*y are in registers here):
+//             +0 max mu, +1 max (mu[i] != mu[0]), +2 max |mu*y| — are the penalties uniform, are the scaled multipliers zero?
 template <class T>
 __global__ void __launch_bounds__(BLOCK)
 k_muy(const T* __restrict__ mu, T* __restrict__ y, T* __restrict__ muy, int64_t n,
@@ -4127,28 +4071,6 @@ k_muy(const T* __restrict__ mu, T* __restrict__ y, T* __restrict__ muy, int64_t 
     });
     block_reduce_store<2>(acc, 2u, parts, slot0);
     if (slot_probe >= 0) block_reduce_store<3>(pr, 7u, parts, slot_probe);
-}
-
-// are the penalties uniform, are the scaled multipliers zero?  slots (all max, all >= 0 as the folds assume):
-//   +0 max mu, +1 max (mu[i] != mu[0]), +2 max |mu*y|
-template <class T>
-__global__ void __launch_bounds__(BLOCK)
-k_uniform_probe(const T* __restrict__ mu, const T* __restrict__ muy, int64_t n, double* __restrict__ parts,
-                int slot0) {
-    double acc[3] = {0.0, 0.0, 0.0};
-    const T m0 = mu[0];
-    bz_for_chunks<T>(n, [&](const int64_t i0, const auto cnt_) {
-        const int cnt = cnt_;
-        Pack<T> pm = ld(mu, i0, cnt), py = ld(muy, i0, cnt);
-#pragma unroll
-        for (int e = 0; e < PackN<T>::N; ++e)
-            if (e < cnt) {
-                acc[0] = nanmax(acc[0], (double)pm.v[e]);
-                acc[1] = nanmax(acc[1], pm.v[e] == m0 ? 0.0 : 1.0);
-                acc[2] = nanmax(acc[2], (double)(py.v[e] < T(0) ? -py.v[e] : py.v[e]));
-            }
-    });
-    block_reduce_store<3>(acc, 7u, parts, slot0);
 }
 
 // dual update with c = Identity (alps.jl:72-84):

@@ -139,30 +139,24 @@ struct CreateKnobs {
 };
 struct BeginKnobs {
     explicit BeginKnobs(int nranks) : gate(env_int("BZ_GATE", nranks > 1 ? 0 : 1)) {}
-    int gate;                                    // BZ_GATE: gated pre-launch off (0) / on the solver's stream (1) / a second one (2)
-    int xr = env_int("BZ_XR", 2);                // one-pass pass on the stored pairs (0) / history as iterates (1) / residuals re-evaluated (2)
+    int gate;                                    // BZ_GATE: gated pre-launch off (0) / on (non-zero)
+    int xr = env_int("BZ_XR", 2);                // one-pass pass on the stored pairs (0) / on the iterates, residuals re-evaluated (non-zero)
     int skipz = env_int("BZ_SKIPZ", 1);          // 0: the one-pass pass always stores z
     int gfc = env_int("BZ_GFC", 0);              // k_fused_compact on k workgroups per CU (0: the per-form default)
     int trialfuse = env_int("BZ_TRIALFUSE", 1);  // 0: a tau-backtracked point finishes in the generic kernels
     int fused_begin = env_int("BZ_FUSED_BEGIN", 1);      // 0: the start of a solve (and ensure_z) in the generic kernels
     int slackfast = env_int("BZ_SLACKFAST", 1);  // 0: the slack iterate-history pass always in its run-time-kinds instantiation
     int slackkind = env_int("BZ_SLACKKIND", 1);  // 0: ... its fast instantiations with run-time kinds of g and D
-    int slackdepth = env_int("BZ_SLACKDEPTH", 1);        // 0: ... without the one-pack-ahead register pipeline (232 against 227 us per pass)
     int suc_grid = env_int("BZ_SUC_GRID", 1);    // k_stencil_update_c on k workgroups per CU (0: the problem's grid)
-    int stencil_regx = env_int("BZ_STENCIL_REGX", 1);    // cfg 3's second pass reads res and grad L(x_d) (0) / re-forms res (1) / both (2)
+    int stencil_regx = env_int("BZ_STENCIL_REGX", 1);    // cfg 3's second pass reads res (0) / re-forms it (1)
     int affine_blend = env_int("BZ_AFFINE_BLEND", 1);    // 0: a tau-backtracked point of cfg 4 always evaluated with a pass over A
     int densesmall = env_int("BZ_DENSESMALL", 1);        // 0: cfg 4's short kernels around the pass over A as launches of their own
     int nt = env_int("BZ_NT", -1);               // non-temporal streams by working-set size (-1) / forced off (0) or on (1)
     int keepp = env_int("BZ_KEEPP", -1);         // q and b of the headline pass cacheable by size (-1, keep_params) / forced
     int ldsq = env_int("BZ_LDSQ", -1);           // the non-temporal fp64 headline pass through its LDS ring (-1, 1) / not (0)
     int famrt = env_int("BZ_FAMRT", 0);          // 1: the headline family through its family-table instantiation
-    int famct = env_int("BZ_FAMCT", 1);          // 0: family kernels always in the run-time UNI / TRIAL instantiation
     int spec = env_int("BZ_SPEC", 1);            // 0: k_fused_compact always in its generic instantiation (run-time kinds)
-    int off32 = env_int("BZ_OFF32", 1);          // 0: k_fused_compact with 64-bit per-stream addresses
     int xdnt = env_int("BZ_XDNT", 1);            // 0: k_compact_xd, k_stencil_fb, k_stencil_update_c never non-temporal
-    int affine = env_int("BZ_AFFINE", -1);       // overrides bz_panoc_opts.affine_refresh (-1: no override)
-    int gatelate = env_int("BZ_GATELATE", 1);    // 0: the gated launch goes to its gate before issuing any load
-    int collect_wave = env_int("BZ_COLLECT_WAVE", 1);    // 0: read-back with one 256-thread workgroup per scalar, not one wave
     bool gemv_valu = std::getenv("BZ_GEMV_VALU") != nullptr;     // set: A'v (fp32) on the vector ALUs, not the MFMA form
     long long persist_min_n = env_ll("BZ_PERSIST_MIN_N", 300000);        // the length from which the persistent kernel runs
     // test-only
@@ -184,7 +178,6 @@ template <class T> class Solver final : public SolverBase {
    public:
     Solver(Ctx* c, const bz_problem_desc& d)
         : ctx(c), desc(d), n(d.n), ny(d.ny), nx(d.n), slack(d.slack != 0), env_(c->nranks) {
-        cur_ = ctx->stream;
         if (n <= 0 || ny < 0) throw Error(BZ_ERR_ARG, "n must be positive");
         if (d.c_kind == BZ_C_IDENTITY && ny != n)
             throw Error(BZ_ERR_ARG, "c = Identity requires ny == n");
@@ -383,7 +376,6 @@ template <class T> class Solver final : public SolverBase {
 
     ~Solver() override {
         gate_abort();
-        if (gate_stream_) { (void)hipStreamSynchronize(gate_stream_); (void)hipStreamDestroy(gate_stream_); }
         (void)hipStreamSynchronize(ctx->stream);
         if (gate_host_) (void)hipHostFree(gate_host_);
         for (auto& r : prof_recs) { (void)hipEventDestroy(r.a); (void)hipEventDestroy(r.b); }
@@ -750,9 +742,9 @@ template <class T> class Solver final : public SolverBase {
     int grid = 1, grid_y = 1;
     ElemParams<T> P;
     DBuf<T> q_, b_, gu_, glo_, ghi_, dlo_, dhi_, mu_, muy_, ymul_, sproj_;
-    // x and res live in rings long enough to keep the last CM+1 iterates alive (history as iterates, see
-    // xr_run_): CM+1 snapshots + the slot being written (+ one more x slot for the tau blend)
-    static constexpr int NXR = CM + 3, NRR = CM + 2;
+    // x lives in a ring long enough to keep the last CM+1 iterates alive (history as iterates, see xr_run_): CM+1
+    // snapshots + the slot being written (+ one more slot for the tau blend); res in two slots, the current and the next
+    static constexpr int NXR = CM + 3, NRR = 2;
     DBuf<T> X_[NXR], RES_[NRR], Z_[2], GX_, GZ_, D_, TMP_;
     DBuf<T> A_, cb_, CX_, YU_, GT_;          // DenseAffine c: A[ny][n], b, c(x), yupd, A'v row-chunk partials
     int rows_per_chunk = 1, nrowchunks = 1;
@@ -875,49 +867,39 @@ template <class T> class Solver final : public SolverBase {
     // the store is the dearest of the kernel's streams (-8 % of its time).  Who does need it — a tau backtrack
     // (z_curr), the caller asking for the solution — gets it re-materialised bit for bit from x and gamma.
     bool z_valid = true;
-    // History as iterates: once the last CM iterations were plain ones that each inserted their pair, the CM
-    // stored pairs are the successive differences of the last CM+1 iterates, which the long x / res rings
-    // still hold — the fused pass then reads those snapshots instead of S and Y (same number of streams,
-    // same bits: s = x_d - x, y = res - res_prev are re-formed by the very subtraction that made them) and
-    // stops WRITING s and y (two of its dearest streams).  The first iteration that is not a plain one
-    // turns the snapshots back into pairs (k_pairs_from_snapshots) and the classic kernels take over.
-    // One step further (headline family, after CM+1 such iterations): the residual of an iterate is a function
-    // of that iterate alone (res = x - prox(x - gamma grad L(x)), with gamma, mu, mu*y fixed along the run), so
-    // the fused pass re-evaluates the CM+1 residuals from the CM+1 iterates instead of reading them, and
-    // stops writing res as well: reads CM+1 iterates + q, b, mu, mu*y, writes x_d.  Same operations on the
-    // same inputs as when each residual was first computed -> the same bits.
+    // History as iterates: once the last iterations were plain ones that each inserted their pair, the stored
+    // pairs are the successive differences of the last iterates, which the long x ring still holds, and the
+    // residual of an iterate is a function of that iterate alone (res = x - prox(x - gamma grad L(x)), with
+    // gamma, mu, mu*y fixed along the run).  The fused pass then reads those iterates instead of S and Y,
+    // re-evaluates their residuals instead of reading them, and re-forms the pairs by the very subtractions
+    // that made them (s = x_d - x, y = res - res_prev): the same bits.  It stops WRITING s, y and res: reads
+    // the iterates + q, b, mu, mu*y, writes x_d.  The first iteration that is not a plain one turns the
+    // iterates back into pairs (k_pairs_from_iterates) and the classic kernels take over.
     int xr_run_ = 0;             // consecutive plain, pair-inserting iterations so far
-    bool sy_stale_ = false;      // S_/Y_ do not hold the stored pairs (they live in the rings)
-    bool rh_stale_ = false;      // ... and the residual ring was not written either during this run
+    bool sy_stale_ = false;      // S_/Y_ do not hold the stored pairs (they live in the x ring)
     double gring_[NXR] = {0};    // the gamma the residual of each iterate in the ring was (or would be) formed with
     bool res_valid = true;       // RES_[rc] holds the residual of the current state
     void materialize_pairs() {
         if (!sy_stale_) return;
         SnapVecs<T, CM> V;
         std::memset(&V, 0, sizeof(V));
-        const int m = (int)order.size();      // (< CM only in the re-evaluating form, soon after a memory reset)
+        const int m = (int)order.size();      // (< CM soon after a memory reset)
         for (int i = 0; i <= CM; ++i) {
             const int back = std::max(0, m - i);
             V.XH[i] = X_[(xc - back + NXR) % NXR].p;
-            V.RH[i] = RES_[(rc - back + NRR) % NRR].p;
             V.gam[i] = back ? gring_[(xc - back + NXR) % NXR] : (double)gamma;
         }
         for (int i = 0; i < m; ++i) { V.S[i] = S_[order[m - 1 - i]].p; V.Y[i] = Y_[order[m - 1 - i]].p; }
-        if (rh_stale_ && slack) {
+        if (slack) {
             // (the lifted vector: both halves of every iterate in, both halves of the pairs, the residual and z out)
             mv(2 * ((m + 1) + 2 * m + 2) + pstreams(true, true, true) + (P.uni >= 2 ? 0 : 1), nx);
             launch(C_MISC, k_pairs_from_iterates_slack<T, CM>, grid_y, V, m, P, (const T*)ymul_.p, RES_[rc].p, Z_[zc].p, nx);
-            res_valid = true; z_valid = true;
-        } else if (rh_stale_) {
+        } else {
             // (must run before gamma changes: the residuals are re-evaluated with the gamma of this run)
             mv((m + 1) + pstreams(true, true, true) + 2 * m + 2);
             launch(C_MISC, k_pairs_from_iterates<T, CM>, grid, V, m, P, RES_[rc].p, Z_[zc].p, n);
-            res_valid = true; z_valid = true;
-        } else {
-            if (m != CM) throw Error(BZ_ERR_STATE, "history as snapshots with a partial memory");
-            mv(2 * (CM + 1) + 2 * CM);
-            launch(C_MISC, k_pairs_from_snapshots<T, CM>, grid, V, n);
         }
+        res_valid = true; z_valid = true;
         sy_stale_ = false;
     }
     int xc = 0, rc = 0, zc = 0;
@@ -1054,11 +1036,6 @@ template <class T> class Solver final : public SolverBase {
     // The non-temporal headline pass (fp64) loads its packs ahead into a per-wave LDS ring instead of two register stages
     // (k_fused_compact<..., LQ = 1>): the LDS read one pack ahead of use, 246 VGPRs instead of 256 + 18 AGPRs.
     bool lds_ring(bool nt, bool table) const { return sizeof(T) == 8 && nt && !table && env_.ldsq != 0; }
-    // The early launch goes on the OTHER of two streams, so that it is dispatched (and, registers permitting, resident)
-    // while the current pass still runs instead of queueing behind the read-back kernel; when it is released the
-    // solver's launches move over to that stream (everything on the old one has completed by then: the host has the
-    // read-back's scalars in hand).  Between library calls the solver is always back on the context's stream.
-    hipStream_t cur_ = nullptr, gate_stream_ = nullptr, gate_on_ = nullptr;
     GateRec* gate_host_ = nullptr;           // pinned host memory
     GateRec* gate_host_dev_ = nullptr;       // ... its device address
     DBuf<GateRec> gate_dev_;
@@ -1077,15 +1054,9 @@ template <class T> class Solver final : public SolverBase {
         std::memset(gate_host_, 0, sizeof(GateRec));
         BZ_HIP(hipHostGetDevicePointer((void**)&gate_host_dev_, gate_host_, 0));
         gate_dev_.alloc(1);
-        BZ_HIP(hipStreamCreateWithFlags(&gate_stream_, hipStreamNonBlocking));
-    }
-    // back on the context's stream, nothing outstanding on the other one (end of every library-run loop)
-    void gate_quiesce() {
-        gate_abort();
-        if (cur_ != ctx->stream) { BZ_HIP(hipStreamSynchronize(cur_)); cur_ = ctx->stream; }
     }
     // (per-stream offsets of the one-pass kernels in 32 bits while every vector is shorter than 4 GB)
-    bool small_vectors() const { return env_.off32 && (double)vcap * sizeof(T) < 4.0e9; }
+    bool small_vectors() const { return (double)vcap * sizeof(T) < 4.0e9; }
     // streams of the iterate-history pass without z: the m_now + 1 distinct iterates (x among them), the family's parameter
     // vectors (mu / mu*y unless passed as numbers), x_d
     int xr2_streams(int m_now) const { return (m_now + 1) + pstreams(true, true, true) + 1; }
@@ -1095,7 +1066,7 @@ template <class T> class Solver final : public SolverBase {
     // released only if the two plans are equal.
     bool xr2_plan(int xc_, int m_now, const double* gring, int xr_run, bool zstore, GatePlan& pl) const {
         const int fam = fused_family();
-        if (!(env_.xr >= 2 && small_vectors() && fam >= 0 && xr_run >= m_now)) return false;
+        if (!(env_.xr && small_vectors() && fam >= 0 && xr_run >= m_now)) return false;
         // (only the oldest stored iterate may carry another gamma — see CompactCoef::gam0)
         for (int i = 1; i < m_now; ++i)
             if (gring[(xc_ - m_now + i + NXR) % NXR] != (double)gamma) return false;
@@ -1132,7 +1103,7 @@ template <class T> class Solver final : public SolverBase {
         if (pl.table) {
             C.uni_rt = pl.uni; C.trial_rt = trial;
             // the plain pass with uniform penalties has compile-time instantiations (fp64); run-time UNI / TRIAL otherwise
-            FusedFn<T> fn = (trial == 0 && env_.famct && !env_.famrt) ? family_kernel<T>(pl.fam, pl.nt, pl.uni) : nullptr;
+            FusedFn<T> fn = (trial == 0 && !env_.famrt) ? family_kernel<T>(pl.fam, pl.nt, pl.uni) : nullptr;
             const bool ct = fn != nullptr;
             if (!fn) fn = family_kernel<T>(pl.fam, pl.nt, -1);
             if (!fn) throw Error(BZ_ERR_STATE, "no one-pass kernel instantiation for this oracle family");
@@ -1169,29 +1140,18 @@ template <class T> class Solver final : public SolverBase {
         gate_alloc();
         CompactCoef<CM> C2;
         std::memset(&C2, 0, sizeof(C2));
-        C2.gate_late = env_.gatelate;
         // (BZ_GATE_SPIN: the poll bounds, for the test of the fall-back)
         C2.gate_spin_host = env_.gate_spin ? env_.gate_spin : GATE_SPIN_HOST;
         C2.gate_spin_dev = env_.gate_spin ? 8u * env_.gate_spin : GATE_SPIN_DEV;
         C2.gate_seq = ++gate_seq_; C2.gate_host = gate_host_dev_; C2.gate_dev = gate_dev_.p; C2.gate_timeout = ptimeout_dev_;
         mv(xr2_streams(pl.m_now));
         gate_bytes_ = pending_bytes_;
-        hipStream_t here = cur_;
-        gate_on_ = gate_env_ != 2 ? cur_ : ((cur_ == ctx->stream) ? gate_stream_ : ctx->stream);
-        C2.gate_other_stream = gate_on_ != cur_ ? 1 : 0;
-        cur_ = gate_on_;
-        try {
-            launch_xr2(pl, C2, 0, pl.xd, (T*)nullptr, (T*)nullptr);
-        } catch (...) {
-            cur_ = here;
-            throw;
-        }
-        cur_ = here;
+        launch_xr2(pl, C2, 0, pl.xd, (T*)nullptr, (T*)nullptr);
         gate_plan_ = pl; gate_pending_ = true;
     }
     void gate_release(const CompactCoef<CM>& C, T* zstore) {
         if (gate_sabotage_ > 0 && --gate_sabotage_ == 0) {      // (test) forget this release: the launch times out at its gate
-            cur_ = gate_on_; gate_pending_ = false; ++n_gated_;
+            gate_pending_ = false; ++n_gated_;
             return;
         }
         // 12 values (u1, u2h, H0, the z address) as tagged half-words: any order, each word validates itself
@@ -1209,7 +1169,6 @@ template <class T> class Solver final : public SolverBase {
             w[2 * i + 1] = tag | (bits >> 32);
         }
         std::atomic_thread_fence(std::memory_order_release);
-        cur_ = gate_on_;                         // the rest of this iteration queues behind the released pass
         gate_pending_ = false; ++n_gated_;
         if (zstore) bytes_all_[C_FUSED_IT] += (double)n * sizeof(T);
     }
@@ -1270,7 +1229,6 @@ template <class T> class Solver final : public SolverBase {
     void drain_prof() {
         if (prof_recs.empty()) return;
         BZ_HIP(hipStreamSynchronize(ctx->stream));
-        if (gate_stream_) BZ_HIP(hipStreamSynchronize(gate_stream_));
         for (auto& r : prof_recs) {
             float ms = 0; BZ_HIP(hipEventElapsedTime(&ms, r.a, r.b));
             prof_ms[r.cat] += ms; prof_n[r.cat] += 1; bytes_timed_[r.cat] += r.bytes;
@@ -1292,11 +1250,11 @@ template <class T> class Solver final : public SolverBase {
         if (prof_on) {
             // start/stop events bound to the dispatch itself: kernel time without the launch gap
             r.a = get_event(); r.b = get_event();
-            hipExtLaunchKernelGGL(kernel, g, dim3(block), 0, cur_, r.a, r.b, 0, args...);
+            hipExtLaunchKernelGGL(kernel, g, dim3(block), 0, ctx->stream, r.a, r.b, 0, args...);
             prof_recs.push_back(r);
             if (prof_recs.size() > 8192) drain_prof();
         } else {
-            hipLaunchKernelGGL(kernel, g, dim3(block), 0, cur_, args...);
+            hipLaunchKernelGGL(kernel, g, dim3(block), 0, ctx->stream, args...);
         }
         BZ_HIP(hipGetLastError());
     }
@@ -1569,7 +1527,7 @@ template <class T> class Solver final : public SolverBase {
         launch_b(C_GATHER, k_pack, cnt, 64, (const double*)parts_.p, counts, first, cnt, maxmask, send_.p, ctx->rank,
                  keepmask);
         BZ_NCCL(ncclAllGather(send_.p + first, recv_.p + (size_t)first * ctx->nranks, cnt, ncclDouble,
-                              ctx->comm, cur_));
+                              ctx->comm, ctx->stream));
         for (int s = first; s < first + cnt; ++s) { grp_first[s] = first; grp_cnt[s] = cnt; }
     }
     // the arguments of the fold + (p2p) exchange + read-back of slots [first, first + cnt): with mailboxes the exchange over
@@ -1630,7 +1588,7 @@ template <class T> class Solver final : public SolverBase {
     }
     void collect_launch(CollectArgs& a) {
         a.ticket = ++collect_seq;
-        bool unit = env_.collect_wave != 0;
+        bool unit = true;
         for (int i = 0; i < a.n; ++i) unit = unit && a.src[i].stride == 1;
         if (unit) launch_b(C_COLLECT, k_collect_w, a.n, 64, a, host_out_dev_);
         else launch(C_COLLECT, k_collect, a.n, a, host_out_dev_);
@@ -1664,13 +1622,13 @@ template <class T> class Solver final : public SolverBase {
         try {
             run();
             if (n_dense_onepass_ != launched) {
-                BZ_HIP(hipStreamSynchronize(cur_));
+                BZ_HIP(hipStreamSynchronize(ctx->stream));
                 std::atomic_thread_fence(std::memory_order_acquire);
                 if (*ptimeout_) raise_timeout();
             }
         } catch (const DenseFusedTimeout&) {
             if (ctx->nranks > 1 || gate_pending_) throw;
-            BZ_HIP(hipStreamSynchronize(cur_));
+            BZ_HIP(hipStreamSynchronize(ctx->stream));
             *ptimeout_ = 0;
             run();
         }
@@ -1691,14 +1649,14 @@ template <class T> class Solver final : public SolverBase {
                 for (int i = 0; i < a.n; ++i)
                     if ((ho[2 * i] & himask) != tag || (ho[2 * i + 1] & himask) != tag) { done = false; break; }
                 if (!done && (spin & 0x3FFu) == 0x3FFu) {
-                    if (!gate_pending_ && hipStreamQuery(cur_) != hipErrorNotReady) break;     // finished or failed
+                    if (!gate_pending_ && hipStreamQuery(ctx->stream) != hipErrorNotReady) break;     // finished or failed
                     if (std::chrono::steady_clock::now() - t_start > std::chrono::seconds(30)) break;
                 }
             }
             bool complete = done;
             if (!done) {
                 gate_abort();
-                BZ_HIP(hipStreamSynchronize(cur_));
+                BZ_HIP(hipStreamSynchronize(ctx->stream));
                 std::atomic_thread_fence(std::memory_order_acquire);
                 // everything queued has run: the scalars are there now, or they will never be (a device poll that gave
                 // up is reported below; anything else must not be read as numbers)
@@ -1821,7 +1779,7 @@ template <class T> class Solver final : public SolverBase {
         }
         if (desc.c_kind == BZ_C_DENSE_AFFINE) {
             eval_c(x);                                                        // cx = A x - b
-            if (cx_keep_) BZ_HIP(hipMemcpyAsync(cx_keep_, CX_.p, ny * sizeof(T), hipMemcpyDeviceToDevice, cur_));
+            if (cx_keep_) BZ_HIP(hipMemcpyAsync(cx_keep_, CX_.p, ny * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
             mv(2 + pstreams(false, true, false), ny);
             launch(C_MISC, k_yupd<T>, grid_y, (const T*)CX_.p, P, YU_.p, ny, parts_.p, slot0 + 1);
             slot_n[slot0] = grid; slot_n[slot0 + 1] = grid_y;
@@ -2176,10 +2134,10 @@ template <class T> class Solver final : public SolverBase {
         account(C_PERSIST, prof_on ? &r : nullptr);
         if (prof_on) {
             r.a = get_event(); r.b = get_event();
-            hipExtLaunchKernelGGL(kernel, dim3(a.nb), dim3(PBLOCK), 0, cur_, r.a, r.b, 0, a);
+            hipExtLaunchKernelGGL(kernel, dim3(a.nb), dim3(PBLOCK), 0, ctx->stream, r.a, r.b, 0, a);
             prof_recs.push_back(r);
         } else {
-            hipLaunchKernelGGL(kernel, dim3(a.nb), dim3(PBLOCK), 0, cur_, a);
+            hipLaunchKernelGGL(kernel, dim3(a.nb), dim3(PBLOCK), 0, ctx->stream, a);
         }
         BZ_HIP(hipGetLastError());
     }
@@ -2241,7 +2199,7 @@ template <class T> class Solver final : public SolverBase {
         } catch (const DenseFusedTimeout&) {
             // (the start of a solve writes nothing it does not write again: once more, in the two-kernel form)
             if (ctx->nranks > 1) throw;
-            BZ_HIP(hipStreamSynchronize(cur_));
+            BZ_HIP(hipStreamSynchronize(ctx->stream));
             *ptimeout_ = 0;
             std::fprintf(stderr, "Warning: the one-pass dense kernel timed out (is the GPU shared?); using the two-kernel form\n");
             begin_impl(o, X_[0].p);
@@ -2260,7 +2218,6 @@ template <class T> class Solver final : public SolverBase {
         stencil_fast_ = desc.f_kind == BZ_F_STENCIL5 && o.fuse && !lp_g && !slack;
         if (o.affine_refresh < 0) throw Error(BZ_ERR_ARG, "affine_refresh must be >= 0");
         aff_refresh_ = o.affine_refresh;
-        if (env_.affine >= 0) aff_refresh_ = env_.affine;
         aff_track_ = affine_ok_ && aff_refresh_ > 0 && o.lbfgs_compact != 0 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS;
         compact_ok = M >= 1 && (o.lbfgs_compact == 1 || dir_kind_ == BZ_DIR_ANDERSON ||
                                 (o.lbfgs_compact == 2 && (fused_ok || stencil_fast_ || aff_track_) && M <= CM));
@@ -2336,9 +2293,8 @@ template <class T> class Solver final : public SolverBase {
         t_begin = std::chrono::steady_clock::now();
         k_ = 1; n_grad = n_prox = n_bt = n_halv = n_fused = n_skips = 0;
         last_nbt = 0; last_fused = false; tau = T(0); last_ys = T(0); fbe_last = T(0);
-        xc = 0; rc = 0; zc = 0; z_valid = true; xr_run_ = 0; sy_stale_ = false; rh_stale_ = false; res_valid = true;
-        // BZ_GATE: 0 off; 1 (default) the early launch queues behind the read-back on the solver's own stream; 2 on the other
-        // stream (resident while the previous pass runs: measured slower, kept for the record)
+        xc = 0; rc = 0; zc = 0; z_valid = true; xr_run_ = 0; sy_stale_ = false; res_valid = true;
+        // BZ_GATE: 0 off; non-zero (default) the early launch queues behind the read-back on the solver's stream
         // Several ranks: off unless asked for (BZ_GATE=1).  A launch that misses its gate cannot be redone there (the peers
         // have consumed this rank's scalars: BZ_ERR_COMM), and gated launches on distinct devices have never run on
         // hardware — bench.py asks for them after checking, on the node it runs on, that they reproduce the plain launches.
@@ -2347,8 +2303,8 @@ template <class T> class Solver final : public SolverBase {
         // a one-GPU rehearsal, or whoever made an earlier launch of this problem miss its gate) the two starve each other
         if (ctx->shared_device || gate_broken_) gate_env_ = 0;
         gate_sabotage_ = env_.test_gate_timeout;
-        if (gate_env_ && fused_ok) gate_alloc();      // (pinned record, device copy, second stream: not inside an iteration)
-        gate_quiesce();
+        if (gate_env_ && fused_ok) gate_alloc();      // (pinned record, device copy: not inside an iteration)
+        gate_abort();
         if (x0_dev != X_[0].p)
             BZ_HIP(hipMemcpyAsync(X_[0].p, x0_dev, n * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
         const T eps = std::numeric_limits<T>::epsilon();
@@ -2471,12 +2427,12 @@ template <class T> class Solver final : public SolverBase {
     // ---------------------------------------- Base.iterate(iter, state)  (k += 1)
    public:
     // (leaving a library-run loop, normally or by an exception: no pass stays pre-launched at its gate, the flag that
-    // allows pre-launching is down, the solver is back on the context's stream)
+    // allows pre-launching is down)
     struct LoopGuard {
         Solver* s;
         ~LoopGuard() {
             s->more_coming_ = false;
-            try { s->gate_quiesce(); } catch (...) {}
+            s->gate_abort();
         }
     };
     void steps(int64_t k) override {
@@ -2512,8 +2468,7 @@ template <class T> class Solver final : public SolverBase {
                 // (several ranks: the others have taken this rank's stale scalars for good ones — not recoverable here)
                 if (ctx->nranks > 1) throw;
                 gate_abort();              // (the pass launched early for the iteration after this one)
-                BZ_HIP(hipStreamSynchronize(cur_));
-                cur_ = ctx->stream;
+                BZ_HIP(hipStreamSynchronize(ctx->stream));
                 *ptimeout_ = 0;
                 restore();
                 gate_broken_ = true; gate_env_ = 0; ++n_gate_fallbacks_;
@@ -2524,8 +2479,7 @@ template <class T> class Solver final : public SolverBase {
                 // row group can be partly resident — the two-kernel form from now on, and the iteration again
                 if (ctx->nranks > 1) throw;
                 gate_abort();
-                BZ_HIP(hipStreamSynchronize(cur_));
-                cur_ = ctx->stream;
+                BZ_HIP(hipStreamSynchronize(ctx->stream));
                 *ptimeout_ = 0;
                 if (!sv_state || (dir_kind_ == BZ_DIR_BROYDEN && n_halv != sv[4])) throw;      // (a halving resets Broyden's operator itself)
                 restore();
@@ -2547,10 +2501,10 @@ template <class T> class Solver final : public SolverBase {
             }
         } catch (...) {
             more_coming_ = false;
-            try { gate_quiesce(); } catch (...) {}
+            gate_abort();
             throw;
         }
-        if (!more_coming_) gate_quiesce();
+        if (!more_coming_) gate_abort();
     }
     int64_t n_persist_fallbacks_ = 0;
    private:
@@ -2680,19 +2634,17 @@ template <class T> class Solver final : public SolverBase {
         T* const zstore = (env_.skipz && !near_stop) ? (T*)nullptr : Z_[it.zn].p;
         it.z_skipped = zstore == nullptr;
         const bool small = small_vectors();
-        // 0: stored pairs; 1: pairs re-formed from the iterate / residual rings (full memory only); 2: residuals
-        // re-evaluated too — possible as soon as every stored pair is a difference of ring neighbours, also
-        // with a partial memory (the absent pairs are x - x = 0 with zero coefficients)
+        // 0: stored pairs; 2: pairs re-formed from the iterate ring, residuals re-evaluated — possible as soon as every
+        // stored pair is a difference of ring neighbours, also with a partial memory (the absent pairs are x - x = 0 with
+        // zero coefficients)
         const int m_now = (int)order.size();
         int xr = 0;
-        // (the slack form of ALS has its own iterate-history kernel, k_fused_slack_xr: BZ_XR >= 2, any element-wise kinds)
+        // (the slack form of ALS has its own iterate-history kernel, k_fused_slack_xr: any element-wise kinds)
         if (env_.xr && small && (fam >= 0 || slack) && xr_run_ >= m_now) {
-            if (env_.xr >= 2) xr = 2;
-            else if (headline && m_now == CM && !rh_stale_) xr = 1;
+            xr = 2;
             // (only the oldest stored iterate may carry another gamma — see CompactCoef::gam0)
             for (int i = 1; i < m_now; ++i)
                 if (gring_[(xc - m_now + i + NXR) % NXR] != (double)gamma) xr = 0;
-            if (xr == 1 && gring_[(xc - m_now + NXR) % NXR] != (double)gamma) xr = 0;
         }
         if (sy_stale_ && !xr) materialize_pairs();
         if (xr != 2 && !res_valid) ensure_z();
@@ -2707,7 +2659,7 @@ template <class T> class Solver final : public SolverBase {
                                 !(P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX));
         // ... with the kinds fixed too (g = NormL1, D = Box: the ALS form of cfg 2), one pack of loads ahead
         const bool slack_hk = slack_fast && env_.slackkind && P.g_kind == BZ_G_NORM_L1 && P.D_kind == BZ_D_BOX;
-        if (xr == 2 && env_.gfc <= 0 && (!slack || (slack_hk && env_.slackdepth > 0))) gfc = std::min(grid, std::max(1, num_cus));
+        if (xr == 2 && env_.gfc <= 0 && (!slack || slack_hk)) gfc = std::min(grid, std::max(1, num_cus));
         for (int k = 0; k < NFC; ++k) slot_n[SL_TRIAL + k] = gfc;
         // (the vectors this pass touches: history + x_d + z + the parameter vectors (+ res, s, y))
         const int nvec = (xr == 2 ? xr2_streams(m_now) : 2 * CM + 5 + pstreams(true, true, true)) + (zstore ? 1 : 0);
@@ -2715,7 +2667,6 @@ template <class T> class Solver final : public SolverBase {
         if (gate_pending_ && xr != 2) gate_abort();
         if (xr == 2 && slack) onepass_slack_xr(it, gfc, zstore, slack_fast, slack_hk);
         else if (xr == 2) onepass_xr2(it, zstore);
-        else if (xr) onepass_xr1(it, gfc, zstore, nt);
         else onepass_stored(it, gfc, zstore, nt, spec, small && spec);
         // (XR = 2 with the gate: the read-back kernel now, so that the next iteration's pass can queue right behind it)
         onepass_scalars(it, xr == 2 && gate_env_);
@@ -2757,14 +2708,13 @@ template <class T> class Solver final : public SolverBase {
             if (fast) {
                 with_uni(P.uni, [&](auto un) {
                     constexpr int UNI = decltype(un)::value;
-                    if (hk && env_.slackdepth >= 1) go(k_fused_slack_xr<T, CM, NT, true, UNI, 1, 1>);
-                    else if (hk) go(k_fused_slack_xr<T, CM, NT, true, UNI, 1, 0>);
+                    if (hk) go(k_fused_slack_xr<T, CM, NT, true, UNI, 1, 1>);
                     else go(k_fused_slack_xr<T, CM, NT, true, UNI, 0, 0>);
                 });
             } else if (m_now == CM) go(k_fused_slack_xr<T, CM, NT, true, -1, 0, 0>);
             else go(k_fused_slack_xr<T, CM, NT, false, -1, 0, 0>);
         });
-        sy_stale_ = true; rh_stale_ = true; it.res_skipped = true;
+        sy_stale_ = true; it.res_skipped = true;
         it.trial_ok = false;      // (a tau-backtracked point finishes in the generic chain, after the pairs are re-materialised)
     }
     // the headline or family-table pass on the iterate history (k_fused_compact<XR=2>): released if it was pre-launched
@@ -2781,25 +2731,8 @@ template <class T> class Solver final : public SolverBase {
             mv(xr2_streams(cur.m_now) + (zstore ? 1 : 0));
             launch_xr2(cur, it.CC, 0, cur.xd, zstore, (T*)nullptr);
         }
-        sy_stale_ = true; rh_stale_ = true; it.res_skipped = true;
+        sy_stale_ = true; it.res_skipped = true;
         it.trial_ok = env_.trialfuse != 0; it.trial_plan = cur; it.trial_coef = it.CC;
-    }
-    // pairs re-formed from the iterate and residual rings (k_fused_compact<XR=1>)
-    void onepass_xr1(Iter& it, int gfc, T* zstore, bool nt) {
-        CompactVecs<T, CM> XV;
-        XV.m = CM;
-        for (int i = 0; i < CM; ++i) {
-            XV.S[i] = X_[(xc - CM + i + NXR) % NXR].p;
-            XV.Y[i] = RES_[(rc - CM + i + NRR) % NRR].p;
-        }
-        mv(2 * (CM + 1) + pstreams(true, true, true) + 2 + (zstore ? 1 : 0));
-        form_[C_FUSED] = std::string("k_fused_compact<XR=1") + (nt ? ",NT=1>" : ",NT=0>");
-        with_bool(nt, [&](auto nt_) {
-            launch(C_FUSED, k_fused_compact<T, CM, decltype(nt_)::value, true, true, 1>, gfc, XV, it.CC, (const T*)X_[it.xp].p,
-                   (const T*)RES_[it.rp].p, P, gamma, X_[it.xd].p, zstore, RES_[it.rn].p, (T*)nullptr, (T*)nullptr, n, parts_.p,
-                   (int)SL_TRIAL);
-        });
-        sy_stale_ = true;
     }
     // the stored pairs S, Y (k_fused_slack for the lifted vector of ALS, k_fused_compact<XR=0>)
     void onepass_stored(Iter& it, int gfc, T* zstore, bool nt, bool spec, bool off32) {
@@ -2884,16 +2817,16 @@ template <class T> class Solver final : public SolverBase {
         for (int sidx = SL_FXD; sidx <= SL_STOP; ++sidx) slot_n[sidx] = grid;
         // (uniform penalties / zero multipliers travel as numbers, P.uni: the two stencil passes stream mu and mu*y
         // otherwise — 4 of the iteration's 43 passes)
-        // (r03: with the compact form the second pass re-forms grad L(x_d) and res from x_d and z — k_stencil_update_c<REGX> —
-        // so this pass does not write the gradient and that one reads neither: 39 -> 36 passes over n per iteration)
-        const int regx = it.use_compact ? std::max(0, std::min(2, env_.stencil_regx)) : 0;
-        mv(2 + pstreams(false, true, true) + (regx >= 2 ? 2 : 3));        // x_d, b + parameters ; (grad,) z, res
+        // (r03: with the compact form the second pass re-forms res from x_d and z — k_stencil_update_c<REGX = 1> — instead of
+        // reading it)
+        const int regx = it.use_compact && env_.stencil_regx > 0 ? 1 : 0;
+        mv(2 + pstreams(false, true, true) + 3);        // x_d, b + parameters ; grad, z, res
         const StencilHalo<T> halo_x = halo_exchange(X_[xd].p);
         const bool fb_nt = env_.xdnt && (double)n * sizeof(T) * 12 > 340e6;
         nm(fb_nt ? "k_stencil_fb<NT=1>" : "k_stencil_fb<NT=0>");
         with_bool(fb_nt, [&](auto nt_) {
             launch(C_STENCIL_FB, k_stencil_fb<T, decltype(nt_)::value>, grid, (const T*)X_[xd].p, P, (int64_t)desc.f_grid_nx,
-                   (int64_t)desc.f_grid_ny, gamma, regx >= 2 ? (T*)nullptr : GX_.p, Z_[zn].p, RES_[it.rn].p, n, parts_.p,
+                   (int64_t)desc.f_grid_ny, gamma, GX_.p, Z_[zn].p, RES_[it.rn].p, n, parts_.p,
                    (int)SL_FXD, (int)SL_GSUM, halo_x);
         });
         const StencilHalo<T> halo_z = halo_exchange(Z_[zn].p);
@@ -2907,20 +2840,18 @@ template <class T> class Solver final : public SolverBase {
             for (int sidx = 0; sidx < NFC; ++sidx) slot_n[SL_TRIAL + sidx] = sidx < 5 ? grid : g_upd;      // (slots 0..4: k_stencil_fb's)
             mv(2 + pstreams(false, true, false) + (5 - regx) + 2 + 2 * CV.m);
             const bool hist_nt = env_.xdnt && (double)n * sizeof(T) * (2 * CV.m + 12) > 340e6;
-            static const char* const forms[3][3] = {
+            static const char* const forms[2][3] = {
                 {"k_stencil_update_c<FULL=0,NT=0>", "k_stencil_update_c<FULL=1,NT=0>", "k_stencil_update_c<FULL=1,NT=1>"},
-                {"k_stencil_update_c<FULL=0,NT=0,REGX=1>", "k_stencil_update_c<FULL=1,NT=0,REGX=1>", "k_stencil_update_c<FULL=1,NT=1,REGX=1>"},
-                {"k_stencil_update_c<FULL=0,NT=0,REGX=2>", "k_stencil_update_c<FULL=1,NT=0,REGX=2>", "k_stencil_update_c<FULL=1,NT=1,REGX=2>"}};
+                {"k_stencil_update_c<FULL=0,NT=0,REGX=1>", "k_stencil_update_c<FULL=1,NT=0,REGX=1>", "k_stencil_update_c<FULL=1,NT=1,REGX=1>"}};
             nm(forms[regx][CV.m == CM ? 1 + hist_nt : 0]);
             auto go = [&](auto full_, auto nt_) {
                 constexpr bool FULL = decltype(full_)::value, NT = decltype(nt_)::value;
                 auto run = [&](auto kernel) {
                     launch(C_STENCIL_UPD, kernel, g_upd, CV, (const T*)Z_[zn].p, P, (int64_t)desc.f_grid_nx, (int64_t)desc.f_grid_ny,
                            (const T*)X_[xd].p, (const T*)X_[it.xp].p, (const T*)RES_[it.rn].p, (const T*)RES_[it.rp].p,
-                           (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL, halo_z, halo_x);
+                           (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL, halo_z);
                 };
-                if (regx >= 2) run(k_stencil_update_c<T, CM, FULL, NT, 2>);
-                else if (regx == 1) run(k_stencil_update_c<T, CM, FULL, NT, 1>);
+                if (regx == 1) run(k_stencil_update_c<T, CM, FULL, NT, 1>);
                 else run(k_stencil_update_c<T, CM, FULL, NT, 0>);
             };
             if (CV.m == CM && hist_nt) go(std::true_type{}, std::true_type{});
@@ -2940,7 +2871,7 @@ template <class T> class Solver final : public SolverBase {
                    (const T*)RES_[it.rp].p, (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, (T*)nullptr, n, parts_.p,
                    (int)SL_FZ, (int)SL_YS, halo_z);
         }
-        it.have_trial = true; gx_valid = regx < 2; gz_valid = false;
+        it.have_trial = true; gx_valid = true; gz_valid = false;
         n_grad += 2; n_prox += 1;
     }
     // cfg 4: gradient (and c) at x_d into the candidate buffers — the same combination of the held images that forms x_d
@@ -3231,7 +3162,7 @@ template <class T> class Solver final : public SolverBase {
         }
         // A tau-backtracked point sits in the blend buffer: trade the two buffers so that the accepted iterate is
         // the next one of the ring whatever produced it — the stored pairs stay the successive differences of
-        // the ring's last iterates (and residuals), and the run below goes on through backtracks
+        // the ring's last iterates, and the run below goes on through backtracks
         if (it.xcur == it.xb && fused_ok && compact_ok) {
             std::swap(X_[it.xd].p, X_[it.xb].p);
             std::swap(X_[it.xd].n, X_[it.xb].n);
@@ -3244,7 +3175,6 @@ template <class T> class Solver final : public SolverBase {
         // because every iterate in the ring remembers the gamma of its residual, gring_)
         xr_run_ = (fused_ok && compact_ok && (ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON) && it.xcur == it.xd) ? (it.reset_this ? 1 : xr_run_ + 1) : 0;
         gring_[it.xcur] = (double)gamma;
-        if (xr_run_ == 0) rh_stale_ = false;       // (whatever broke the run has materialised the pairs above)
         stop_norm_ = it.v[9];
         xc = it.xcur; rc = it.rn; zc = it.zn;
         z_valid = !(it.z_skipped && it.fused_this);      // the generic trial writes z; an accepted fused one may not have

@@ -244,9 +244,9 @@ def test_slack_iterate_history_form_is_bitwise_neutral(bz, ref, n, iters, start,
     runs = {}
     for name, env in (("pairs", dict(pin, BZ_XR="0")), ("iterates", dict(pin, BZ_XR="2")), ("iterates-z", dict(pin, BZ_XR="2", BZ_SKIPZ="0")),
                       ("iterates-nt", dict(pin, BZ_XR="2", BZ_NT="1")), ("iterates-generic", dict(pin, BZ_XR="2", BZ_SLACKFAST="0")),
-                      # (the fast instantiations with run-time kinds of g and D; with the kinds fixed but no register pipeline)
-                      ("iterates-rtkinds", dict(pin, BZ_XR="2", BZ_SLACKKIND="0")), ("iterates-depth0", dict(pin, BZ_XR="2", BZ_SLACKDEPTH="0"))):
-        for k in ("BZ_XR", "BZ_SKIPZ", "BZ_NT", "BZ_GFC", "BZ_GRID", "BZ_SLACKFAST", "BZ_SLACKKIND", "BZ_SLACKDEPTH"):
+                      # (the fast instantiations with run-time kinds of g and D)
+                      ("iterates-rtkinds", dict(pin, BZ_XR="2", BZ_SLACKKIND="0"))):
+        for k in ("BZ_XR", "BZ_SKIPZ", "BZ_NT", "BZ_GFC", "BZ_GRID", "BZ_SLACKFAST", "BZ_SLACKKIND"):
             monkeypatch.delenv(k, raising=False)
         for k, v in env.items():
             monkeypatch.setenv(k, v)
@@ -263,7 +263,7 @@ def test_slack_iterate_history_form_is_bitwise_neutral(bz, ref, n, iters, start,
         prob.close()
     base = runs["pairs"]
     assert base[5] == 0
-    for name in ("iterates", "iterates-z", "iterates-nt", "iterates-generic", "iterates-rtkinds", "iterates-depth0"):
+    for name in ("iterates", "iterates-z", "iterates-nt", "iterates-generic", "iterates-rtkinds"):
         r = runs[name]
         assert r[5] >= max(4, iters - 12 - 7 * base[4][2] - 2 * base[4][0] - base[4][1]), (name, r[5], base[4])
         assert r[6].startswith("k_fused_slack_xr<NT=1>" if name == "iterates-nt" else "k_fused_slack_xr<NT=0>"), r[6]

@@ -780,12 +780,12 @@ def test_no_acceleration_direction(bz, ref):
 def test_stencil_fast_path_equals_generic_bitwise(bz, ref, compact, monkeypatch):
     """cfg 3: the two fused stencil passes ({gradL(x_d) + FB step}, {gradL(z) + pair + stop norm [+ the compact
     form's Gram products and next p, w: k_stencil_update_c]}) are the same arithmetic and the same summation order
-    as the generic kernels they replace, in both forms of the L-BFGS operator — with grad L(x_d) and res re-formed in the
-    second pass (r03, the default with the compact form: 36 passes over n instead of 39) and with both read from memory."""
+    as the generic kernels they replace, in both forms of the L-BFGS operator — with res re-formed in the second pass
+    (r03, the default with the compact form) and with it read from memory."""
     nx, ny = 96, 128
     d, n, dev, orc = make_cfg3(bz, ref, nx, ny, load=-1.0)
     out = []
-    for fuse, regx in ((True, "1"), (False, "1"), (True, "0"), (True, "2")):
+    for fuse, regx in ((True, "1"), (False, "1"), (True, "0")):
         monkeypatch.setenv("BZ_STENCIL_REGX", regx)
         prob = bz.Problem(*dev, n, n, np.float64)
         prob.set_multipliers(np.full(n, 0.1), np.zeros(n))
@@ -1342,16 +1342,15 @@ def test_fused_start_of_a_solve_is_bitwise_neutral(bz, ref, n, D):
 
 
 @pytest.mark.parametrize("n,iters,start", [(30011, 160, "random"), (400003, 60, "random"), (200003, 470, "zero")])
-def test_history_as_iterates_and_lazy_z_are_bitwise_neutral(bz, ref, n, iters, start):
+def test_iterate_history_and_lazy_z_are_bitwise_neutral(bz, ref, n, iters, start):
     """Two storage tricks of the one-pass compact kernel change WHAT is written, never a value:
-    (1) once the last five iterations were plain ones, the stored pairs are re-formed from the last six iterates
-        kept in the x / res rings (s = x_d - x, y = res - res_prev: the same subtractions) and s, y are no longer
-        written; the first iteration that is not plain turns the snapshots back into pairs;
+    (1) BZ_XR=2 (the default): once the last iterations were plain ones, the stored pairs are re-formed from the
+        last iterates kept in the x ring (s = x_d - x, y = res - res_prev: the same subtractions), the residuals
+        are not read but re-evaluated from those iterates (res = x - prox(x - gamma grad L(x)): the same
+        operations on the same inputs), and s, y, res are no longer written; the first iteration that is not
+        plain turns the iterates back into pairs;
     (2) z is not stored and is re-materialised on demand;
-    (3) BZ_XR=2 (the default): after one more plain iteration the residuals are not read from their ring either but
-        re-evaluated from the six iterates (res = x - prox(x - gamma grad L(x)): the same operations on the same
-        inputs), and res is no longer written;
-    (4) BZ_UNI: uniform penalties mu (and mu*y = 0, the "zero" start) are detected and passed as numbers instead of
+    (3) BZ_UNI: uniform penalties mu (and mu*y = 0, the "zero" start) are detected and passed as numbers instead of
         being streamed.
     With all off, all on, and each alone, runs that go through gamma halvings, tau backtracks, and — the
     "zero" start run to convergence — skipped pairs and re-entries must produce identical bits."""
@@ -1364,7 +1363,7 @@ def test_history_as_iterates_and_lazy_z_are_bitwise_neutral(bz, ref, n, iters, s
     try:
         # (BZ_GFC pins one grid for every form of the kernel: by default the iterate-history form runs on half as
         # many workgroups, a different summation tree — the last run below, compared to rounding)
-        for xr, skipz, uni, gfc in (("0", "0", "0", "2"), ("1", "1", "0", "2"), ("1", "0", "0", "2"), ("0", "1", "0", "2"),
+        for xr, skipz, uni, gfc in (("0", "0", "0", "2"), ("0", "1", "0", "2"),
                                     ("2", "1", "0", "2"), ("2", "0", "0", "2"), ("2", "1", "1", "2"), ("2", "1", "2", "2"),
                                     ("2", "1", "2", None)):
             os.environ["BZ_XR"], os.environ["BZ_SKIPZ"], os.environ["BZ_UNI"] = xr, skipz, uni
@@ -1405,9 +1404,9 @@ def test_history_as_iterates_and_lazy_z_are_bitwise_neutral(bz, ref, n, iters, s
     # the 9..11-pass form (timing category k_fused_iterates) serves every iteration, the first one included (empty
     # memory): it resumes straight after a tau backtrack, runs with a partial memory, and carries the pair of a
     # gamma-halving iteration (y = res_new(gamma/2) - res_prev(gamma)) through the gamma tag of the oldest iterate
-    assert all(r[7] == 0 for r in runs[:4])
+    assert all(r[7] == 0 for r in runs[:2])
     if base[5][2] == 0:
-        assert all(r[7] >= iters - 2 for r in runs[4:] + [dflt])
+        assert all(r[7] >= iters - 2 for r in runs[2:] + [dflt])
     for r in runs[1:]:
         assert np.array_equal(r[0], base[0]) and np.array_equal(r[1], base[1]) and np.array_equal(r[2], base[2])
         assert all(np.array_equal(a, b) for a, b in zip(r[4], base[4]))
@@ -1416,9 +1415,8 @@ def test_history_as_iterates_and_lazy_z_are_bitwise_neutral(bz, ref, n, iters, s
         assert r[5] == base[5]
     assert base[5][3] >= iters - 12                      # the fused pass served (almost) every iteration
     if start == "zero":
-        assert base[5][2] > 0                            # pairs were skipped: the snapshots had to become pairs again
-        assert runs[1][6] > runs[0][6]                   # ... by k_pairs_from_snapshots (category misc)
-        assert runs[4][6] > runs[0][6]                   # ... or k_pairs_from_iterates
+        assert base[5][2] > 0                            # pairs were skipped: the iterates had to become pairs again
+        assert runs[2][6] > runs[0][6]                   # ... by k_pairs_from_iterates (category misc)
 
 
 def test_persistent_kernel_barrier_timeout_falls_back_to_the_kernel_chain(bz, ref, monkeypatch):

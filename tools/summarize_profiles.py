@@ -61,8 +61,6 @@ def form_of(kernel):
             # compile-time UNI that the host launches outside the family table; PP = 1 — q and b cacheable — is tagged)
             table = uni == "-1" or (len(a) > 8 and fam != "35")
             return s + (f",FAM={fam}>" if table else (",PP=1>" if pp == "1" else ">"))
-        if xr == "1":
-            return f"k_fused_compact<XR=1,NT={int(nt)}>"
         return f"k_fused_compact<XR=0,SPEC={int(spec)},NT={int(nt)}>"
     m = re.match(r"(k_compact_xd|k_stencil_update_c)<\w+, \d+(?:, (true|false), (true|false))?(?:, (\d))?>$", k)
     if m:
