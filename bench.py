@@ -1,7 +1,12 @@
 #!/usr/bin/env python3
 """bench.py — PANOCplus inner iterations/sec on the BASELINE headline workload.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full]
+
+A plain run does what the headline figure needs and nothing else: set-up, the W warm-up and K timed iterations, the
+outputs if --dump-outputs is given, the result line.  Every other measurement — the CPU baselines, the two-loop /
+outer-iteration-3 / whole-solve side figures, the repeat blocks of a short K-step window, the RCCL line beside a
+mailbox one — runs only with --full, which adds its keys to the same line; the keys of a plain line mean the same in both.
 
 Workload (BASELINE.json configs[1], SURVEY.md §8(d) cfg 2): l1-regularised diagonal
 quadratic, n = 10^7, fp64, f = sum x(0.5 q x - b), g = 2.5||x||_1 (soft-threshold prox),
@@ -15,7 +20,7 @@ N > 1 (one process per GPU, launched by torch.distributed.run): the SAME n = 10^
 with x sharded in contiguous blocks over the ranks ("scaling": "strong"); the only data
 exchanged are the reductions' partial scalars (RCCL all-gather of <= 10 doubles per rank).
 
-Output: ONE JSON line on rank 0 (contract fields + "roofline" + "cpu_baseline").
+Output: ONE JSON line on rank 0 (contract fields + "roofline" + "cpu_baseline", which is null without --full).
 
 Roofline accounting (round 2): every fraction is BYTES THE IMPLEMENTED DATAFLOW MOVES / time / 8 TB/s, so it can
 never exceed 1.  The library counts, per launch, the bytes the launch is designed to move (its read + write
@@ -574,11 +579,11 @@ def side_workload(args):
         roof["other_gemv"] = {k: {"avg_launch_us": round(1e3 * prof[k]["timed_ms"] / prof[k]["timed_launches"], 3),
                                   "achieved": round(prof[k]["timed_bytes"] / prof[k]["timed_ms"] / 1e6, 1), "form": prof[k]["form"]}
                               for k in ("gemv", "k_gemv_t_mfma") if prof[k]["timed_launches"] and k != roof["category"]}
-    rep = repeat_blocks(elapsed, args.steps, lambda: (fresh(), run_block(prob, args.steps, None))[1])
+    rep = repeat_blocks(elapsed, args.steps, lambda: (fresh(), run_block(prob, args.steps, None))[1]) if args.full else None
     if args.dump_outputs:
         dump_outputs(args.dump_outputs, prob)
     cpu = None
-    if not args.no_cpu_baseline:
+    if args.full and not args.no_cpu_baseline:
         note(f"{args.workload}: cpu baseline on the numpy oracle")
         from oracle import bazinga_ref as ref
         cpu = cpu_baseline_oracle(args.workload, oracles(ref), n, ny, dt, mu, y, x0, mg)
@@ -697,14 +702,19 @@ def main():
                          "zero|l1|nonneg|l1box|indbox|indboxvec, D in box|boxvec|boxveclo|free|zero|vc|cc|eitheror|xor "
                          "(default: the BASELINE workload).  Same sizes, same JSON; every family has its own instantiation "
                          "of the one-pass kernel")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also run every side measurement (off by default: a plain run sets up, warms up, times --steps "
+                         "iterations and prints its line): the CPU baselines, at N = 1 the two-loop, outer-iteration-3 and "
+                         "whole-solve figures, the repeat blocks of a K-step window shorter than 100 ms, at N > 1 the RCCL "
+                         "line beside a mailbox one")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--cpu-states", type=int, default=31)
     ap.add_argument("--no-fuse", action="store_true")
     ap.add_argument("--compact", action="store_true", help="(default) compact L-BFGS representation")
     ap.add_argument("--two-loop", action="store_true",
                     help="evaluate the L-BFGS operator by the two-loop recursion in the reference's operation order "
                          "(2M sequential reductions: 11 exchanges per iteration at N > 1)")
-    ap.add_argument("--no-extras", action="store_true", help="N = 1: skip the two-loop and outer-iteration-3 side measurements")
+    ap.add_argument("--no-extras", action="store_true", help="with --full, N = 1: skip the two-loop, outer-iteration-3 and whole-solve side measurements")
     ap.add_argument("--no-p2p", action="store_true", help="N > 1: keep the RCCL all-gather for the scalar exchange")
     ap.add_argument("--no-rccl", action="store_true",
                     help="N > 1: do not create the RCCL communicator (p2p mailboxes only, checked for rank agreement "
@@ -1044,10 +1054,10 @@ def main():
         R = timed_run(prob, args.steps, args.warmup)
     if "failed" in R:
         fail(f"timed run failed: {R['failed']}", rank, world)
-    # K-step block shorter than 100 ms: repeat it from a fresh solve (same warm-up; every rank takes the same
+    # --full, K-step block shorter than 100 ms: repeat it from a fresh solve (same warm-up; every rank takes the same
     # decision from the max-over-ranks time) and report the spread beside the headline value
     repeats = None
-    if R["elapsed"] < 0.1:
+    if args.full and R["elapsed"] < 0.1:
         nblk = int(min(15, max(4, np.ceil(0.5 / max(R["elapsed"], 1e-6)))))
         ts = [R["elapsed"]]
         R["prof2_blocks"] = [R["prof2"]]
@@ -1066,9 +1076,9 @@ def main():
         dump_outputs(args.dump_outputs, prob, n, lo_i, grp, rank)
     prob.close()
     # N > 1: north_star names RCCL for the scalar reductions — when the timed transport is the p2p mailboxes, the
-    # RCCL all-gather transport is timed as well and printed beside it
+    # RCCL all-gather transport is timed as well and printed beside it (with --full)
     rccl_extra = None
-    if world > 1 and transport == "p2p" and ctx_rccl is not None:
+    if args.full and world > 1 and transport == "p2p" and ctx_rccl is not None:
         os.environ["BZ_GATE"] = "0"              # (gated launches were checked on the mailbox transport only)
         pr = make_problem(ctx_rccl)
         ctx_saved, ctx = ctx, ctx_rccl
@@ -1081,12 +1091,12 @@ def main():
                       if "failed" not in Rr else {"value": None, "note": Rr["failed"]})
     elapsed, st0, st1, sc, prof_all, prof_warm, dom = (R[k] for k in ("elapsed", "st0", "st1", "sc", "prof", "prof_warm", "dom"))
 
-    # N = 1 extras (rank 0 prints them beside the headline, they never replace it):
+    # --full, N = 1 extras (rank 0 prints them beside the headline, they never replace it):
     #   two_loop : the same workload with the L-BFGS operator in the reference's two-loop operation order
     #   outer3   : the same workload inside outer iteration 3 (mu, y after two ALPS outer iterations: y != 0),
     #              SURVEY §8(d)
     extras = {}
-    if world == 1 and not args.no_extras:
+    if args.full and world == 1 and not args.no_extras:
         note("extras: two-loop form and outer iteration 3")
         if compact:
             popts_tl = bz.PANOCplus(tol=0.0, maxit=10 ** 12, minimum_gamma=float(np.finfo(float).eps),
@@ -1193,7 +1203,7 @@ def main():
             out["rccl_value"] = rccl_extra["value"]
             out["rccl"] = rccl_extra
         out.update(extras)
-        if world == 1 and not args.no_cpu_baseline and headline:
+        if args.full and world == 1 and not args.no_cpu_baseline and headline:
             # bounded sample: ~10-30 s of CPU work whatever the size (the port runs ~2.5 it/s per 1e7 elements)
             states = max(4, int(round((args.cpu_states - 1) * min(1.0, 1.0e7 / n))) + 1)
             out["cpu_baseline"] = cpu_baseline(n, states)

@@ -82,3 +82,11 @@ def test_single_gpu_invocation_does_not_self_launch():
     src = inspect.getsource(bench.main)
     assert "args.gpus > 1 and \"WORLD_SIZE\" not in os.environ" in src
     assert src.index("self_launch(") < src.index("import bazinga_jl_amd")      # before the library is even loaded
+
+
+def test_full_is_an_option_and_off_by_default():
+    """the side measurements hang on --full: the parser knows the option (what it switches is checked on the GPU, in
+    test_gpu_bench_contract.py)"""
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], cwd=ROOT, capture_output=True, text=True,
+                       timeout=180)
+    assert r.returncode == 0 and "--full" in r.stdout
