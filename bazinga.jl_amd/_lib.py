@@ -17,7 +17,7 @@ BZ_F64, BZ_F32 = 0, 1
 BZ_F_ZERO, BZ_F_DIAG_QUADRATIC, BZ_F_STENCIL5, BZ_F_LEAST_SQUARES, BZ_F_QUADRATIC = 0, 1, 2, 3, 4
 BZ_G_ZERO, BZ_G_NORM_L1, BZ_G_NORM_L1_NONNEG, BZ_G_NORM_L1_BOX, BZ_G_IND_BOX, BZ_G_NORM_L0_BOX = 0, 1, 2, 3, 4, 5
 BZ_G_NORM_LP_NONNEG, BZ_G_NORM_LP_BOX = 6, 7
-BZ_C_IDENTITY, BZ_C_DENSE_AFFINE = 0, 1
+BZ_C_IDENTITY, BZ_C_DENSE_AFFINE, BZ_C_SPARSE_AFFINE = 0, 1, 3
 BZ_D_ZERO, BZ_D_FREE, BZ_D_BOX = 0, 1, 2
 BZ_D_VC_PAIRS, BZ_D_CC_PAIRS, BZ_D_EITHEROR_PAIRS, BZ_D_XOR_PAIRS = 3, 4, 5, 6
 BZ_F_CALLBACK, BZ_G_CALLBACK, BZ_C_CALLBACK, BZ_D_CALLBACK = 5, 8, 2, 7
@@ -60,6 +60,7 @@ class ProblemDesc(C.Structure):
         ("D_lo", C.c_double), ("D_hi", C.c_double), ("D_lo_vec", C.c_void_p), ("D_hi_vec", C.c_void_p),
         ("cb_user", C.c_void_p), ("cb_f_gradient", F_GRADIENT_FN), ("cb_g_prox", G_PROX_FN),
         ("cb_c_eval", C_EVAL_FN), ("cb_c_jtprod", C_JTPROD_FN), ("cb_D_proj", D_PROJ_FN),
+        ("c_sp_rowptr", C.c_void_p), ("c_sp_col", C.c_void_p), ("c_sp_val", C.c_void_p), ("c_sp_nnz", C.c_int64),
     ]
 
 

@@ -7,6 +7,7 @@
 // as oracle/bazinga_ref.py (PANOCplusIteration.init/step), which documents the
 // provenance of the restatement.
 #include "bz_solver.h"
+#include "bz_spmv.h"
 
 #include <hip/hip_ext.h>
 
@@ -133,6 +134,7 @@ struct CreateKnobs {
     std::optional<int> persist_blocks = env_opt("BZ_PERSIST_BLOCKS");    // the persistent kernel on b CUs (two ranks on one GPU)
     int dense_fused = env_int("BZ_DENSE_FUSED", 1);      // 0: the dense constraint through two products, not k_dense_fused
     std::optional<int> dense_kp = env_opt("BZ_DENSE_KP");                // k_dense_fused's packs per row and lane
+    std::optional<int> spmv_l = env_opt("BZ_SPMV_L");    // lanes per row of the sparse constraint's two passes (a power of two <= 64)
     // test-only
     int test_dense_timeout = env_int("BZ_TEST_DENSE_TIMEOUT", 0);        // the k-th k_dense_fused exchange is sabotaged
     unsigned dense_spin = (unsigned)env_ll("BZ_DENSE_SPIN", 0);          // k_dense_fused's poll bound (0: the default)
@@ -181,6 +183,19 @@ template <class T> class Solver final : public SolverBase {
         if (n <= 0 || ny < 0) throw Error(BZ_ERR_ARG, "n must be positive");
         if (d.c_kind == BZ_C_IDENTITY && ny != n)
             throw Error(BZ_ERR_ARG, "c = Identity requires ny == n");
+        if (d.c_kind == BZ_C_SPARSE_AFFINE) {
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: the slack (ALS) form is not lowered with a sparse c");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine is not sharded (one rank)");
+            if (d.D_kind >= BZ_D_VC_PAIRS && d.D_kind <= BZ_D_XOR_PAIRS)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: pairwise D sets need c = Identity");
+            if (d.f_kind == BZ_F_STENCIL5) throw Error(BZ_ERR_UNSUPPORTED, "Stencil5pt f with a sparse c");
+            if (d.f_kind == BZ_F_LEAST_SQUARES || d.f_kind == BZ_F_QUADRATIC)
+                throw Error(BZ_ERR_UNSUPPORTED, "dense f with a sparse c");
+            if (ny <= 0 || !d.c_b || !d.c_sp_rowptr || d.c_sp_nnz < 0 || (d.c_sp_nnz > 0 && (!d.c_sp_col || !d.c_sp_val)))
+                throw Error(BZ_ERR_ARG, "SparseAffine needs rowptr[ny + 1], col[nnz], val[nnz] and b[ny]");
+            if (n > (int64_t)std::numeric_limits<int32_t>::max() || ny > (int64_t)std::numeric_limits<int32_t>::max())
+                throw Error(BZ_ERR_ARG, "SparseAffine: n and ny must fit 32-bit column indices");
+        }
         if (slack) {
             // ALS: the inner solver works on xs = [x; s]; from here on `n` is the length of that vector
             if (d.c_kind != BZ_C_IDENTITY || (d.f_kind != BZ_F_ZERO && d.f_kind != BZ_F_DIAG_QUADRATIC))
@@ -205,7 +220,7 @@ template <class T> class Solver final : public SolverBase {
                 if (ny <= 0) throw Error(BZ_ERR_ARG, "generic oracles: ny must be positive");
             }
         }
-        if (d.c_kind != BZ_C_IDENTITY && d.c_kind != BZ_C_DENSE_AFFINE && !generic_)
+        if (d.c_kind != BZ_C_IDENTITY && d.c_kind != BZ_C_DENSE_AFFINE && d.c_kind != BZ_C_SPARSE_AFFINE && !generic_)
             throw Error(BZ_ERR_UNSUPPORTED, "constraint kind not lowered to the device");
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             if (ny <= 0 || !d.c_A || !d.c_b) throw Error(BZ_ERR_ARG, "DenseAffine needs A[ny][n] and b[ny]");
@@ -307,6 +322,11 @@ template <class T> class Solver final : public SolverBase {
             if (affine_ok_) {
                 CXS_.alloc(ny); CZS_.alloc(ny); CXD_.alloc(ny); CZN_.alloc(ny);
             }
+        }
+        if (d.c_kind == BZ_C_SPARSE_AFFINE) {
+            sparse_create(d);
+            upload(cb_, d.c_b, ny);
+            CX_.alloc(ny); YU_.alloc(ny);
         }
 
         std::memset(&P, 0, sizeof(P));
@@ -542,7 +562,7 @@ template <class T> class Solver final : public SolverBase {
         T objx = f_value(v0[1]) + gz0;
         // eval!(cx,c,x); proj!(s,D,cx); default_penalty_parameter!     alps.jl:40-42
         const double denom = std::max(1.0, (double)objx);
-        const bool dense_c = desc.c_kind == BZ_C_DENSE_AFFINE;
+        const bool dense_c = desc.c_kind == BZ_C_DENSE_AFFINE || desc.c_kind == BZ_C_SPARSE_AFFINE;      // c(x) lives in CX_
         if (dense_c) eval_c(x);
         if (generic_) {
             // eval!(cx, c, x) ; proj!(s, D, cx) ; default_penalty_parameter!   (alps.jl:40-42, safeguards.jl:13-18:
@@ -1711,6 +1731,176 @@ template <class T> class Solver final : public SolverBase {
         }
     }
 
+    // ---- c = SparseAffine: A and A' as two CSR matrices in HBM, each with the launch plan fixed at creation
+    struct SpCsr {
+        DBuf<int64_t> ptr;                 // [nv + 1]: the row pointers, refined at the cuts of long rows
+        DBuf<int32_t> col;
+        DBuf<T> val;
+        DBuf<int32_t> vrow, vpart;         // cut matrices only: virtual row -> row, and -> its slot in `part` (-1: a whole row)
+        DBuf<int32_t> crow, cptr;          // the cut rows and where each one's segment sums start in `part`
+        DBuf<double> part;
+        int64_t rows = 0, cols = 0, nnz = 0, nv = 0, S = 0;
+        int L = 1, ncut = 0;
+        SpMat<T> mat() const { return SpMat<T>{ptr.p, col.p, val.p, ncut ? vrow.p : nullptr, ncut ? vpart.p : nullptr, part.p, nv}; }
+        // bytes of one pass without the per-row vectors: both CSR arrays, the row pointers (and the two virtual-row
+        // tables of a cut matrix), one read of the gathered vector
+        double bytes() const {
+            return (double)nnz * (sizeof(T) + 4) + (double)(nv + 1) * 8 + (ncut ? (double)nv * 8 : 0.0) + (double)cols * sizeof(T);
+        }
+    };
+    SpCsr spA_, spAt_;
+    std::string sp_form_[2];
+    template <class V> static void sp_upload(DBuf<V>& dst, const std::vector<V>& src) {
+        dst.alloc(src.size());
+        if (!src.empty()) BZ_HIP(hipMemcpy(dst.p, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
+    }
+    // Segment length: rows longer than a quarter of one wave's share of the entries are cut (the machine taken as the
+    // largest grid the row kernels use, PSTRIDE workgroups of WAVES waves), never below 512 entries, a multiple of 64.
+    // A function of the matrix alone.
+    static int64_t sp_segment_length(int64_t nnz) {
+        const int64_t share = nnz / ((int64_t)PSTRIDE * WAVES);
+        return std::max<int64_t>(512, ((share / 4 + 63) / 64) * 64);
+    }
+    // lanes per row from the mean (virtual) row length: about four entries per lane and batch
+    static int sp_lanes(int64_t nnz, int64_t nv) {
+        const double mean = nv > 0 ? (double)nnz / (double)nv : 0.0;
+        int L = 1;
+        while (L < 64 && mean > 4.0 * L) L *= 2;
+        return L;
+    }
+    void sp_build(SpCsr& m, int64_t rows, int64_t cols, const std::vector<int64_t>& rp, const std::vector<int32_t>& col,
+                  const std::vector<T>& val) {
+        m.rows = rows; m.cols = cols; m.nnz = rp[rows];
+        m.S = sp_segment_length(m.nnz);
+        int64_t nv = 0, nparts = 0;
+        int ncut = 0;
+        for (int64_t r = 0; r < rows; ++r) {
+            const int64_t len = rp[r + 1] - rp[r];
+            const int64_t segs = len > m.S ? (len + m.S - 1) / m.S : 1;
+            nv += segs;
+            if (segs > 1) { ++ncut; nparts += segs; }
+        }
+        if (nv > (int64_t)std::numeric_limits<int32_t>::max()) throw Error(BZ_ERR_ARG, "SparseAffine: too many row segments");
+        m.nv = nv; m.ncut = ncut;
+        if (ncut) {
+            std::vector<int64_t> vp; std::vector<int32_t> vrow, vpart, crow, cptr;
+            vp.reserve(nv + 1); vrow.reserve(nv); vpart.reserve(nv);
+            int32_t np = 0;
+            for (int64_t r = 0; r < rows; ++r) {
+                const int64_t len = rp[r + 1] - rp[r];
+                if (len > m.S) {
+                    crow.push_back((int32_t)r); cptr.push_back(np);
+                    for (int64_t s0 = rp[r]; s0 < rp[r + 1]; s0 += m.S) { vp.push_back(s0); vrow.push_back((int32_t)r); vpart.push_back(np++); }
+                } else {
+                    vp.push_back(rp[r]); vrow.push_back((int32_t)r); vpart.push_back(-1);
+                }
+            }
+            vp.push_back(rp[rows]); cptr.push_back(np);
+            sp_upload(m.ptr, vp); sp_upload(m.vrow, vrow); sp_upload(m.vpart, vpart);
+            sp_upload(m.crow, crow); sp_upload(m.cptr, cptr);
+            m.part.alloc((size_t)nparts);
+        } else {
+            sp_upload(m.ptr, rp);
+        }
+        sp_upload(m.col, col); sp_upload(m.val, val);
+        m.L = sp_lanes(m.nnz, nv);
+        if (cenv_.spmv_l) {
+            const int l = *cenv_.spmv_l;
+            if (l < 1 || l > 64 || (l & (l - 1))) throw Error(BZ_ERR_ARG, "BZ_SPMV_L must be a power of two in 1..64");
+            m.L = l;
+        }
+    }
+    // validate the caller's CSR on a host copy, build A' by a stable counting sort (a column's entries stay in
+    // ascending row order) and put both in HBM
+    void sparse_create(const bz_problem_desc& d) {
+        const int64_t nnz = d.c_sp_nnz;
+        std::vector<int64_t> rp((size_t)ny + 1);
+        std::vector<int32_t> col((size_t)nnz);
+        std::vector<T> val((size_t)nnz);
+        BZ_HIP(hipMemcpy(rp.data(), d.c_sp_rowptr, rp.size() * sizeof(int64_t), hipMemcpyDefault));
+        if (nnz) {
+            BZ_HIP(hipMemcpy(col.data(), d.c_sp_col, col.size() * sizeof(int32_t), hipMemcpyDefault));
+            BZ_HIP(hipMemcpy(val.data(), d.c_sp_val, val.size() * sizeof(T), hipMemcpyDefault));
+        }
+        if (rp[0] != 0) throw Error(BZ_ERR_ARG, "SparseAffine: rowptr[0] must be 0 (row 0)");
+        for (int64_t r = 0; r < ny; ++r)
+            if (rp[r + 1] < rp[r] || rp[r + 1] > nnz)
+                throw Error(BZ_ERR_ARG, "SparseAffine: rowptr must be non-decreasing and end at nnz (row " + std::to_string(r) + ")");
+        if (rp[ny] != nnz)
+            throw Error(BZ_ERR_ARG, "SparseAffine: rowptr[ny] must equal nnz (row " + std::to_string(ny - 1) + ")");
+        std::vector<int64_t> tp((size_t)n + 1, 0);
+        for (int64_t r = 0; r < ny; ++r)
+            for (int64_t k = rp[r]; k < rp[r + 1]; ++k) {
+                if (col[k] < 0 || (int64_t)col[k] >= n)
+                    throw Error(BZ_ERR_ARG, "SparseAffine: column index outside [0, n) (row " + std::to_string(r) + ")");
+                ++tp[(size_t)col[k] + 1];
+            }
+        for (int64_t j = 0; j < n; ++j) tp[j + 1] += tp[j];
+        std::vector<int32_t> tcol((size_t)nnz);
+        std::vector<T> tval((size_t)nnz);
+        {
+            std::vector<int64_t> next(tp.begin(), tp.end() - 1);
+            for (int64_t r = 0; r < ny; ++r)
+                for (int64_t k = rp[r]; k < rp[r + 1]; ++k) {
+                    const int64_t at = next[col[k]]++;
+                    tcol[at] = (int32_t)r; tval[at] = val[k];
+                }
+        }
+        sp_build(spA_, ny, n, rp, col, val);
+        sp_build(spAt_, n, ny, tp, tcol, tval);
+        for (int t = 0; t < 2; ++t) {
+            const SpCsr& m = t ? spAt_ : spA_;
+            sp_form_[t] = std::string(t ? "k_spmv_t_finish<L=" : "k_spmv_yupd<L=") + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
+        }
+    }
+    // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A') and, for a cut matrix, the fold
+    // of its cut rows; returns the number of block partials left in `slot`
+    template <int MODE> int sp_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
+        const double bytes = m.bytes() + vec_bytes;
+        const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
+        const int gfold = m.ncut ? (int)std::min<int64_t>(512, (m.ncut + WAVES - 1) / WAVES) : 0;
+        int g = 1;
+        auto go = [&](auto l_, auto nt_) {
+            constexpr int L = decltype(l_)::value;
+            constexpr bool NT = decltype(nt_)::value;
+            const int64_t rpb = BLOCK / L;
+            g = (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - gfold, (m.nv + rpb - 1) / rpb));
+            pending_bytes_ += bytes;
+            nm(sp_form_[MODE].c_str());
+            if constexpr (MODE == 0) launch(C_GEMV, k_spmv_yupd<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else launch(C_GEMV, k_spmv_t_finish<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+        };
+        with_bool(nt, [&](auto nt_) {
+            switch (m.L) {
+            case 1: go(std::integral_constant<int, 1>{}, nt_); break;
+            case 2: go(std::integral_constant<int, 2>{}, nt_); break;
+            case 4: go(std::integral_constant<int, 4>{}, nt_); break;
+            case 8: go(std::integral_constant<int, 8>{}, nt_); break;
+            case 16: go(std::integral_constant<int, 16>{}, nt_); break;
+            case 32: go(std::integral_constant<int, 32>{}, nt_); break;
+            default: go(std::integral_constant<int, 64>{}, nt_); break;
+            }
+        });
+        if (gfold) {
+            pending_bytes_ += (double)m.part.n * 8 + (double)m.ncut * 8;
+            launch(C_MISC, k_spmv_fold<T, MODE>, gfold, (const double*)m.part.p, (const int32_t*)m.crow.p,
+                   (const int32_t*)m.cptr.p, m.ncut, E, parts_.p, slot, g);
+        }
+        return g + gfold;
+    }
+    // rows of A: c(x) -> cx (where the caller keeps it), yhat -> yupd and the penalty partials -> slot (yupd null: c(x) alone)
+    int spmv_yupd(const T* x, T* cx, T* yupd, int slot) {
+        SpEpi<T> E{cb_.p, cx, yupd, nullptr, P};
+        const double vecs = (1 + (cx ? 1 : 0) + (yupd ? 1 + pstreams(false, true, false) : 0)) * (double)ny * sizeof(T);
+        return sp_pass<0>(spA_, x, E, slot, vecs);
+    }
+    // rows of A': grad = grad f(x) + A'yhat and the f partials -> slot
+    int spmv_t_finish(const T* x, T* grad, int slot) {
+        SpEpi<T> E{nullptr, nullptr, grad, x, P};
+        const double vecs = ((grad ? 1 : 0) + (P.f_kind == BZ_F_DIAG_QUADRATIC ? 3 : 0)) * (double)n * sizeof(T);
+        return sp_pass<1>(spAt_, YU_.p, E, slot, vecs);
+    }
+
     // gradient!(dlx, al, x) on the device; partials -> slot0 (f terms), slot0+1 (t^2/mu)
     // row chunks of the transposed product: enough blocks to fill the chip, fixed summation order
     void plan_chunks(int64_t rows, int& rpc, int& nch) const {
@@ -1743,7 +1933,10 @@ template <class T> class Solver final : public SolverBase {
         launch2d(C_GEMV, k_gemv_t<T>, colblocks, nch, M, v, GT_.p, rows, n, rpc, npad);
     }
     // eval!(cx, c, x) for the dense constraint
-    void eval_c(const T* x) { gemv_rows(A_.p, ny, x, cb_.p, CX_.p); }
+    void eval_c(const T* x) {
+        if (desc.c_kind == BZ_C_SPARSE_AFFINE) { spmv_yupd(x, CX_.p, nullptr, (int)SL_SCRATCH); return; }
+        gemv_rows(A_.p, ny, x, cb_.p, CX_.p);
+    }
     // dense f: leaves what k_algrad_elem / k_fvalue_elem need in FR_ / DFX_ and the f partials in slot0
     //   LeastSquares: r = A x - b ; slot0 <- <r,r> ; DFX = A' r        (ProximalOperators: 0.5||Ax-b||^2)
     //   Quadratic:    FR = Q x (value and gradient finished element-wise)
@@ -1768,6 +1961,13 @@ template <class T> class Solver final : public SolverBase {
     }
     void algrad(const T* x, T* grad, int slot0) {
         if (generic_) { algrad_generic(x, grad, slot0); return; }
+        if (desc.c_kind == BZ_C_SPARSE_AFFINE) {
+            // two launches: rows of A (c(x), yhat, the penalty partials), rows of A' (A'yhat, grad f, the f partials)
+            slot_n[slot0 + 1] = spmv_yupd(x, cx_keep_, YU_.p, slot0 + 1);
+            slot_n[slot0] = spmv_t_finish(x, grad, slot0);
+            gather(slot0, 2, 0u, 2u);
+            return;
+        }
         if (desc.c_kind == BZ_C_DENSE_AFFINE && dense_fused_on()) {
             // one pass over A: c(x), yhat and the row-group partials of A'yhat (k_dense_fused), then the fold + f terms
             slot_n[slot0] = grid;

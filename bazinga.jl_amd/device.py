@@ -112,10 +112,10 @@ class Problem:
     """bz_problem: the lowered (f, g, c, D) with its device-resident data and solver state."""
 
     def __init__(self, f, g, c, D, n, ny, dtype, ctx: Context | None = None, slack: bool = False):
-        self.ctx = ctx or default_context()
         self.nx, self.ny, self.dtype, self.slack = int(n), int(ny), np.dtype(dtype), bool(slack)
         self.n = self.nx + self.ny if slack else self.nx       # length of the inner decision vector
-        desc, keep = lower(f, g, c, D, self.nx, self.ny, self.dtype, slack)
+        desc, keep = lower(f, g, c, D, self.nx, self.ny, self.dtype, slack)      # (raises before any device call)
+        self.ctx = ctx or default_context()
         h = C.c_void_p()
         L.check(L.load().bz_problem_create(self.ctx._h, C.byref(desc), C.byref(h)))
         # structured oracles: the library has copied the data.  Generic oracles: the callback thunks (and the list

@@ -253,6 +253,72 @@ class DenseAffine(SmoothFunction):
         jtv[...] = self.A.T @ v
 
 
+class SparseAffine(SmoothFunction):
+    """c(x) = A x - b with A[ny][n] in CSR (indptr[ny + 1], indices[nnz] 0-based, data[nnz]): the structured, never
+    densified constraint map of demo/obstacle.jl:93-113 (c(x) = x1 + T x2 - x3).  The column indices of a row need not
+    be sorted, an index that occurs twice in a row contributes twice, an empty row gives -b_i and an empty column a
+    zero of A'v.  eval! / jtprod! below are numpy (the host outer loop, and the generic-oracle protocol); on the device
+    the kind is BZ_C_SPARSE_AFFINE."""
+
+    def __init__(self, indptr, indices, data, b, n):
+        ip, ix = np.asarray(indptr), np.asarray(indices)
+        self.data = np.ascontiguousarray(data)
+        self.b = np.ascontiguousarray(b)
+        self.n = int(n)
+        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or self.b.ndim != 1:
+            raise ValueError("indptr, indices, data and b must be one-dimensional")
+        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr and indices must be integer arrays")
+        if self.data.dtype not in (np.float64, np.float32) or self.b.dtype not in (np.float64, np.float32):
+            raise ValueError("data and b must be float64 or float32")
+        self.ny = self.b.shape[0]
+        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.ny <= 0:
+            raise ValueError("n must be in 1 .. 2^31 - 1 and b non-empty")
+        if ip.shape[0] != self.ny + 1:
+            raise ValueError(f"indptr must have length ny + 1 = {self.ny + 1}")
+        if ix.shape[0] != self.data.shape[0]:
+            raise ValueError("indices and data must have the same length")
+        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
+        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
+            raise ValueError(f"column indices must lie in [0, {self.n})")
+        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
+        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
+        self._rows = np.repeat(np.arange(self.ny, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+
+    @property
+    def nnz(self):
+        return int(self.indices.shape[0])
+
+    @classmethod
+    def from_dense(cls, A, b):
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise ValueError("A must be ny-by-n")
+        mask = A != 0
+        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
+        indices = np.nonzero(mask)[1].astype(np.int32)
+        return cls(indptr, indices, np.ascontiguousarray(A[mask]), b, A.shape[1])
+
+    @classmethod
+    def from_scipy(cls, M, b):
+        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        return cls(M.indptr, M.indices, M.data, b, M.shape[1])
+
+    def toarray(self):
+        A = np.zeros((self.ny, self.n), self.data.dtype)
+        np.add.at(A, (self._rows, self.indices), self.data)
+        return A
+
+    def eval(self, cx, x):
+        cx[...] = np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.ny) - self.b
+
+    def jtprod(self, jtv, x, v):
+        jtv[...] = np.bincount(self.indices, weights=self.data * v[self._rows], minlength=self.n)
+
+
 # ------------------------------------------------------------------------- D
 class ZeroSet(ClosedSetBase):
     """src/projections/zeroSet.jl:8-20"""
@@ -375,7 +441,7 @@ def _vec(a, dtype, n, name):
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, Stencil5ptQuadratic))
 _LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
-_LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine))
+_LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
 _LOWERED_D = lambda D: isinstance(D, (ZeroSet, FreeSet, PairwiseSet)) or \
     (isinstance(D, IndicatorSet) and isinstance(D.f, (IndBox, IndFree)))
 
@@ -539,6 +605,22 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
             raise ValueError(f"A must be {ny}-by-{n}")
         A = np.ascontiguousarray(c.A, dtype=dtype)
         d.c_A = ptr(A)
+        d.c_b = ptr(_vec(c.b, dtype, ny, "b"))
+    elif isinstance(c, SparseAffine):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("SparseAffine is not lowered in the slack (ALS) form")
+        if not isinstance(f, (Zero, DiagQuadratic)):
+            raise UnsupportedOracle(f"SparseAffine is lowered with an element-wise f (Zero, DiagQuadratic), not {type(f).__name__}")
+        if isinstance(D, PairwiseSet):
+            raise UnsupportedOracle("pairwise D sets need c = IdentityFunction")
+        if (c.ny, c.n) != (ny, n):
+            raise ValueError(f"A must be {ny}-by-{n}")
+        d.c_kind = L.BZ_C_SPARSE_AFFINE
+        d.c_sp_rowptr = ptr(c.indptr)
+        d.c_sp_col = ptr(c.indices)
+        d.c_sp_val = ptr(np.ascontiguousarray(c.data, dtype=dtype))
+        d.c_sp_nnz = c.nnz
         d.c_b = ptr(_vec(c.b, dtype, ny, "b"))
     else:
         raise UnsupportedOracle(f"c of type {type(c).__name__} is not lowered to the device")

@@ -412,9 +412,13 @@ def _als_host_loop(f, g, c, D, x, y, cx, s, mu, gFun, objx, tol_prim, tol_dual, 
 
 def _eval_c_host(c, x, ny=None):
     """eval!(cx, c, x) for the host outer loop's O(ny) bookkeeping (outside the hot path)."""
-    from .oracles import DenseAffine, IdentityFunction
+    from .oracles import DenseAffine, IdentityFunction, SparseAffine
     if isinstance(c, IdentityFunction):
         return x
+    if isinstance(c, SparseAffine):
+        cx = np.empty(c.ny, x.dtype)
+        c.eval(cx, x)
+        return cx
     if isinstance(c, DenseAffine):
         return (c.A @ x - c.b).astype(x.dtype, copy=False)
     if callable(getattr(c, "eval", None)) and ny is not None:      # generic oracle: the reference's protocol

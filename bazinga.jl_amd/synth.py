@@ -67,3 +67,47 @@ def basis_pursuit(ny: int = 8192, n: int = 65536, dtype=np.float32, density: flo
     xtrue = np.where(u < density, sgn, 0.0).astype(dtype)
     b = (A.astype(np.float64) @ xtrue.astype(np.float64)).astype(dtype)
     return {"A": A, "b": b, "xtrue": xtrue}
+
+
+def obstacle_1d(N: int, dtype=np.float64):
+    """The constraint map of the one-dimensional obstacle problem, c(x) = x1 + T x2 - x3 on x = [x1; x2; x3] with
+    T = tridiag(-1, 2, -1): the CSR of [I, T, -I] (ny = N, n = 3N, at most five entries per row), b = 0, D = ZeroSet
+    (x = 0 is feasible).  With it a DiagQuadratic f: q_i = 0.5 + u1, b_i = 2 u2 - 1."""
+    i = np.arange(N, dtype=np.int64)
+    cols = np.stack([i, N + i - 1, N + i, N + i + 1, 2 * N + i], axis=1)
+    vals = np.tile(np.array([1.0, -1.0, 2.0, -1.0, -1.0]), (N, 1))
+    keep = np.ones((N, 5), bool)
+    keep[0, 1] = False
+    keep[N - 1, 3] = False
+    indptr = np.concatenate(([0], np.cumsum(keep.sum(axis=1)))).astype(np.int64)
+    n = 3 * N
+    return {"indptr": indptr, "indices": cols[keep].astype(np.int32), "data": vals[keep].astype(dtype),
+            "b": np.zeros(N, dtype), "n": n, "ny": N,
+            "q": (0.5 + uniform(1, n)).astype(dtype), "fb": (2.0 * uniform(2, n) - 1.0).astype(dtype)}
+
+
+def budget_bands(n: int, m: int, dtype=np.float64):
+    """A budget row beside band rows (ny = m + 1): row 0 is sum_i x_i = 1 (n entries, D_0 = {0} with b_0 = 1); row k >= 1
+    has three consecutive entries a = 2 u3 - 1 starting at column ((k - 1)(n - 4)) div m and one entry in column n - 1,
+    which every band row shares, with b_k = 0 and D_k = [lo_k, hi_k] drawn around the row's value at a point xfeas of
+    the simplex: the constraints are consistent.  With it g = IndBox(0, 1) and a DiagQuadratic f: q_i = 0.5 + u1,
+    b_i = 2 u2 - 1."""
+    if n < 5 or m < 1:
+        raise ValueError("budget_bands needs n >= 5 and m >= 1")
+    k = np.arange(m, dtype=np.int64)
+    start = (k * (n - 4)) // m
+    bcols = np.stack([start, start + 1, start + 2, np.full(m, n - 1, np.int64)], axis=1)
+    bvals = (2.0 * uniform(3, 4 * m) - 1.0).reshape(m, 4)
+    indptr = np.concatenate(([0], n + 4 * np.arange(m + 1, dtype=np.int64)))
+    indices = np.concatenate((np.arange(n, dtype=np.int64), bcols.reshape(-1))).astype(np.int32)
+    data = np.concatenate((np.ones(n), bvals.reshape(-1))).astype(dtype)
+    xfeas = uniform(4, n)
+    xfeas /= xfeas.sum()
+    at = (data[n:].astype(np.float64).reshape(m, 4) * xfeas[bcols]).sum(axis=1)      # the band rows at xfeas
+    lo = np.concatenate(([0.0], at - 0.1 * uniform(5, m))).astype(dtype)
+    hi = np.concatenate(([0.0], at + 0.1 * uniform(6, m))).astype(dtype)
+    b = np.zeros(m + 1, dtype)
+    b[0] = 1
+    return {"indptr": indptr, "indices": indices, "data": data, "b": b, "n": n, "ny": m + 1, "lo": lo, "hi": hi,
+            "xfeas": xfeas.astype(dtype), "q": (0.5 + uniform(1, n)).astype(dtype),
+            "fb": (2.0 * uniform(2, n) - 1.0).astype(dtype)}

@@ -67,6 +67,12 @@ extern "C" {
 /* c: constraint map.  eval!(cx,c,x), jtprod!(jtv,c,x,v)                             */
 #define BZ_C_IDENTITY        0   /* test/definitions/identityFunction.jl:3-13         */
 #define BZ_C_DENSE_AFFINE    1   /* A x - b, demo/basispursuit.jl:38-49               */
+#define BZ_C_SPARSE_AFFINE   3   /* A x - b with A in CSR (c_sp_*): the structured, never densified constraint of
+                                    demo/obstacle.jl:93-113 (c(x) = x1 + T x2 - x3, T = SymTridiagonal(2, -1)).
+                                    The column indices of a row need not be sorted; an index that occurs twice in a
+                                    row contributes twice; an empty row gives c_i = -b_i; an empty column gives
+                                    (A'v)_j = 0.  n <= 2^31 - 1, nnz is 64-bit.  slack = 0, one rank, f Zero or
+                                    DiagQuadratic, D Zero / Free / Box; affine_refresh is ignored (no images).    */
 /* D: closed set.  proj!(s,D,v)                                                      */
 #define BZ_D_ZERO            0   /* src/projections/zeroSet.jl:17-20                  */
 #define BZ_D_FREE            1   /* src/projections/freeSet.jl:17-20                  */
@@ -192,6 +198,11 @@ typedef struct {
     bz_c_eval_fn     cb_c_eval;
     bz_c_jtprod_fn   cb_c_jtprod;
     bz_D_proj_fn     cb_D_proj;
+    /* c, SPARSE_AFFINE (with c_b[ny]): A in CSR, copied (and validated: BZ_ERR_ARG) at bz_problem_create */
+    const int64_t* c_sp_rowptr;    /* rowptr[ny + 1], rowptr[0] = 0, non-decreasing, rowptr[ny] = nnz */
+    const int32_t* c_sp_col;       /* col[nnz], 0-based, in [0, n)                    */
+    const void*    c_sp_val;       /* val[nnz]                                        */
+    int64_t        c_sp_nnz;
 } bz_problem_desc;
 
 int  bz_problem_create(bz_ctx* ctx, const bz_problem_desc* desc, bz_problem** out);

@@ -14,6 +14,7 @@ module BazingaHIP
 
 using Bazinga
 import ProximalOperators
+using SparseArrays: SparseMatrixCSC, sparse
 
 const lib = get(ENV, "BAZINGA_HIP_LIB", "libbazinga_hip.so")
 
@@ -34,6 +35,8 @@ Base.@kwdef mutable struct ProblemDesc
     # generic oracles (all four kinds BZ_*_CALLBACK): host callbacks, see lower_generic!
     cb_user::Ptr{Cvoid} = C_NULL; cb_f_gradient::Ptr{Cvoid} = C_NULL; cb_g_prox::Ptr{Cvoid} = C_NULL
     cb_c_eval::Ptr{Cvoid} = C_NULL; cb_c_jtprod::Ptr{Cvoid} = C_NULL; cb_D_proj::Ptr{Cvoid} = C_NULL
+    # c = SparseAffine (BZ_C_SPARSE_AFFINE): A in CSR, 0-based
+    c_sp_rowptr::Ptr{Cvoid} = C_NULL; c_sp_col::Ptr{Cvoid} = C_NULL; c_sp_val::Ptr{Cvoid} = C_NULL; c_sp_nnz::Int64 = 0
 end
 Base.@kwdef mutable struct PanocOpts
     tol::Float64 = 1e-8; maxit::Int64 = 1000; freq::Int32 = 10; verbose::Int32 = 0
@@ -105,6 +108,19 @@ end
 Bazinga.eval!(cx, c::DenseAffine, x) = (cx .= c.A * x .- c.b; nothing)
 Bazinga.jtprod!(jtv, c::DenseAffine, x, v) = (jtv .= c.A' * v; nothing)
 
+"""`SparseAffine(A::SparseMatrixCSC, b)`: c(x) = A x - b with a sparse A that is never densified (the shape of
+demo/obstacle.jl:93-113).  The library takes CSR: the CSC arrays of `sparse(A')` ARE the CSR arrays of A, made 0-based here."""
+struct SparseAffine{T} <: Bazinga.SmoothFunction
+    A::SparseMatrixCSC{T,Int}; b::Vector{T}
+    rowptr::Vector{Int64}; col::Vector{Int32}; val::Vector{T}
+    function SparseAffine(A::SparseMatrixCSC{T}, b::Vector{T}) where {T}
+        At = sparse(A')
+        new{T}(A, b, Int64.(At.colptr .- 1), Int32.(At.rowval .- 1), Vector{T}(At.nzval))
+    end
+end
+Bazinga.eval!(cx, c::SparseAffine, x) = (cx .= c.A * x .- c.b; nothing)
+Bazinga.jtprod!(jtv, c::SparseAffine, x, v) = (jtv .= c.A' * v; nothing)
+
 "`LBFGS(M; compact = nothing)`: how the operator is evaluated (bz_panoc_opts.lbfgs_compact) — `false` the two-loop recursion in the reference's order, `true` the compact representation, `nothing` (default) compact where the one-pass kernel applies"
 struct LBFGS
     memory::Int; compact::Union{Nothing,Bool}
@@ -147,6 +163,8 @@ lower_g!(d, g) = :generic
 abstract type IdentityLike <: Bazinga.SmoothFunction end
 lower_c!(d, c::IdentityLike) = (d.c_kind = 0)
 lower_c!(d, c::DenseAffine) = (d.c_kind = 1; d.c_A = pointer(c.At); d.c_b = pointer(c.b))
+lower_c!(d, c::SparseAffine) = (d.c_kind = 3; d.c_sp_rowptr = pointer(c.rowptr); d.c_sp_col = pointer(c.col);
+                                d.c_sp_val = pointer(c.val); d.c_sp_nnz = length(c.val); d.c_b = pointer(c.b))
 lower_c!(d, c) = :generic
 
 lower_D!(d, D::Bazinga.ZeroSet) = (d.D_kind = 0)
