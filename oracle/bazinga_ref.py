@@ -344,9 +344,11 @@ def _solve_lp_quasi_norm(x, p, a, gamma, u=None):
     ap = alpha * p
     zbar = (T(1) / (ap * (T(1) - p))) ** (T(1) / (p - T(2)))
     psi = zbar + ap * zbar ** (p - T(1))
-    act = (x > 0) & (psi < x)
+    # (the reference's early returns are `x <= 0 [|| u == 0]` and `psi >= x`: a NaN argument passes both, goes through the
+    # Newton loop and comes back as NaN — so the negated tests, not `x > 0` and `psi < x`)
+    act = ~(x <= 0) & ~(psi >= x)
     if box:
-        act &= (u != 0)
+        act &= ~(u == 0)
     if not np.any(act):
         return out
     xa = x[act]
