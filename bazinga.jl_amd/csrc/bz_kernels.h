@@ -1149,6 +1149,30 @@ k_gemv_t_mfma(const float* __restrict__ A, const float* __restrict__ v, float* _
     }
 }
 
+// jtv of one pack: the row-chunk partials of k_gemv_t / k_gemv_t_mfma added in their fixed order — chunk order, or rank
+// order when they are the ranks' — with eight loads in flight at a time (34 dependent load-add steps made the short finish
+// kernel 14.5 us long).  The one copy of this summation order: every finish kernel takes its jtv from here.
+template <class T>
+__device__ __forceinline__ Pack<T> gemv_t_fold(const T* __restrict__ part, int nchunks, int64_t pstride, int64_t i0, int cnt) {
+    Pack<T> j = ld(part, i0, cnt);
+    int k = 1;
+    for (; k + 7 < nchunks; k += 8) {
+        Pack<T> q[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) q[u] = ld(part + (int64_t)(k + u) * pstride, i0, cnt);
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+            for (int e = 0; e < PackN<T>::N; ++e) j.v[e] = j.v[e] + q[u].v[e];
+    }
+    for (; k < nchunks; ++k) {
+        Pack<T> q = ld(part + (int64_t)k * pstride, i0, cnt);
+#pragma unroll
+        for (int e = 0; e < PackN<T>::N; ++e) j.v[e] = j.v[e] + q.v[e];
+    }
+    return j;
+}
+
 // dlx = dfx + jtv with jtv = sum over row chunks (fixed order) ; f element-wise (Zero|DiagQuadratic)
 //   slot +0: sum f terms
 template <class T>
@@ -1158,24 +1182,7 @@ k_gemv_t_finish(const T* __restrict__ part, int nchunks, int64_t pstride, const 
     double acc[1] = {0.0};
     bz_for_chunks<T>(n, [&](const int64_t i0, const auto cnt_) {
         const int cnt = cnt_;      // compile-time PackN in the main loop, run-time only for the ragged last chunk
-        // (the partials in their fixed order — chunk order, or rank order when they are the ranks' — with eight loads in
-        // flight at a time: 34 dependent load-add steps made this short kernel 14.5 us long)
-        Pack<T> j = ld(part, i0, cnt);
-        int k = 1;
-        for (; k + 7 < nchunks; k += 8) {
-            Pack<T> q[8];
-#pragma unroll
-            for (int u = 0; u < 8; ++u) q[u] = ld(part + (int64_t)(k + u) * pstride, i0, cnt);
-#pragma unroll
-            for (int u = 0; u < 8; ++u)
-#pragma unroll
-                for (int e = 0; e < PackN<T>::N; ++e) j.v[e] = j.v[e] + q[u].v[e];
-        }
-        for (; k < nchunks; ++k) {
-            Pack<T> q = ld(part + (int64_t)k * pstride, i0, cnt);
-#pragma unroll
-            for (int e = 0; e < PackN<T>::N; ++e) j.v[e] = j.v[e] + q.v[e];
-        }
+        const Pack<T> j = gemv_t_fold(part, nchunks, pstride, i0, cnt);
         Pack<T> px = ld(x, i0, cnt), pq = splat(T(0)), pb = splat(T(0)), pg;
         if (P.f_kind == BZ_F_DIAG_QUADRATIC) { pq = ld(P.q, i0, cnt); pb = ld(P.b, i0, cnt); }
 #pragma unroll

@@ -8,6 +8,7 @@
 // provenance of the restatement.
 #include "bz_solver.h"
 #include "bz_spmv.h"
+#include "bz_als_dense.h"
 
 #include <hip/hip_ext.h>
 
@@ -198,8 +199,13 @@ template <class T> class Solver final : public SolverBase {
         }
         if (slack) {
             // ALS: the inner solver works on xs = [x; s]; from here on `n` is the length of that vector
-            if (d.c_kind != BZ_C_IDENTITY || (d.f_kind != BZ_F_ZERO && d.f_kind != BZ_F_DIAG_QUADRATIC))
-                throw Error(BZ_ERR_UNSUPPORTED, "slack (ALS) form: c = Identity and element-wise f only");
+            // (c = Identity: x_i pairs with s_i, element-wise f ; c = DenseAffine: halves of unequal length, f element-wise
+            // or dense, the generic kernel chain around two passes over A)
+            const bool f_elem = d.f_kind == BZ_F_ZERO || d.f_kind == BZ_F_DIAG_QUADRATIC;
+            const bool f_dense = d.f_kind == BZ_F_LEAST_SQUARES || d.f_kind == BZ_F_QUADRATIC;
+            if (!((d.c_kind == BZ_C_IDENTITY && f_elem) || (d.c_kind == BZ_C_DENSE_AFFINE && (f_elem || f_dense))))
+                throw Error(BZ_ERR_UNSUPPORTED, "slack (ALS) form: c = Identity with an element-wise f, or c = DenseAffine with an "
+                                                "element-wise or dense f (no Stencil5pt f, no callbacks)");
             if (nx % PackN<T>::N != 0)
                 throw Error(BZ_ERR_ARG, "slack (ALS) form: n must be a multiple of 16 bytes");
             if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "slack (ALS) form is not sharded");
@@ -235,8 +241,9 @@ template <class T> class Solver final : public SolverBase {
         dense_f = d.f_kind == BZ_F_LEAST_SQUARES || d.f_kind == BZ_F_QUADRATIC;
         if (dense_f) {
             if (!d.f_A || !d.f_b || d.f_rows <= 0) throw Error(BZ_ERR_ARG, "dense f needs its matrix, vector and row count");
-            if (d.f_kind == BZ_F_QUADRATIC && d.f_rows != n) throw Error(BZ_ERR_ARG, "Quadratic: Q must be n-by-n");
-            if (d.c_kind != BZ_C_IDENTITY) throw Error(BZ_ERR_UNSUPPORTED, "dense f with a dense c");
+            if (d.f_kind == BZ_F_QUADRATIC && d.f_rows != nx) throw Error(BZ_ERR_ARG, "Quadratic: Q must be n-by-n");
+            if (d.c_kind != BZ_C_IDENTITY && d.c_kind != BZ_C_DENSE_AFFINE)
+                throw Error(BZ_ERR_UNSUPPORTED, "dense f needs c = Identity or c = DenseAffine");
             if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "dense f is not sharded");
         }
         if (d.f_kind == BZ_F_STENCIL5) {
@@ -287,35 +294,42 @@ template <class T> class Solver final : public SolverBase {
         const int64_t nychunks = (ny + PackN<T>::N - 1) / PackN<T>::N;
         grid_y = (int)std::min<int64_t>(grid, std::max<int64_t>(1, (nychunks + BLOCK - 1) / BLOCK));
         if (d.c_kind == BZ_C_IDENTITY) grid_y = grid;
+        grid_x = grid;
+        slack_dense = slack && d.c_kind == BZ_C_DENSE_AFFINE;
         if (slack) {
+            // kernels over the x half alone (and, with c = Identity, over the index both halves share)
             const int64_t c2 = (nx / PackN<T>::N + BLOCK - 1) / BLOCK;
-            grid_y = (int)std::min<int64_t>(PSTRIDE, std::max<int64_t>(1, c2));
+            grid_x = (int)std::min<int64_t>(PSTRIDE, std::max<int64_t>(1, c2));
+            if (!slack_dense) grid_y = grid_x;
+            lifted_sections(nx, ny, lgx_, lgs_);
         }
         npad = ((n + PackN<T>::N - 1) / PackN<T>::N) * PackN<T>::N;
+        npadx = ((nx + PackN<T>::N - 1) / PackN<T>::N) * PackN<T>::N;      // (the matrices of f and c have nx columns)
         if (dense_f) {
             frows = d.f_rows;
-            FA_.alloc((size_t)frows * n);
-            BZ_HIP(hipMemcpyAsync(FA_.p, d.f_A, (size_t)frows * n * sizeof(T), hipMemcpyDefault, ctx->stream));
+            FA_.alloc((size_t)frows * nx);
+            BZ_HIP(hipMemcpyAsync(FA_.p, d.f_A, (size_t)frows * nx * sizeof(T), hipMemcpyDefault, ctx->stream));
             BZ_HIP(hipStreamSynchronize(ctx->stream));
-            upload(fb_, d.f_b, d.f_kind == BZ_F_LEAST_SQUARES ? frows : n);
-            FR_.alloc(std::max<int64_t>(frows, n));
+            upload(fb_, d.f_b, d.f_kind == BZ_F_LEAST_SQUARES ? frows : nx);
+            FR_.alloc(std::max<int64_t>(frows, nx));
             fscale = d.f_kind == BZ_F_LEAST_SQUARES ? T(0.5) : T(1);
             if (d.f_kind == BZ_F_LEAST_SQUARES) {
-                DFX_.alloc(npad);
-                plan_chunks(frows, f_rows_per_chunk, f_nrowchunks);
-                GT_.alloc((size_t)f_nrowchunks * npad);
+                // (f's matrix has its own chunk plan and its own partials: f_rows, ny and n are unrelated)
+                DFX_.alloc(npadx);
+                plan_chunks(frows, nx, f_rows_per_chunk, f_nrowchunks);
+                FGT_.alloc((size_t)f_nrowchunks * npadx);
             }
         }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
-            A_.alloc((size_t)ny * n);
-            BZ_HIP(hipMemcpyAsync(A_.p, d.c_A, (size_t)ny * n * sizeof(T), hipMemcpyDefault, ctx->stream));
+            A_.alloc((size_t)ny * nx);
+            BZ_HIP(hipMemcpyAsync(A_.p, d.c_A, (size_t)ny * nx * sizeof(T), hipMemcpyDefault, ctx->stream));
             BZ_HIP(hipStreamSynchronize(ctx->stream));
             upload(cb_, d.c_b, ny);
             CX_.alloc(ny); YU_.alloc(ny);
-            plan_chunks(ny, rows_per_chunk, nrowchunks);
+            plan_chunks(ny, nx, rows_per_chunk, nrowchunks);
             x_replicated = ctx->nranks > 1;
             dense_fused_plan();
-            GT_.alloc((size_t)std::max(nrowchunks, df_groups_) * npad);
+            GT_.alloc((size_t)std::max(nrowchunks, df_groups_) * npadx);
             if (x_replicated) JL_.alloc(npad);
             affine_ok_ = !x_replicated && !slack && (d.D_kind == BZ_D_ZERO || d.D_kind == BZ_D_FREE) &&
                          (d.f_kind == BZ_F_ZERO || d.f_kind == BZ_F_DIAG_QUADRATIC);
@@ -684,15 +698,17 @@ template <class T> class Solver final : public SolverBase {
         copy_in(TMP_.p, x0, nx);
         // prox!(x, gFun, x0, eps(T)) ; objx = f(x) + gFun.gz              als.jl:41-42
         mv(2 + pstreams(false, false, true), nx);
-        if (lp_g) launch(C_FB, k_fbstep<T, true>, grid_y, (const T*)TMP_.p, (const T*)nullptr, epsT, P, xs, (T*)nullptr, nx, parts_.p, (int)SL_GSUM);
-        else launch(C_FB, k_fbstep<T, false>, grid_y, (const T*)TMP_.p, (const T*)nullptr, epsT, P, xs, (T*)nullptr, nx, parts_.p, (int)SL_GSUM);
-        for (int k = 0; k < 3; ++k) slot_n[SL_GSUM + k] = grid_y;
+        if (lp_g) launch(C_FB, k_fbstep<T, true>, grid_x, (const T*)TMP_.p, (const T*)nullptr, epsT, P, xs, (T*)nullptr, nx, parts_.p, (int)SL_GSUM);
+        else launch(C_FB, k_fbstep<T, false>, grid_x, (const T*)TMP_.p, (const T*)nullptr, epsT, P, xs, (T*)nullptr, nx, parts_.p, (int)SL_GSUM);
+        for (int k = 0; k < 3; ++k) slot_n[SL_GSUM + k] = grid_x;
         fvalue(xs, SL_AUX);
         auto v0 = collect({SL_GSUM, SL_AUX}, 0u);
         T objx = f_value(v0[1]) + g_value(v0[0]);
         // eval!(cx,c,x); proj!(s,D,cx); default_penalty_parameter!          als.jl:43-45   (s lands in xs[nx:])
+        if (slack_dense) eval_c(xs);                                 // cx = A x - b -> CX_ ; c = Identity: cx is x itself
         mv(3 + (P.D_lo_vec ? 1 : 0) + (P.D_hi_vec ? 1 : 0), ny);
-        launch(C_MISC, k_penalty_init<T>, grid_y, (const T*)xs, P, std::max(1.0, (double)objx), xs + nx, mu_.p, ny);
+        launch(C_MISC, k_penalty_init<T>, grid_y, slack_dense ? (const T*)CX_.p : (const T*)xs, P, std::max(1.0, (double)objx),
+               xs + nx, mu_.p, ny);
         copy_in(ymul_.p, y0, ny);
         double norm_res_prim = 0, norm_res_prim_old = 0;
         bool have_old = false, have_res = false;
@@ -716,9 +732,16 @@ template <class T> class Solver final : public SolverBase {
             tot_inner += sub_it;
             const bool sub_solved = sub_it < ao.subsolver_maxit;
             // y += (cx - s)/mu ; ||cx - s||_inf                      als.jl:82-87
-            mv(5, nx);
-            launch(C_MISC, k_dual_update_slack<T>, grid_y, (const T*)xs, (const T*)mu_.p, ymul_.p, nx, parts_.p,
-                   (int)SL_OUTER);
+            if (slack_dense) {
+                eval_c(xs);                                          // eval!(cx, c, x) at the subsolver's solution   als.jl:82
+                mv(5, ny); nm("k_dual_update_slack_rows");
+                launch(C_MISC, k_dual_update_slack_rows<T>, grid_y, (const T*)CX_.p, (const T*)(xs + nx), (const T*)mu_.p,
+                       ymul_.p, ny, parts_.p, (int)SL_OUTER);
+            } else {
+                mv(5, nx);
+                launch(C_MISC, k_dual_update_slack<T>, grid_y, (const T*)xs, (const T*)mu_.p, ymul_.p, nx, parts_.p,
+                       (int)SL_OUTER);
+            }
             slot_n[SL_OUTER] = grid_y;
             gather(SL_OUTER, 1, 1u);
             auto r = collect({SL_OUTER}, 1u);
@@ -760,6 +783,15 @@ template <class T> class Solver final : public SolverBase {
     const CreateKnobs cenv_;                 // the knobs read when the problem was created
     BeginKnobs env_;                         // ... at the last bz_panoc_begin (at creation before the first)
     int grid = 1, grid_y = 1;
+    int grid_x = 1;                          // kernels over x alone (== grid unless slack)
+    bool slack_dense = false;                // slack form with c = DenseAffine: halves of unequal length
+    int lgx_ = 1, lgs_ = 1;                  // k_fbstep_lifted: workgroups of its x section and of its s section
+    // the sections of a launch over the lifted vector: a function of (nx, ny) alone, so that the partial sums are too
+    static void lifted_sections(int64_t nx_, int64_t ny_, int& gx, int& gs) {
+        constexpr int64_t N = PackN<T>::N;
+        gx = (int)std::min<int64_t>(PSTRIDE / 2, std::max<int64_t>(1, ((nx_ + N - 1) / N + BLOCK - 1) / BLOCK));
+        gs = (int)std::min<int64_t>(PSTRIDE / 2, std::max<int64_t>(1, ((ny_ + N - 1) / N + BLOCK - 1) / BLOCK));
+    }
     ElemParams<T> P;
     DBuf<T> q_, b_, gu_, glo_, ghi_, dlo_, dhi_, mu_, muy_, ymul_, sproj_;
     // x lives in a ring long enough to keep the last CM+1 iterates alive (history as iterates, see xr_run_): CM+1
@@ -768,7 +800,7 @@ template <class T> class Solver final : public SolverBase {
     DBuf<T> X_[NXR], RES_[NRR], Z_[2], GX_, GZ_, D_, TMP_;
     DBuf<T> A_, cb_, CX_, YU_, GT_;          // DenseAffine c: A[ny][n], b, c(x), yupd, A'v row-chunk partials
     int rows_per_chunk = 1, nrowchunks = 1;
-    DBuf<T> FA_, fb_, FR_, DFX_;             // dense f: matrix, vector, residual / Qx, gradient of f
+    DBuf<T> FA_, fb_, FR_, DFX_, FGT_;       // dense f: matrix, vector, residual / Qx, gradient of f, A_f'r row-chunk partials
     bool dense_f = false, lp_g = false;
     // generic oracles (host callbacks): host mirrors of the vectors the callbacks read and write
     bool generic_ = false;
@@ -834,7 +866,7 @@ template <class T> class Solver final : public SolverBase {
         fill_slot(slot0 + 1, dot);
         fill_slot(slot0 + 2, ss);
     }
-    int64_t frows = 0, npad = 0;
+    int64_t frows = 0, npad = 0, npadx = 0;
     int f_rows_per_chunk = 1, f_nrowchunks = 1;
     T fscale = T(1);                         // f(x) = fscale * (sum of the f partials)
     // persistent two-loop
@@ -947,7 +979,7 @@ template <class T> class Solver final : public SolverBase {
     int b_rpc_ = 1, b_nch_ = 1;
     // Broyden: D_ = H res (the caller forms x_d = x - D_ through the returned tail)
     TailArgs<T> broyden_dir() {
-        gemv_rows(HB_.p, n, RES_[rc].p, (const T*)nullptr, D_.p);
+        gemv_rows(HB_.p, n, n, RES_[rc].p, (const T*)nullptr, D_.p);
         TailArgs<T> t;
         std::memset(&t, 0, sizeof(t));
         t.alphas = alphas_.p;
@@ -964,8 +996,8 @@ template <class T> class Solver final : public SolverBase {
     void broyden_update() {
         const T* sv = S_[spare].p;
         const T* yv = Y_[spare].p;
-        gemv_rows(HB_.p, n, yv, (const T*)nullptr, BHy_.p);
-        gemv_cols(HB_.p, n, sv, b_rpc_, b_nch_);
+        gemv_rows(HB_.p, n, n, yv, (const T*)nullptr, BHy_.p);
+        gemv_cols(HB_.p, n, n, sv, b_rpc_, b_nch_, GT_.p, npad);
         {
             ElemParams<T> Pz = P;
             Pz.f_kind = BZ_F_ZERO;
@@ -1375,7 +1407,8 @@ template <class T> class Solver final : public SolverBase {
     void dense_fused_plan() {
         df_kp_ = 0;
         constexpr int N = PackN<T>::N;
-        if (desc.c_kind != BZ_C_DENSE_AFFINE || x_replicated || slack || (n % N) != 0) return;
+        // (a dense f beside the dense c, and the slack form: the two-kernel form — no row epilogue for them in k_dense_fused)
+        if (desc.c_kind != BZ_C_DENSE_AFFINE || x_replicated || slack || dense_f || (n % N) != 0) return;
         if (desc.D_kind >= BZ_D_VC_PAIRS) return;
         const int64_t npk = n / N;
         // KP packs per row and lane: kp_full fills a CU's registers with ONE workgroup's ring of tiles — the fewest slices per
@@ -1702,6 +1735,16 @@ template <class T> class Solver final : public SolverBase {
     // common kinds keep their register budget
     void fbstep(const T* x, const T* g, T gam, T* z, T* res, int slot0) {
         if (generic_) { fbstep_generic(x, g, gam, z, res, slot0); return; }
+        if (slack_dense) {
+            // one launch over the lifted vector, a section per half (k_fbstep_lifted)
+            for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = lgx_ + lgs_;
+            const int vs = 1 + (g ? 1 : 0) + 1 + (res ? 1 : 0);
+            mv(vs + pstreams(false, false, true), nx); mv(vs + (P.D_lo_vec ? 1 : 0) + (P.D_hi_vec ? 1 : 0), ny);
+            nm(lp_g ? "k_fbstep_lifted<LP=1>" : "k_fbstep_lifted<LP=0>");
+            if (lp_g) launch(C_FB, k_fbstep_lifted<T, true>, lgx_ + lgs_, x, g, gam, P, z, res, nx, ny, lgx_, lgs_, parts_.p, slot0);
+            else launch(C_FB, k_fbstep_lifted<T, false>, lgx_ + lgs_, x, g, gam, P, z, res, nx, ny, lgx_, lgs_, parts_.p, slot0);
+            return;
+        }
         if (slack) {
             for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = grid_y;
             mv(2 * (1 + (g ? 1 : 0) + 1 + (res ? 1 : 0)) + pstreams(false, false, true) + (P.D_lo_vec ? 1 : 0) + (P.D_hi_vec ? 1 : 0), nx);
@@ -1903,60 +1946,61 @@ template <class T> class Solver final : public SolverBase {
 
     // gradient!(dlx, al, x) on the device; partials -> slot0 (f terms), slot0+1 (t^2/mu)
     // row chunks of the transposed product: enough blocks to fill the chip, fixed summation order
-    void plan_chunks(int64_t rows, int& rpc, int& nch) const {
-        const int64_t colblocks = std::max<int64_t>(1, (n / PackN<T>::N + BLOCK - 1) / BLOCK);
+    void plan_chunks(int64_t rows, int64_t cols, int& rpc, int& nch) const {
+        const int64_t colblocks = std::max<int64_t>(1, (cols / PackN<T>::N + BLOCK - 1) / BLOCK);
         const int64_t chunks = std::max<int64_t>(1, std::min<int64_t>(rows, (2048 + colblocks - 1) / colblocks));
         rpc = (int)((rows + chunks - 1) / chunks);
         nch = (int)((rows + rpc - 1) / rpc);
     }
-    // out = M p - b (b may be null): M[rows][n] row-major
-    void gemv_rows(const T* M, int64_t rows, const T* p, const T* b, T* out) {
-        mv((double)rows, n); mv(b ? 2 : 1, rows); mv(1, n);      // the matrix once, x, b and the result
+    // out = M p - b (b may be null): M[rows][cols] row-major
+    void gemv_rows(const T* M, int64_t rows, int64_t cols, const T* p, const T* b, T* out) {
+        mv((double)rows, cols); mv(b ? 2 : 1, rows); mv(1, cols);      // the matrix once, x, b and the result
         nm("k_gemv_n");
-        launch(C_GEMV, k_gemv_n<T>, (int)std::min<int64_t>(rows, 65535), M, p, b, out, rows, n);
+        launch(C_GEMV, k_gemv_n<T>, (int)std::min<int64_t>(rows, 65535), M, p, b, out, rows, cols);
     }
-    // GT_ partials of M' v over row chunks.  fp32 with n % 64 == 0 runs on the matrix cores
-    // (v_mfma_f32_16x16x4_f32), everything else on the vector ALUs; both are bound by the bytes of M.
-    void gemv_cols(const T* M, int64_t rows, const T* v, int rpc, int nch) {
+    // partials of M' v over row chunks (M[rows][cols]) into part[nch][pstride].  fp32 with cols % 64 == 0 runs on the
+    // matrix cores (v_mfma_f32_16x16x4_f32), everything else on the vector ALUs; both are bound by the bytes of M.
+    void gemv_cols(const T* M, int64_t rows, int64_t cols, const T* v, int rpc, int nch, T* part, int64_t pstride) {
         if constexpr (std::is_same<T, float>::value) {
-            if (n % 64 == 0 && !env_.gemv_valu) {
-                mv((double)rows, n); mv(1, rows); mv(nch, npad);      // the matrix once, v, the row-chunk partials
+            if (cols % 64 == 0 && !env_.gemv_valu) {
+                mv((double)rows, cols); mv(1, rows); mv(nch, pstride);      // the matrix once, v, the row-chunk partials
                 nm("k_gemv_t_mfma");
-                launch2d(C_GEMV_MFMA, k_gemv_t_mfma, (int)((n / 64 + WAVES - 1) / WAVES), nch, (const float*)M,
-                         (const float*)v, (float*)GT_.p, rows, n, rpc, npad);
+                launch2d(C_GEMV_MFMA, k_gemv_t_mfma, (int)((cols / 64 + WAVES - 1) / WAVES), nch, (const float*)M,
+                         (const float*)v, (float*)part, rows, cols, rpc, pstride);
                 return;
             }
         }
-        const bool aligned = (n % PackN<T>::N) == 0;
-        const int colblocks = (int)(((aligned ? n / PackN<T>::N : n) + BLOCK - 1) / BLOCK);
-        mv((double)rows, n); mv(1, rows); mv(nch, npad); nm("k_gemv_t");
-        launch2d(C_GEMV, k_gemv_t<T>, colblocks, nch, M, v, GT_.p, rows, n, rpc, npad);
+        const bool aligned = (cols % PackN<T>::N) == 0;
+        const int colblocks = (int)(((aligned ? cols / PackN<T>::N : cols) + BLOCK - 1) / BLOCK);
+        mv((double)rows, cols); mv(1, rows); mv(nch, pstride); nm("k_gemv_t");
+        launch2d(C_GEMV, k_gemv_t<T>, colblocks, nch, M, v, part, rows, cols, rpc, pstride);
     }
     // eval!(cx, c, x) for the dense constraint
     void eval_c(const T* x) {
         if (desc.c_kind == BZ_C_SPARSE_AFFINE) { spmv_yupd(x, CX_.p, nullptr, (int)SL_SCRATCH); return; }
-        gemv_rows(A_.p, ny, x, cb_.p, CX_.p);
+        gemv_rows(A_.p, ny, nx, x, cb_.p, CX_.p);
     }
     // dense f: leaves what k_algrad_elem / k_fvalue_elem need in FR_ / DFX_ and the f partials in slot0
     //   LeastSquares: r = A x - b ; slot0 <- <r,r> ; DFX = A' r        (ProximalOperators: 0.5||Ax-b||^2)
     //   Quadratic:    FR = Q x (value and gradient finished element-wise)
     void dense_f_eval(const T* x, int slot0, bool need_grad) {
+        // (x: a vector of nx elements — the x half of the lifted vector in the slack form)
         if (desc.f_kind == BZ_F_LEAST_SQUARES) {
-            gemv_rows(FA_.p, frows, x, fb_.p, FR_.p);
+            gemv_rows(FA_.p, frows, nx, x, fb_.p, FR_.p);
             const int gm = (int)std::min<int64_t>(grid, std::max<int64_t>(1, (frows / PackN<T>::N + BLOCK) / BLOCK));
             mv(1, frows);
             launch(C_MISC, k_dot<T>, gm, (const T*)FR_.p, (const T*)FR_.p, T(1), frows, parts_.p, slot0);
             slot_n[slot0] = gm;
             if (need_grad) {
-                gemv_cols(FA_.p, frows, FR_.p, f_rows_per_chunk, f_nrowchunks);
+                gemv_cols(FA_.p, frows, nx, FR_.p, f_rows_per_chunk, f_nrowchunks, FGT_.p, npadx);
                 ElemParams<T> Pz = P;
                 Pz.f_kind = BZ_F_ZERO;
-                mv(f_nrowchunks + 2);
-                launch(C_MISC, k_gemv_t_finish<T>, grid, (const T*)GT_.p, f_nrowchunks, npad, x, Pz, DFX_.p, n,
+                mv(f_nrowchunks + 2, nx);
+                launch(C_MISC, k_gemv_t_finish<T>, grid_x, (const T*)FGT_.p, f_nrowchunks, npadx, x, Pz, DFX_.p, nx,
                        parts_.p, (int)SL_SCRATCH);
             }
         } else {
-            gemv_rows(FA_.p, n, x, (const T*)nullptr, FR_.p);
+            gemv_rows(FA_.p, nx, nx, x, (const T*)nullptr, FR_.p);
         }
     }
     void algrad(const T* x, T* grad, int slot0) {
@@ -1978,13 +2022,30 @@ template <class T> class Solver final : public SolverBase {
             return;
         }
         if (desc.c_kind == BZ_C_DENSE_AFFINE) {
+            // the two-kernel form: one pass over A for A x, one ny-length kernel, one pass over A for A' yupd, the finish
+            // (x: nx elements — the x half of the lifted vector in the slack form, whose s half follows it)
+            slot_n[slot0] = grid_x; slot_n[slot0 + 1] = grid_y;
+            // dense f: its own products first (grad f -> DFX_ / Q x -> FR_ ; LeastSquares: <r, r> -> slot0, with its own count)
+            if (dense_f) dense_f_eval(x, slot0, true);
             eval_c(x);                                                        // cx = A x - b
             if (cx_keep_) BZ_HIP(hipMemcpyAsync(cx_keep_, CX_.p, ny * sizeof(T), hipMemcpyDeviceToDevice, ctx->stream));
-            mv(2 + pstreams(false, true, false), ny);
-            launch(C_MISC, k_yupd<T>, grid_y, (const T*)CX_.p, P, YU_.p, ny, parts_.p, slot0 + 1);
-            slot_n[slot0] = grid; slot_n[slot0 + 1] = grid_y;
-            gemv_cols(A_.p, ny, YU_.p, rows_per_chunk, nrowchunks);           // jtv = A' yupd (row-chunk partials)
-            if (x_replicated) {
+            if (slack) {
+                // w = (cx + mu y) - s, sum w^2/mu, yupd = y + (cx - s)/mu and dFxs[nx:] = -yupd in one pass
+                mv(5 + 1 + (grad ? 1 : 0), ny); nm("k_algrad_slack_rows");
+                launch(C_ALGRAD, k_algrad_slack_rows<T>, grid_y, (const T*)CX_.p, x + nx, (const T*)mu_.p, (const T*)muy_.p,
+                       (const T*)ymul_.p, YU_.p, grad ? grad + nx : (T*)nullptr, ny, parts_.p, slot0 + 1);
+            } else {
+                mv(2 + pstreams(false, true, false), ny);
+                launch(C_MISC, k_yupd<T>, grid_y, (const T*)CX_.p, P, YU_.p, ny, parts_.p, slot0 + 1);
+            }
+            gemv_cols(A_.p, ny, nx, YU_.p, rows_per_chunk, nrowchunks, GT_.p, npadx);      // jtv = A' yupd (row-chunk partials)
+            if (dense_f) {
+                // dlx = dfx + jtv with the dense f's gradient (k_algrad_elem's modes 1 and 2)
+                const bool ls = desc.f_kind == BZ_F_LEAST_SQUARES;
+                mv(nrowchunks + 3 + (ls ? 0 : 1), nx); nm("k_gemv_t_finish_ext");
+                launch(C_MISC, k_gemv_t_finish_ext<T>, grid_x, (const T*)GT_.p, nrowchunks, npadx, x, P, ls ? 1 : 2,
+                       ls ? (const T*)DFX_.p : (const T*)FR_.p, grad, nx, parts_.p, slot0);
+            } else if (x_replicated) {
                 // this rank's rows only: fold the chunks, sum over the ranks (rank order), then finish
                 ElemParams<T> Pz = P;
                 Pz.f_kind = BZ_F_ZERO;
@@ -1995,8 +2056,8 @@ template <class T> class Solver final : public SolverBase {
                 mv(ctx->nranks + 2 + pstreams(true, false, false));
                 launch(C_MISC, k_gemv_t_finish<T>, grid, chunks, ctx->nranks, npad, x, P, grad, n, parts_.p, slot0);
             } else {
-                mv(nrowchunks + 2 + pstreams(true, false, false));
-                launch(C_MISC, k_gemv_t_finish<T>, grid, (const T*)GT_.p, nrowchunks, npad, x, P, grad, n, parts_.p, slot0);
+                mv(nrowchunks + 2 + pstreams(true, false, false), nx);
+                launch(C_MISC, k_gemv_t_finish<T>, grid_x, (const T*)GT_.p, nrowchunks, npadx, x, P, grad, nx, parts_.p, slot0);
             }
             gather(slot0, 2, 0u, 2u);         // slot0: f terms (x-space) ; slot0 + 1: penalty terms (this rank's rows)
             return;
@@ -2034,9 +2095,15 @@ template <class T> class Solver final : public SolverBase {
         }
         slot_n[slot0] = grid;
         if (slack) {      // f on the x part only
-            slot_n[slot0] = grid_y;
-            mv(1 + pstreams(true, false, false), nx);
-            launch(C_MISC, k_fvalue_elem<T>, grid_y, x, P, nx, parts_.p, slot0, (const T*)nullptr);
+            slot_n[slot0] = grid_x;
+            if (dense_f) {
+                dense_f_eval(x, slot0, false);
+                if (desc.f_kind == BZ_F_QUADRATIC)
+                    { mv(3, nx); launch(C_MISC, k_fvalue_elem<T>, grid_x, x, P, nx, parts_.p, slot0, (const T*)FR_.p); }
+            } else {
+                mv(1 + pstreams(true, false, false), nx);
+                launch(C_MISC, k_fvalue_elem<T>, grid_x, x, P, nx, parts_.p, slot0, (const T*)nullptr);
+            }
             gather(slot0, 1, 0u);
             return;
         }
@@ -2471,7 +2538,7 @@ template <class T> class Solver final : public SolverBase {
             broyden_theta_bar_ = (T)o.broyden_theta_bar;
             if (!HB_.p) {
                 HB_.alloc((size_t)n * n); BHy_.alloc(npad); BsH_.alloc(npad);
-                plan_chunks(n, b_rpc_, b_nch_);
+                plan_chunks(n, n, b_rpc_, b_nch_);
                 if (GT_.n < (size_t)b_nch_ * npad) GT_.alloc((size_t)b_nch_ * npad);
             }
         }

@@ -284,6 +284,8 @@ def alps(f, g, c, D, x0, y0, *, tol=None, tol_prim=None, tol_dual=None, inner_to
                 st.inner_tol, st.norm_res_prim if st.tot_it else None, s, mu)
 
     # ---- host outer loop, device subsolver (line numbers: src/algorithms/alps.jl)
+    if _slack and warm_start:           # (refused before the loop's first device call)
+        raise UnsupportedOracle("warm_start with the host outer loop of als: use resident=True")
     start_time = time.time()
     x = np.empty_like(x0)                                       # :31-35
     y = np.empty_like(y0)
@@ -307,8 +309,6 @@ def alps(f, g, c, D, x0, y0, *, tol=None, tol_prim=None, tol_dual=None, inner_to
     norm_res_prim = None
     norm_res_prim_old = None
     if _slack:
-        if warm_start:
-            raise UnsupportedOracle("warm_start with the host outer loop of als: use resident=True")
         return _als_host_loop(f, g, c, D, x, y, cx, s, mu, gFun, objx, tol_prim, tol_dual, inner_tol, maxit,
                               theta_penalty, kappa_penalty, kappa_tol, verbose, dual_safeguard, subsolver,
                               subsolver_maxit, start_time)

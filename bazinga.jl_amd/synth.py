@@ -111,3 +111,36 @@ def budget_bands(n: int, m: int, dtype=np.float64):
     return {"indptr": indptr, "indices": indices, "data": data, "b": b, "n": n, "ny": m + 1, "lo": lo, "hi": hi,
             "xfeas": xfeas.astype(dtype), "q": (0.5 + uniform(1, n)).astype(dtype),
             "fb": (2.0 * uniform(2, n) - 1.0).astype(dtype)}
+
+
+def portfolio(n: int, dtype=np.float64, rank: int | None = None):
+    """A stand-in for the absent demo/portfolio_data (demo/portfolio.jl:70-91: Q, rho, mu, ub), from the uniform stream:
+
+        Q  = F F' + diag(d), F n-by-r with F_ij = 0.2 (2 u1 - 1) (r = max(1, n div 10)), d_i = 0.01 + 0.04 u2
+             (symmetric positive definite: a low-rank factor model plus specific risk);
+        mu = 0.1 u3 in [0, 0.1], the expected returns;
+        ub = (2 + 6 u4)/n, so that sum(ub) >= 2 and the budget sum(x) = 1 fits under the bounds;
+        rho a quarter of the way from the return of xfeas = ub/sum(ub) to the best return the set allows (the greedy
+            fill of the largest mu_i up to ub_i): {x : sum(x) = 1, mu'x >= rho, 0 <= x <= ub} contains the same convex
+            combination of the two points, so it is non-empty and the return constraint is active for a minimum-risk x.
+
+    Also returns the demo's constraint as matrices: c(x) = A x - b with A = [mu'; e'], b = 0 (demo/portfolio.jl:43-56) and
+    D = [rho, inf) x {1} as vector bounds lo, hi (:58-66)."""
+    r = max(1, n // 10) if rank is None else int(rank)
+    F = 0.2 * (2.0 * uniform(1, n * r) - 1.0).reshape(n, r)
+    d = 0.01 + 0.04 * uniform(2, n)
+    Q = F @ F.T + np.diag(d)
+    Q = 0.5 * (Q + Q.T)
+    mu = 0.1 * uniform(3, n)
+    ub = (2.0 + 6.0 * uniform(4, n)) / n
+    xfeas = ub / ub.sum()
+    order = np.argsort(-mu, kind="stable")
+    room = 1.0 - np.concatenate(([0.0], np.cumsum(ub[order])[:-1]))
+    xbest = np.zeros(n)
+    xbest[order] = np.clip(room, 0.0, ub[order])
+    rho = 0.75 * float(mu @ xfeas) + 0.25 * float(mu @ xbest)
+    A = np.stack([mu, np.ones(n)])
+    return {"Q": Q.astype(dtype), "mu": mu.astype(dtype), "ub": ub.astype(dtype), "rho": float(np.dtype(dtype).type(rho)),
+            "A": np.ascontiguousarray(A.astype(dtype)), "b": np.zeros(2, dtype),
+            "lo": np.array([rho, 1.0], dtype), "hi": np.array([np.inf, 1.0], dtype),
+            "xfeas": (0.75 * xfeas + 0.25 * xbest).astype(dtype)}

@@ -167,7 +167,13 @@ typedef struct {
     int32_t dtype;                 /* BZ_F64 | BZ_F32                                 */
     int32_t f_kind, g_kind, c_kind, D_kind;
     int32_t slack;                 /* 0: ALPS subproblem on x (auglagfun.jl); 1: ALS subproblem on
-                                      xs = [x; s] of length n + ny (auglagfunslack.jl)      */
+                                      xs = [x; s] of length n + ny (auglagfunslack.jl).  The slack form
+                                      takes (f, c) = (Zero | DiagQuadratic, Identity), where ny == n, and
+                                      (Zero | DiagQuadratic | LeastSquares | Quadratic, DenseAffine), where
+                                      ny is arbitrary; n must be a whole number of 16-byte packs (2 fp64 /
+                                      4 fp32 elements) so that s starts aligned.  Refused with slack = 1:
+                                      SparseAffine, Stencil5pt f, LeastSquares / Quadratic with c = Identity,
+                                      pairwise D, callbacks, more than one rank */
     int64_t n;                     /* length of x (local shard)                       */
     int64_t ny;                    /* length of y / c(x) (local shard)                */
     /* f */
@@ -384,7 +390,9 @@ int bz_alps_solve(bz_problem* p, const bz_alps_opts* ao, const bz_panoc_opts* po
                   void* x, void* y, void* s, void* mu, bz_alps_stats* stats);
 
 /* Bazinga.als (src/algorithms/als.jl:7-120), the slack-variable sibling: same arguments and outputs;
- * the problem must have been created with desc.slack = 1.                                            */
+ * the problem must have been created with desc.slack = 1 (see bz_problem_desc.slack for the (f, c) kinds the
+ * slack form takes).  c = Identity: the one-pass kernels on the index x_i and s_i share.  c = DenseAffine
+ * (x0 of length n, y0 / s / mu of length ny): the generic kernel chain around two passes over A per AL gradient. */
 int bz_als_solve(bz_problem* p, const bz_alps_opts* ao, const bz_panoc_opts* po,
                  const void* x0, const void* y0,
                  void* x, void* y, void* s, void* mu, bz_alps_stats* stats);

@@ -257,8 +257,12 @@ end
 mutable struct Problem
     h::Ptr{Cvoid}
     keep::Any
-    function Problem(f, g, c, D, n, ny, ::Type{T}) where {T}
-        d = ProblemDesc(dtype = dtype_code(T), n = n, ny = ny)
+    # slack = true: the ALS form on xs = [x; s] (auglagfunslack.jl).  The library takes it for c = identity with an
+    # element-wise f (Zero, DiagQuadratic; ny == n) and for c = DenseAffine with f Zero, DiagQuadratic, LeastSquares or
+    # Quadratic (ny arbitrary, n a whole number of 16-byte packs); a sparse c, the stencil f, pairwise D and generic
+    # oracles are BZ_ERR_UNSUPPORTED there
+    function Problem(f, g, c, D, n, ny, ::Type{T}; slack::Bool = false) where {T}
+        d = ProblemDesc(dtype = dtype_code(T), n = n, ny = ny, slack = Int32(slack))
         tmp = (lower_f!(d, f), lower_g!(d, g), lower_c!(d, c), lower_D!(d, D))      # temporaries the descriptor points into
         keep = any(t -> t === :generic, tmp) ? lower_generic!(d, f, g, c, D, T) : nothing
         h = Ref{Ptr{Cvoid}}(C_NULL)
@@ -290,8 +294,11 @@ end
 # one device problem per live AugLagFun; the entry (and, through the finalizer, the device buffers) goes with the functor
 const _problems = WeakKeyDict{Any,Problem}()
 
-"`solver(f = alFun, g = gFun, x0 = x) -> (sol, it)`   (alps.jl:66)"
-function (s::PANOCplusHIP)(; f::Bazinga.AugLagFun, g::Bazinga.NonsmoothCostFun, x0::AbstractVector{T}) where {T}
+"`solver(f = alFun, g = gFun, x0 = x) -> (sol, it)`   (alps.jl:66; als.jl:72 with the slack functors).  Keyword arguments
+take no part in dispatch: the one keyword method hands over to `_solve`, which dispatches on the functor types."
+(s::PANOCplusHIP)(; f, g, x0) = _solve(s, f, g, x0)
+
+function _solve(s::PANOCplusHIP, f::Bazinga.AugLagFun, g::Bazinga.NonsmoothCostFun, x0::AbstractVector{T}) where {T}
     p = get!(() -> Problem(f.f, g.g, f.c, f.D, length(x0), length(f.y), T), _problems, f)
     mu = convert(Vector{T}, f.mu); y = convert(Vector{T}, f.y)
     check(ccall((:bz_problem_set_multipliers, lib), Cint, (Ptr{Cvoid}, Ptr{T}, Ptr{T}), p.h, mu, y), p)
@@ -302,6 +309,19 @@ function (s::PANOCplusHIP)(; f::Bazinga.AugLagFun, g::Bazinga.NonsmoothCostFun, 
     g.gz = T(st[].g_z)
     g.gamma = st[].gamma
     return x, Int(st[].iters)
+end
+
+# the slack functors of auglagfunslack.jl (als.jl:72)
+function _solve(s::PANOCplusHIP, f::Bazinga.AugLagFunSlack, g::Bazinga.NonsmoothCostFunSlack, x0::AbstractVector{T}) where {T}
+    p = get!(() -> Problem(f.f, g.g, f.c, g.D, f.nx, f.ny, T; slack = true), _problems, f)
+    mu = convert(Vector{T}, f.mu); y = convert(Vector{T}, f.y)
+    check(ccall((:bz_problem_set_multipliers, lib), Cint, (Ptr{Cvoid}, Ptr{T}, Ptr{T}), p.h, mu, y), p)
+    xs = similar(x0); st = Ref(PanocStats())
+    check(ccall((:bz_panoc_solve, lib), Cint, (Ptr{Cvoid}, Ref{PanocOpts}, Ptr{T}, Ptr{T}, Ref{PanocStats}),
+                p.h, Ref(s.opts), x0, xs, st), p)
+    g.gz = T(st[].g_z)          # als.jl:79 reads gSlack.gz and evaluates f(x) itself
+    g.gamma = st[].gamma
+    return xs, Int(st[].iters)
 end
 
 # ---- the whole outer loop with device-resident vectors (bz_alps_solve) --------------------------
@@ -326,6 +346,28 @@ function alps(f, g, c, D, x0::AbstractVector{T}, y0::AbstractVector{T}; tol::Rea
     r = st[]
     return x, y, Int(r.tot_it), Int(r.tot_inner_it), r.elapsed_s, _status[r.status + 1], T(r.inner_tol),
            (r.tot_it == 0 ? nothing : T(r.norm_res_prim)), s, mu      # alps.jl:34,115: `nothing` before the first outer iteration
+end
+
+"""`als(f, g, c, D, x0, y0; kw...)`: same keywords, defaults and 10-tuple as `Bazinga.als` (als.jl:14-25,118), the whole
+outer loop on the device (bz_als_solve).  Lowered for c = identity with f Zero / DiagQuadratic and for c = DenseAffine with
+f Zero / DiagQuadratic / LeastSquares / Quadratic — the (f, g, c, D) of demo/portfolio.jl with its constraint written as
+`DenseAffine([mu'; ones(1, n)], zeros(2))` and its set as `ClosedSet(IndBox([rho, 1], [Inf, 1]))`."""
+function als(f, g, c, D, x0::AbstractVector{T}, y0::AbstractVector{T}; tol::Real = T(1e-6), tol_prim::Real = tol,
+             tol_dual::Real = tol, inner_tol::Real = cbrt(tol_dual), maxit::Integer = 100,
+             theta_penalty::Real = 0.8, kappa_penalty::Real = 0.5, kappa_tol::Real = 0.1, verbose::Bool = false,
+             subsolver = PANOCplus, subsolver_maxit::Integer = 1_000_000_000, warm_start::Bool = false) where {T}
+    p = Problem(f, g, c, D, length(x0), length(y0), T; slack = true)
+    ao = AlpsOpts(tol_prim = tol_prim, tol_dual = tol_dual, inner_tol = inner_tol, maxit = maxit,
+                  theta_penalty = theta_penalty, kappa_penalty = kappa_penalty, kappa_tol = kappa_tol,
+                  subsolver_maxit = subsolver_maxit, verbose = verbose, warm_start = Int32(warm_start))
+    po = subsolver(tol = inner_tol, verbose = verbose).opts
+    x = similar(x0); y = similar(y0); s = similar(y0); mu = similar(y0); st = Ref(AlpsStats())
+    check(ccall((:bz_als_solve, lib), Cint,
+                (Ptr{Cvoid}, Ref{AlpsOpts}, Ref{PanocOpts}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ptr{T}, Ref{AlpsStats}),
+                p.h, Ref(ao), Ref(po), x0, y0, x, y, s, mu, st), p)
+    r = st[]
+    return x, y, Int(r.tot_it), Int(r.tot_inner_it), r.elapsed_s, _status[r.status + 1], T(r.inner_tol),
+           (r.tot_it == 0 ? nothing : T(r.norm_res_prim)), s, mu
 end
 
 end # module
