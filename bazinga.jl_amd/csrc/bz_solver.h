@@ -10,12 +10,12 @@
 #include <hip/hip_runtime.h>
 #include <rccl/rccl.h>
 
-#include <deque>
 #include <stdexcept>
 #include <string>
 #include <vector>
 
 #include "bz_kernels.h"
+#include "bz_lbfgs_host.h"
 
 namespace bz {
 
@@ -84,6 +84,10 @@ template <class T> struct DBuf {
         if (p) (void)hipFree(p);
         p = nullptr; n = 0;
     }
+    void swap(DBuf& o) {            // trade two buffers by pointer
+        std::swap(p, o.p);
+        std::swap(n, o.n);
+    }
     ~DBuf() { release(); }
 };
 
@@ -103,8 +107,6 @@ enum Slot : int {
     SL_ZS = 79,        // 3 slots: sink of the forward-backward step that re-materialises z
     SL_COUNT = 82
 };
-constexpr int MAX_MEM = 16;
-constexpr int CM = 5;            // capacity of the compact L-BFGS form (pairs)
 
 // the one-pass iteration kernel of an oracle family (k_fused_compact<T, CM, NT, true, true, 2, -1, -1, FAM>)
 template <class T>

@@ -443,7 +443,7 @@ template <class T> class Solver final : public SolverBase {
     }
 
     bool should_stop() const override {
-        return k_ >= opt.maxit || (double)stop_norm_ <= opt.tol;
+        return cnt_.k >= opt.maxit || (double)stop_norm_ <= opt.tol;
     }
 
     void finish(void* x_out, bz_panoc_stats* st) override {
@@ -454,11 +454,11 @@ template <class T> class Solver final : public SolverBase {
 
     void scalars(double* o) override {
         require_active();
-        o[0] = (double)k_; o[1] = (double)gamma; o[2] = (double)tau; o[3] = (double)f_x;
-        o[4] = (double)g_z; o[5] = (double)dot_gr; o[6] = (double)ss_res; o[7] = stop_norm_;
-        o[8] = (double)last_ys; o[9] = (double)order.size(); o[10] = (double)H;
-        o[11] = (double)f_z_al; o[12] = (double)fraw_last; o[13] = (double)last_nbt;
-        o[14] = last_fused ? 1.0 : 0.0; o[15] = (double)fbe_last;
+        o[0] = (double)cnt_.k; o[1] = (double)state_.gamma; o[2] = (double)tau; o[3] = (double)state_.f_x;
+        o[4] = (double)state_.g_z; o[5] = (double)state_.dot_gr; o[6] = (double)state_.ss_res; o[7] = stop_norm_;
+        o[8] = (double)last_ys; o[9] = (double)state_.lbfgs.order.size(); o[10] = (double)state_.lbfgs.H;
+        o[11] = (double)state_.f_z_al; o[12] = (double)state_.fraw_last; o[13] = (double)last_nbt;
+        o[14] = last_fused ? 1.0 : 0.0; o[15] = (double)state_.fbe_last;
     }
 
     void vector(int which, void* out) override {
@@ -468,11 +468,11 @@ template <class T> class Solver final : public SolverBase {
         case 1: ensure_z(false); copy_out(out, Z_[zc].p, n); break;
         case 2: ensure_z(); copy_out(out, RES_[rc].p, n); break;
         case 3:
-            if (!gx_valid) { dense_redo([&] { algrad(X_[xc].p, GX_.p, SL_AUX); }); gx_valid = true; }
+            if (!state_.gx_valid) { dense_redo([&] { algrad(X_[xc].p, GX_.p, SL_AUX); }); state_.gx_valid = true; }
             copy_out(out, GX_.p, n); break;
         case 4:
             ensure_z();
-            if (!gz_valid) { dense_redo([&] { algrad(Z_[zc].p, GZ_.p, SL_AUX); }); gz_valid = true; }
+            if (!state_.gz_valid) { dense_redo([&] { algrad(Z_[zc].p, GZ_.p, SL_AUX); }); state_.gz_valid = true; }
             copy_out(out, GZ_.p, n); break;
         default: throw Error(BZ_ERR_ARG, "unknown vector id");
         }
@@ -504,20 +504,19 @@ template <class T> class Solver final : public SolverBase {
     void eval_lbfgs(int m, const void* S, const void* Y, const void* v, void* d) override {
         if (m < 0 || m > MAX_MEM) throw Error(BZ_ERR_ARG, "bad pair count");
         active = false;
-        M = std::max(1, m);
+        state_.lbfgs.reset_all(std::max(1, m));
         alloc_history();
-        lbfgs_reset_all();
         rc = 0; xc = 0;
         const T* Sh = (const T*)S; const T* Yh = (const T*)Y;
         for (int i = 0; i < m; ++i) {   // oldest first, as update! would have seen them
-            const int slot = spare;
+            const int slot = state_.lbfgs.spare;
             copy_in(S_[slot].p, Sh + (size_t)i * n, n);
             copy_in(Y_[slot].p, Yh + (size_t)i * n, n);
             mv(2); launch(C_MISC, k_dot<T>, grid, (const T*)S_[slot].p, (const T*)Y_[slot].p, T(1), n, parts_.p, (int)SL_YS);
             mv(1); launch(C_MISC, k_dot<T>, grid, (const T*)Y_[slot].p, (const T*)Y_[slot].p, T(1), n, parts_.p, (int)SL_YTY);
             gather(SL_YS, 2, 0u);
             auto r = collect({SL_YS, SL_YTY}, 0u);
-            lbfgs_insert((T)r[0], (T)r[1]);
+            state_.lbfgs.insert((T)r[0], (T)r[1], nullptr, nullptr, compact_ok, dir_kind_ == BZ_DIR_ANDERSON);
         }
         // d = H * v  == two-loop applied to -(-v)
         std::vector<T> neg(n);
@@ -617,15 +616,15 @@ template <class T> class Solver final : public SolverBase {
             po2.tol = inner_tol;                                     // alps.jl:64
             po2.verbose = ao.verbose;
             // opt-in (bz_alps_opts.warm_start bit 0): subsolver(tol, verbose; gamma = gamma_prev, adaptive = true)
-            if ((ao.warm_start & 1) && tot_it > 1 && (double)gamma > 0.0) { po2.gamma = (double)gamma; po2.adaptive = 1; }
+            if ((ao.warm_start & 1) && tot_it > 1 && (double)state_.gamma > 0.0) { po2.gamma = (double)state_.gamma; po2.adaptive = 1; }
             // dual_safeguard(y, cx)  alps.jl:62  +  AugLagUpdate!  alps.jl:65, one pass
             aug_lag_update(true);
             begin_dev(po2, x);                                       // alps.jl:66
             run_to_completion();
-            const int64_t sub_it = k_;
+            const int64_t sub_it = cnt_.k;
             ensure_z(false);
             x = Z_[zc].p;                                            // x .= sub_sol
-            objx = fraw_last + g_z;                                  // alps.jl:68
+            objx = state_.fraw_last + state_.g_z;                    // alps.jl:68
             tot_inner += sub_it;
             const bool sub_solved = sub_it < ao.subsolver_maxit;     // alps.jl:70
             // dual update + primal residual                          alps.jl:72-84
@@ -669,8 +668,7 @@ template <class T> class Solver final : public SolverBase {
             // next subproblem starts from x (kept in the z buffer): copy to a state buffer
             // (the z buffer BECOMES the first state buffer: the next bz_panoc_begin recomputes z anyway)
             if (!can_stop) {
-                std::swap(X_[0].p, Z_[zc].p);
-                std::swap(X_[0].n, Z_[zc].n);
+                X_[0].swap(Z_[zc]);
                 x = X_[0].p;
             }
         }
@@ -721,14 +719,14 @@ template <class T> class Solver final : public SolverBase {
         while (!can_stop) {
             ++tot_it;
             po2.tol = inner_tol; po2.verbose = ao.verbose;
-            if ((ao.warm_start & 1) && tot_it > 1 && (double)gamma > 0.0) { po2.gamma = (double)gamma; po2.adaptive = 1; }
+            if ((ao.warm_start & 1) && tot_it > 1 && (double)state_.gamma > 0.0) { po2.gamma = (double)state_.gamma; po2.adaptive = 1; }
             aug_lag_update(true);                                    // dual_safeguard + AugLagUpdate!(fSlack, mu, y)
             begin_dev(po2, xs);                                      // sub_solver(f=fSlack, g=gSlack, x0=xSlack)
             run_to_completion();
-            const int64_t sub_it = k_;
+            const int64_t sub_it = cnt_.k;
             ensure_z(false);                                         // (the one-pass kernel keeps z in registers until it is asked for)
             xs = Z_[zc].p;                                           // xSlack .= sub_sol
-            objx = fraw_last + g_z;                                  // f(x) + gSlack.gz       als.jl:79
+            objx = state_.fraw_last + state_.g_z;                    // f(x) + gSlack.gz       als.jl:79
             tot_inner += sub_it;
             const bool sub_solved = sub_it < ao.subsolver_maxit;
             // y += (cx - s)/mu ; ||cx - s||_inf                      als.jl:82-87
@@ -886,23 +884,23 @@ template <class T> class Solver final : public SolverBase {
     // iterations stops rounding drift.  State: c and grad L at the current x and z (CXS_, GX_, CZS_, GZ_), their
     // candidates (CXD_, CZN_, GXN_, GZN_) and the images of every stored pair (AS_, AY_: ny-vectors; GS_, GY_: n).
     bool affine_ok_ = false, aff_track_ = false;
-    int aff_refresh_ = 8, aff_count_ = 0;
-    int64_t n_affine_ = 0, n_affine_verify_ = 0, n_affine_blends_ = 0;
+    int aff_refresh_ = 8;
     T* cx_keep_ = nullptr;                   // algrad (dense c): also leave c(point) here
     DBuf<T> CXS_, CZS_, CXD_, CZN_, GXN_, GZN_;
     std::vector<DBuf<T>> AS_, AY_, GS_, GY_;
     CompactVecs<T, CM> image_vecs(bool ny_space) const {      // logical (oldest first) view, as compact_vecs()
         CompactVecs<T, CM> V;
         std::memset(&V, 0, sizeof(V));
-        V.m = (int)order.size();
+        V.m = (int)state_.lbfgs.order.size();
         for (int i = 0; i < V.m; ++i) {
-            const int s = order[V.m - 1 - i];
+            const int s = state_.lbfgs.order[V.m - 1 - i];
             V.S[i] = ny_space ? AS_[s].p : GS_[s].p;
             V.Y[i] = ny_space ? AY_[s].p : GY_[s].p;
         }
         return V;
     }
     bool persist_broken_ = false;            // a grid barrier timed out once on this problem: the kernel chain from then on
+    int64_t n_persist_fallbacks_ = 0;
     std::vector<DBuf<T>> S_, Y_;
     DBuf<double> parts_, alphas_, send_, recv_;
     double* host_out_ = nullptr;             // pinned mailbox: {value, ticket} per collected scalar
@@ -913,12 +911,7 @@ template <class T> class Solver final : public SolverBase {
 
     // solver state (host scalars)
     bz_panoc_opts opt{};
-    bool active = false, fused_ok = false, gx_valid = false, gz_valid = false;
-    // The one-pass compact kernel computes z in registers and does not store it: nothing in a plain iteration
-    // reads it back (the next iterate is x_d, the stopping test uses grad L(z) formed in the same pass), and
-    // the store is the dearest of the kernel's streams (-8 % of its time).  Who does need it — a tau backtrack
-    // (z_curr), the caller asking for the solution — gets it re-materialised bit for bit from x and gamma.
-    bool z_valid = true;
+    bool active = false, fused_ok = false;
     // History as iterates: once the last iterations were plain ones that each inserted their pair, the stored
     // pairs are the successive differences of the last iterates, which the long x ring still holds, and the
     // residual of an iterate is a function of that iterate alone (res = x - prox(x - gamma grad L(x)), with
@@ -930,18 +923,17 @@ template <class T> class Solver final : public SolverBase {
     int xr_run_ = 0;             // consecutive plain, pair-inserting iterations so far
     bool sy_stale_ = false;      // S_/Y_ do not hold the stored pairs (they live in the x ring)
     double gring_[NXR] = {0};    // the gamma the residual of each iterate in the ring was (or would be) formed with
-    bool res_valid = true;       // RES_[rc] holds the residual of the current state
     void materialize_pairs() {
         if (!sy_stale_) return;
         SnapVecs<T, CM> V;
         std::memset(&V, 0, sizeof(V));
-        const int m = (int)order.size();      // (< CM soon after a memory reset)
+        const int m = (int)state_.lbfgs.order.size();      // (< CM soon after a memory reset)
         for (int i = 0; i <= CM; ++i) {
             const int back = std::max(0, m - i);
             V.XH[i] = X_[(xc - back + NXR) % NXR].p;
-            V.gam[i] = back ? gring_[(xc - back + NXR) % NXR] : (double)gamma;
+            V.gam[i] = back ? gring_[(xc - back + NXR) % NXR] : (double)state_.gamma;
         }
-        for (int i = 0; i < m; ++i) { V.S[i] = S_[order[m - 1 - i]].p; V.Y[i] = Y_[order[m - 1 - i]].p; }
+        for (int i = 0; i < m; ++i) { V.S[i] = S_[state_.lbfgs.order[m - 1 - i]].p; V.Y[i] = Y_[state_.lbfgs.order[m - 1 - i]].p; }
         if (slack) {
             // (the lifted vector: both halves of every iterate in, both halves of the pairs, the residual and z out)
             mv(2 * ((m + 1) + 2 * m + 2) + pstreams(true, true, true) + (P.uni >= 2 ? 0 : 1), nx);
@@ -951,27 +943,43 @@ template <class T> class Solver final : public SolverBase {
             mv((m + 1) + pstreams(true, true, true) + 2 * m + 2);
             launch(C_MISC, k_pairs_from_iterates<T, CM>, grid, V, m, P, RES_[rc].p, Z_[zc].p, n);
         }
-        res_valid = true; z_valid = true;
+        state_.res_valid = true; state_.z_valid = true;
         sy_stale_ = false;
     }
     int xc = 0, rc = 0, zc = 0;
     T alpha = T(0.95), beta = T(0.5), min_gamma = T(1e-7), musqy = T(0);
     T gamma_given_ = T(0);       // bz_panoc_opts.gamma / alpha / Lf (0: estimate a Lipschitz constant)
     bool adaptive_ = true;       // upstream's `adaptive`: gamma halvings at the start and inside the line search
-    T gamma = T(0), tau = T(0), f_x = T(0), g_z = T(0), dot_gr = T(0), ss_res = T(0);
-    T f_z_al = T(0), fraw_last = T(0), last_ys = T(0), fbe_last = T(0);
+    T tau = T(0), last_ys = T(0);
     double stop_norm_ = 0;
-    int64_t k_ = 0, n_grad = 0, n_prox = 0, n_bt = 0, n_halv = 0, n_fused = 0, n_skips = 0;
+    // What step_impl may change before its last read-back (the ring indices, the pair insertion and the stop norm are
+    // committed after it): the state's scalars, the L-BFGS bookkeeping (a halving resets it), the image counters, the
+    // validity flags, and which allocation each affine-image buffer holds — traded by pointer, and only the candidates
+    // (GXN_, GZN_, CXD_, CZN_) and the spare pair's images are written.  step() snapshots this struct by copy and puts it
+    // back by assignment: a member an iteration changes before its last read-back belongs here, and is then restored.
+    struct ImageRef { T* p; size_t n; };
+    struct IterState {
+        T gamma = T(0), f_x = T(0), g_z = T(0), dot_gr = T(0), ss_res = T(0);
+        T f_z_al = T(0), fraw_last = T(0), fbe_last = T(0);
+        LbfgsMemory<T> lbfgs;
+        int aff_count = 0;
+        bool gx_valid = false, gz_valid = false;
+        // The one-pass compact kernel computes z in registers and does not store it: nothing in a plain iteration
+        // reads it back (the next iterate is x_d, the stopping test uses grad L(z) formed in the same pass), and
+        // the store is the dearest of the kernel's streams (-8 % of its time).  Who does need it — a tau backtrack
+        // (z_curr), the caller asking for the solution — gets it re-materialised bit for bit from x and gamma.
+        bool z_valid = true;
+        bool res_valid = true;       // RES_[rc] holds the residual of the current state
+        int64_t n_affine = 0, n_affine_verify = 0, n_affine_blends = 0;
+        ImageRef img[8] = {};        // image_bufs() as snapshot() found them (the DBufs own the memory; unused in state_ itself)
+    };
+    IterState state_;
+    // the counters an iteration advances: every recovery in step() puts them back
+    struct IterCounters { int64_t k = 0, n_grad = 0, n_prox = 0, n_bt = 0, n_halv = 0, n_fused = 0, n_skips = 0; };
+    IterCounters cnt_;
     int last_nbt = 0;
     bool last_fused = false;
     std::chrono::steady_clock::time_point t_begin;
-    // L-BFGS ring: M+1 physical slots, `order` newest first, `spare` receives the candidate pair
-    int M = 5;
-    std::deque<int> order;
-    std::vector<int> freeslots;
-    int spare = 0;
-    T ys_[MAX_MEM + 1];
-    T H = T(1);
     // `directions` other than L-BFGS (bz_panoc_opts.directions)
     int dir_kind_ = BZ_DIR_LBFGS;
     T broyden_theta_bar_ = T(0.2);
@@ -994,8 +1002,8 @@ template <class T> class Solver final : public SolverBase {
     //   Hy = H y ; sH = s'H ; delta = <Hy, s> / <s, s> ; theta = 1 if |delta| >= theta_bar else
     //   (1 - sgn(delta) theta_bar) / (1 - delta), sgn(0) = 1 ; H += (s - Hy) / <s, (1/theta - 1) s + Hy> * sH
     void broyden_update() {
-        const T* sv = S_[spare].p;
-        const T* yv = Y_[spare].p;
+        const T* sv = S_[state_.lbfgs.spare].p;
+        const T* yv = Y_[state_.lbfgs.spare].p;
         gemv_rows(HB_.p, n, n, yv, (const T*)nullptr, BHy_.p);
         gemv_cols(HB_.p, n, n, sv, b_rpc_, b_nch_, GT_.p, npad);
         {
@@ -1021,49 +1029,7 @@ template <class T> class Solver final : public SolverBase {
         launch(C_MISC, k_rank1_update<T>, (int)std::min<int64_t>(PSTRIDE, (n * n + BLOCK - 1) / BLOCK), HB_.p, sv,
                (const T*)BHy_.p, (const T*)BsH_.p, T(1) / denom, n);
     }
-    // Anderson: a = (Y'Y)^-1 Y'v by elimination with complete pivoting on the Gram matrix (pivots below 1e-14 of the
-    // largest are treated as a rank deficiency: their coefficient is zero)
-    void anderson_coefficients(int m, const double* w, double* a) const {
-        double A[CM * CM], b[CM];
-        int perm[CM];
-        for (int i = 0; i < m; ++i) { b[i] = w[i]; perm[i] = i; for (int j = 0; j < m; ++j) A[i * CM + j] = Gyy[i * CM + j]; }
-        double amax = 0.0;
-        for (int i = 0; i < m; ++i) amax = std::max(amax, std::abs(A[i * CM + i]));
-        int rank = 0;
-        for (int k = 0; k < m; ++k) {
-            int pi = k, pj = k;
-            double best = 0.0;
-            for (int i = k; i < m; ++i)
-                for (int j = k; j < m; ++j)
-                    if (std::abs(A[i * CM + j]) > best) { best = std::abs(A[i * CM + j]); pi = i; pj = j; }
-            if (!(best > 1e-14 * amax)) break;
-            if (pi != k) { for (int j = 0; j < m; ++j) std::swap(A[k * CM + j], A[pi * CM + j]); std::swap(b[k], b[pi]); }
-            if (pj != k) { for (int i = 0; i < m; ++i) std::swap(A[i * CM + k], A[i * CM + pj]); std::swap(perm[k], perm[pj]); }
-            for (int i = k + 1; i < m; ++i) {
-                const double f = A[i * CM + k] / A[k * CM + k];
-                for (int j = k; j < m; ++j) A[i * CM + j] -= f * A[k * CM + j];
-                b[i] -= f * b[k];
-            }
-            rank = k + 1;
-        }
-        double z[CM] = {0};
-        for (int k = rank - 1; k >= 0; --k) {
-            double acc = b[k];
-            for (int j = k + 1; j < rank; ++j) acc -= A[k * CM + j] * z[j];
-            z[k] = acc / A[k * CM + k];
-        }
-        for (int i = 0; i < m; ++i) a[i] = 0.0;
-        for (int k = 0; k < rank; ++k) a[perm[k]] = z[k];
-    }
-    // compact form: Gram products of the stored pairs in logical order (oldest first), CM x CM
-    bool compact_ok = false;
-    int gm = 0;
-    double Gsy[CM * CM], Gyy[CM * CM];
-    // p = S'(-res), w = Y'(-res) at the current state (logical order, oldest first), when the accepted
-    // trial delivered them (k_fused_compact): the next application then needs no reduction pass at all
-    double p_new_ = 0.0, w_new_ = 0.0;      // <s_new, -res>, <y_new, -res> of the candidate pair
-    bool pw_valid = false;
-    double hp_[CM] = {0}, hw_[CM] = {0};
+    bool compact_ok = false;                 // the compact form of the memory serves this solve (select_paths)
 
     // ---- gated pre-launch of the next iteration's one-pass kernel (see GateRec in bz_kernels.h) ----
     struct GatePlan {                        // everything the launch needs except the coefficients and the z address
@@ -1121,7 +1087,7 @@ template <class T> class Solver final : public SolverBase {
         if (!(env_.xr && small_vectors() && fam >= 0 && xr_run >= m_now)) return false;
         // (only the oldest stored iterate may carry another gamma — see CompactCoef::gam0)
         for (int i = 1; i < m_now; ++i)
-            if (gring[(xc_ - m_now + i + NXR) % NXR] != (double)gamma) return false;
+            if (gring[(xc_ - m_now + i + NXR) % NXR] != (double)state_.gamma) return false;
         std::memset(&pl, 0, sizeof(pl));
         for (int i = 0; i < CM; ++i) {
             const int slot = (xc_ - std::max(0, m_now - i) + NXR) % NXR;      // (beyond m: x itself)
@@ -1129,7 +1095,7 @@ template <class T> class Solver final : public SolverBase {
             if (i == 0) pl.gam0 = gring[slot];
         }
         pl.x = X_[xc_].p; pl.xd = X_[(xc_ + 1) % NXR].p;
-        pl.gamma = (double)gamma; pl.uni = uni_; pl.fam = fam; pl.m_now = m_now;
+        pl.gamma = (double)state_.gamma; pl.uni = uni_; pl.fam = fam; pl.m_now = m_now;
         // (one wave per SIMD, see trial_onepass)
         pl.gfc = env_.gfc > 0 ? std::min(grid, env_.gfc * std::max(1, num_cus)) : std::min(grid, std::max(1, num_cus));
         pl.nt = env_.nt >= 0 ? env_.nt != 0 : (double)n * sizeof(T) * (xr2_streams(m_now) + (zstore ? 1 : 0)) > 340e6;
@@ -1186,9 +1152,9 @@ template <class T> class Solver final : public SolverBase {
     void gate_prelaunch(int xd, int m_now) {
         double gr[NXR];
         for (int i = 0; i < NXR; ++i) gr[i] = gring_[i];
-        gr[xd] = (double)gamma;
+        gr[xd] = (double)state_.gamma;
         GatePlan pl;
-        if (!xr2_plan(xd, std::min(m_now + 1, M), gr, xr_run_ + 1, false, pl)) return;
+        if (!xr2_plan(xd, std::min(m_now + 1, state_.lbfgs.M), gr, xr_run_ + 1, false, pl)) return;
         gate_alloc();
         CompactCoef<CM> C2;
         std::memset(&C2, 0, sizeof(C2));
@@ -1332,6 +1298,11 @@ template <class T> class Solver final : public SolverBase {
     // ---- row-block-sharded stencil: halo rows through IPC-mapped fine-grained buffers -------------------
     // region layout: rows[parity][side][ny] of T (side 0 = north halo, written by the previous rank; side 1 =
     // south halo, written by the next rank), then flags[parity][side] (64-byte aligned)
+    void* halo_local_ = nullptr;
+    void* halo_prev_ = nullptr;
+    void* halo_next_ = nullptr;
+    bool halo_connected_ = false;
+    unsigned long long hseq_ = 0;
     size_t halo_rows_bytes() const { return ((size_t)4 * desc.f_grid_ny * sizeof(T) + 63) / 64 * 64; }
     size_t halo_bytes() const { return halo_rows_bytes() + 64; }
     static T* halo_row(void* base, int par, int side, int64_t ny) { return (T*)base + (size_t)(par * 2 + side) * ny; }
@@ -1386,8 +1357,6 @@ template <class T> class Solver final : public SolverBase {
         return StencilHalo<T>{halo_prev_ ? halo_row(halo_local_, par, 0, gny) : nullptr,
                               halo_next_ ? halo_row(halo_local_, par, 1, gny) : nullptr};
     }
-    // ---- row-sharded dense constraint: x replicated, A' yhat summed over the ranks --------------------
-    // region layout: slots[parity][rank][npad] of T, then flags[parity][rank]
     // ---- dense constraint in ONE pass over A (k_dense_fused) ------------------------------------------
     bool dense_fused_broken_ = false;
     int64_t n_dense_fallbacks_ = 0, n_dense_onepass_ = 0;
@@ -1463,6 +1432,8 @@ template <class T> class Solver final : public SolverBase {
         ++n_dense_onepass_;
     }
     int dense_sabotage_count_ = 0;
+    // ---- row-sharded dense constraint: x replicated, A' yhat summed over the ranks --------------------
+    // region layout: slots[parity][rank][npad] of T, then flags[parity][rank]
     bool x_replicated = false;
     DBuf<T> JL_;                     // this rank's partial of A' yhat
     void* ar_local_ = nullptr;
@@ -1526,13 +1497,6 @@ template <class T> class Solver final : public SolverBase {
         return ar_slot(ar_local_, par, 0);
     }
 
-    void* halo_local_ = nullptr;
-    void* halo_prev_ = nullptr;
-    void* halo_next_ = nullptr;
-    bool halo_connected_ = false;
-    unsigned long long hseq_ = 0;
-
-    // multi-GPU: fold this rank's block partials of slots [first, first+cnt) and all-gather
     // z of the CURRENT state into Z_[zc] if the last fused pass skipped its store:
     //   z = prox_{gamma g}(x - gamma grad L(x))   — the arithmetic of k_algrad_elem + k_fbstep, which the fused
     //   passes reproduce bit for bit (test_fused_equals_generic_bitwise)
@@ -1540,19 +1504,20 @@ template <class T> class Solver final : public SolverBase {
     // need_res = false: the caller reads z only (the solution of a subproblem, alps.jl:67): a z that the last pass stored is
     // enough, whatever the state of res (the iterate-history passes never write it)
     void ensure_z(bool need_res = true) {
-        if (z_valid && (res_valid || !need_res)) return;
+        if (state_.z_valid && (state_.res_valid || !need_res)) return;
         if (begin_fb_ok()) {
-            mv(1 + pstreams(true, true, true) + 1 + (res_valid ? 0 : 1));
-            launch(C_FB, k_zres_elem<T>, grid, (const T*)X_[xc].p, P, gamma, Z_[zc].p,
-                   res_valid ? (T*)nullptr : RES_[rc].p, n);      // the two kernels below in one pass
+            mv(1 + pstreams(true, true, true) + 1 + (state_.res_valid ? 0 : 1));
+            launch(C_FB, k_zres_elem<T>, grid, (const T*)X_[xc].p, P, state_.gamma, Z_[zc].p,
+                   state_.res_valid ? (T*)nullptr : RES_[rc].p, n);      // the two kernels below in one pass
         } else {
             dense_redo([&] {
                 algrad(X_[xc].p, D_.p, SL_AUX);              // scratch gradient: GX_/GZ_ keep their meaning
-                fbstep(X_[xc].p, D_.p, gamma, Z_[zc].p, res_valid ? (T*)nullptr : RES_[rc].p, SL_ZS);
+                fbstep(X_[xc].p, D_.p, state_.gamma, Z_[zc].p, state_.res_valid ? (T*)nullptr : RES_[rc].p, SL_ZS);
             });
         }
-        z_valid = true; res_valid = true;
+        state_.z_valid = true; state_.res_valid = true;
     }
+    // multi-GPU: fold this rank's block partials of slots [first, first+cnt) and all-gather
     // ymask (row-sharded dense c only, where x-space quantities are computed in full by every rank): the
     // slots that are sums over THIS rank's constraint rows and must be added up; the others count once
     void gather(int first, int cnt, unsigned maxmask, unsigned ymask = 0u) {
@@ -1562,15 +1527,9 @@ template <class T> class Solver final : public SolverBase {
             if (cnt > P2P_PACK) throw Error(BZ_ERR_ARG, "pack too large for the p2p mailbox");
             XchgArgs a;
             std::memset(&a, 0, sizeof(a));
-            a.parts = parts_.p; a.first = first; a.cnt = cnt; a.maxmask = maxmask;
-            for (int i = 0; i < cnt; ++i) a.counts.set(i, slot_n[first + i]);
-            a.rank = ctx->rank; a.nranks = ctx->nranks; a.seq = ++ctx->xseq;
-            a.recv = recv_.p + (size_t)first * ctx->nranks;
-            a.mbox_local = (P2PWords*)ctx->mbox_local;
-            for (int r = 0; r < ctx->nranks; ++r) a.mbox_peer[r] = (P2PWords*)ctx->mbox_peer[r];
-            a.timeout = ptimeout_dev_; a.keepmask = keepmask;
+            fill_xchg(a, first, cnt, maxmask);
+            a.keepmask = keepmask;
             launch_b(C_GATHER, k_exchange, cnt, 64, a);
-            for (int s = first; s < first + cnt; ++s) { grp_first[s] = first; grp_cnt[s] = cnt; }
             return;
         }
         if (cnt > 32) throw Error(BZ_ERR_ARG, "pack too large");
@@ -1583,13 +1542,8 @@ template <class T> class Solver final : public SolverBase {
                               ctx->comm, ctx->stream));
         for (int s = first; s < first + cnt; ++s) { grp_first[s] = first; grp_cnt[s] = cnt; }
     }
-    // the arguments of the fold + (p2p) exchange + read-back of slots [first, first + cnt): with mailboxes the exchange over
-    // the ranks, without (one rank, no p2p context) the local fold alone
-    XCollectArgs make_xcollect(int first, int cnt, unsigned maxmask) {
-        if (cnt > P2P_PACK) throw Error(BZ_ERR_ARG, "pack too large for the p2p mailbox");
-        XCollectArgs b;
-        std::memset(&b, 0, sizeof(b));
-        XchgArgs& a = b.x;
+    // what k_exchange and k_exchange_collect share (a zeroed `a`): the slots, and with mailboxes the peers and the next sequence number
+    void fill_xchg(XchgArgs& a, int first, int cnt, unsigned maxmask) {
         a.parts = parts_.p; a.first = first; a.cnt = cnt; a.maxmask = maxmask;
         for (int i = 0; i < cnt; ++i) a.counts.set(i, slot_n[first + i]);
         a.rank = 0; a.nranks = 1;
@@ -1600,7 +1554,16 @@ template <class T> class Solver final : public SolverBase {
             for (int r = 0; r < ctx->nranks; ++r) a.mbox_peer[r] = (P2PWords*)ctx->mbox_peer[r];
             for (int s = first; s < first + cnt; ++s) { grp_first[s] = first; grp_cnt[s] = cnt; }
         }
-        a.timeout = ptimeout_dev_; a.keepmask = ~0u;
+        a.timeout = ptimeout_dev_;
+    }
+    // the arguments of the fold + (p2p) exchange + read-back of slots [first, first + cnt): with mailboxes the exchange over
+    // the ranks, without (one rank, no p2p context) the local fold alone
+    XCollectArgs make_xcollect(int first, int cnt, unsigned maxmask) {
+        if (cnt > P2P_PACK) throw Error(BZ_ERR_ARG, "pack too large for the p2p mailbox");
+        XCollectArgs b;
+        std::memset(&b, 0, sizeof(b));
+        fill_xchg(b.x, first, cnt, maxmask);
+        b.x.keepmask = ~0u;
         b.host_out = host_out_dev_;
         b.ticket = ++collect_seq;
         return b;
@@ -2124,6 +2087,7 @@ template <class T> class Solver final : public SolverBase {
 
     // AugLagUpdate!(al, mu, y)  (auglagfun.jl:91-101) on the device copies mu_, ymul_ ; safeguard: the dual
     // safeguard of alps.jl:62 applied to y first, in the same pass
+    int uni_ = 0;                            // P.uni as the last update found it: 1 uniform penalties, 2 and zero multipliers
     void aug_lag_update(bool safeguard = false) {
         // Uniform penalties / zero multipliers (this rank's part of them): the one-pass kernel then takes mu as a
         // number and does not stream mu (nor mu*y).  alps.jl:42 gives every constraint the same mu when c(x0) is
@@ -2192,85 +2156,28 @@ template <class T> class Solver final : public SolverBase {
         }
         return fam_code(fk, gk, dk);
     }
-    int uni_ = 0;
 
     // --------------------------------------------------------------- L-BFGS
     void alloc_history() {
-        if ((int)S_.size() == M + 1) return;
-        S_ = std::vector<DBuf<T>>(M + 1);
-        Y_ = std::vector<DBuf<T>>(M + 1);
-        for (int i = 0; i <= M; ++i) { S_[i].alloc(vcap); Y_[i].alloc(vcap); }
+        if ((int)S_.size() == state_.lbfgs.M + 1) return;
+        S_ = std::vector<DBuf<T>>(state_.lbfgs.M + 1);
+        Y_ = std::vector<DBuf<T>>(state_.lbfgs.M + 1);
+        for (int i = 0; i <= state_.lbfgs.M; ++i) { S_[i].alloc(vcap); Y_[i].alloc(vcap); }
         if (affine_ok_) {
-            AS_ = std::vector<DBuf<T>>(M + 1); AY_ = std::vector<DBuf<T>>(M + 1);
-            GS_ = std::vector<DBuf<T>>(M + 1); GY_ = std::vector<DBuf<T>>(M + 1);
-            for (int i = 0; i <= M; ++i) { AS_[i].alloc(ny); AY_[i].alloc(ny); GS_[i].alloc(vcap); GY_[i].alloc(vcap); }
+            AS_ = std::vector<DBuf<T>>(state_.lbfgs.M + 1); AY_ = std::vector<DBuf<T>>(state_.lbfgs.M + 1);
+            GS_ = std::vector<DBuf<T>>(state_.lbfgs.M + 1); GY_ = std::vector<DBuf<T>>(state_.lbfgs.M + 1);
+            for (int i = 0; i <= state_.lbfgs.M; ++i) { AS_[i].alloc(ny); AY_[i].alloc(ny); GS_[i].alloc(vcap); GY_[i].alloc(vcap); }
         }
-    }
-    void lbfgs_reset_all() {
-        gm = 0; pw_valid = false;
-        order.clear(); freeslots.clear();
-        spare = 0;
-        for (int i = M; i >= 1; --i) freeslots.push_back(i);
-        H = T(1);
     }
     void lbfgs_reset() {                 // reset!(H): currmem = curridx = 0, H = 1
         if (dir_kind_ == BZ_DIR_BROYDEN) broyden_reset();
-        gm = 0; pw_valid = false;
-        for (int s : order) freeslots.push_back(s);
-        order.clear();
-        H = T(1);
-    }
-    // Gram products of the stored pairs after inserting a pair whose products with them are sy[i], yy[i]
-    // (i = logical index, oldest first): drop the oldest when the ring is full, append row/column
-    void gram_insert(double* sy, double* yy, double ys, double yty) {
-        int m = gm;
-        if (m == M) {                    // the oldest pair is overwritten
-            for (int i = 1; i < m; ++i)
-                for (int j = 1; j < m; ++j) { Gsy[(i - 1) * CM + (j - 1)] = Gsy[i * CM + j]; Gyy[(i - 1) * CM + (j - 1)] = Gyy[i * CM + j]; }
-            for (int i = 1; i < m; ++i) { sy[i - 1] = sy[i]; yy[i - 1] = yy[i]; hp_[i - 1] = hp_[i]; hw_[i - 1] = hw_[i]; }
-            --m;
-        }
-        hp_[m] = p_new_; hw_[m] = w_new_;
-        for (int i = 0; i < m; ++i) {
-            Gsy[i * CM + m] = sy[i]; Gsy[m * CM + i] = 0.0;
-            Gyy[i * CM + m] = yy[i]; Gyy[m * CM + i] = yy[i];
-        }
-        Gsy[m * CM + m] = ys; Gyy[m * CM + m] = yty;
-        gm = m + 1;
-    }
-    // M1 = R^-T (D + H0 Y'Y) R^-1 and M2 = R^-1 (same loops as LBFGSCompactOperator.coefficient_matrices)
-    void compact_matrices(double H0, double* M1, double* M2) const {
-        const int m = gm;
-        double Ri[CM * CM] = {0}, B[CM * CM] = {0}, T1[CM * CM] = {0};
-        for (int j = 0; j < m; ++j) {
-            Ri[j * CM + j] = 1.0 / Gsy[j * CM + j];
-            for (int i = j - 1; i >= 0; --i) {
-                double acc = 0.0;
-                for (int k = i + 1; k <= j; ++k) acc += Gsy[i * CM + k] * Ri[k * CM + j];
-                Ri[i * CM + j] = -acc / Gsy[i * CM + i];
-            }
-        }
-        for (int i = 0; i < m; ++i)
-            for (int j = 0; j < m; ++j) B[i * CM + j] = H0 * Gyy[i * CM + j] + (i == j ? Gsy[i * CM + i] : 0.0);
-        for (int i = 0; i < m; ++i)
-            for (int j = 0; j < m; ++j) {
-                double acc = 0.0;
-                for (int k = 0; k <= j; ++k) acc += B[i * CM + k] * Ri[k * CM + j];
-                T1[i * CM + j] = acc;
-            }
-        for (int i = 0; i < CM * CM; ++i) { M1[i] = 0.0; M2[i] = Ri[i]; }
-        for (int i = 0; i < m; ++i)
-            for (int j = 0; j < m; ++j) {
-                double acc = 0.0;
-                for (int k = 0; k <= i; ++k) acc += Ri[k * CM + i] * T1[k * CM + j];
-                M1[i * CM + j] = acc;
-            }
+        state_.lbfgs.reset();
     }
     CompactVecs<T, CM> compact_vecs() const {      // logical (oldest first) view of the physical ring
         CompactVecs<T, CM> V;
         std::memset(&V, 0, sizeof(V));
-        V.m = (int)order.size();
-        for (int i = 0; i < V.m; ++i) { V.S[i] = S_[order[V.m - 1 - i]].p; V.Y[i] = Y_[order[V.m - 1 - i]].p; }
+        V.m = (int)state_.lbfgs.order.size();
+        for (int i = 0; i < V.m; ++i) { V.S[i] = S_[state_.lbfgs.order[V.m - 1 - i]].p; V.Y[i] = Y_[state_.lbfgs.order[V.m - 1 - i]].p; }
         return V;
     }
     // coefficient block for the kernels that apply the operator.  p = S'(-res), w = Y'(-res) normally came
@@ -2279,56 +2186,22 @@ template <class T> class Solver final : public SolverBase {
     CompactCoef<CM> compact_prepare(const CompactVecs<T, CM>& V) {
         const int m = V.m;
         if (m == 0) {
-            for (int i = 0; i < CM; ++i) { hp_[i] = 0.0; hw_[i] = 0.0; }
-            pw_valid = true;
+            for (int i = 0; i < CM; ++i) { state_.lbfgs.hp[i] = 0.0; state_.lbfgs.hw[i] = 0.0; }
+            state_.lbfgs.pw_valid = true;
         }
-        if (!pw_valid) {
+        if (!state_.lbfgs.pw_valid) {
             for (int k = 0; k < 2 * CM; ++k) slot_n[SL_GP + k] = grid;
             mv(2 * m + 1);
             launch(C_DOT, k_gram_dots<T, CM>, grid, V, (const T*)RES_[rc].p, n, parts_.p, (int)SL_GP);
             gather(SL_GP, 2 * CM, 0u);
             auto pv = collect_range(SL_GP, 2 * CM, 0u);
-            for (int i = 0; i < CM; ++i) { hp_[i] = i < m ? pv[i] : 0.0; hw_[i] = i < m ? pv[CM + i] : 0.0; }
-            pw_valid = true;
+            for (int i = 0; i < CM; ++i) { state_.lbfgs.hp[i] = i < m ? pv[i] : 0.0; state_.lbfgs.hw[i] = i < m ? pv[CM + i] : 0.0; }
+            state_.lbfgs.pw_valid = true;
         }
         CompactCoef<CM> C;
         std::memset(&C, 0, sizeof(C));
-        C.H0 = (double)H;
-        if (dir_kind_ == BZ_DIR_ANDERSON) {
-            // d = v + (S - Y) a , a = (Y'Y)^-1 Y'v : the compact kernels' linear combination with u1 = a, H0 u2 = -a
-            double a[CM] = {0};
-            anderson_coefficients(m, hw_, a);
-            C.H0 = 1.0;
-            for (int i = 0; i < CM; ++i) { C.u1[i] = i < m ? a[i] : 0.0; C.u2h[i] = i < m ? -a[i] : 0.0; }
-            return C;
-        }
-        double M1[CM * CM], M2[CM * CM];
-        compact_matrices(C.H0, M1, M2);
-        // same loops as LBFGSCompactOperator.__call__ (rows/columns beyond m are zero)
-        for (int i = 0; i < CM; ++i) {
-            double a = 0.0, b = 0.0, c = 0.0;
-            for (int j = 0; j < CM; ++j) a += M1[i * CM + j] * (j < m ? hp_[j] : 0.0);
-            for (int j = 0; j < CM; ++j) b += M2[j * CM + i] * (j < m ? hw_[j] : 0.0);
-            for (int j = 0; j < CM; ++j) c += M2[i * CM + j] * (j < m ? hp_[j] : 0.0);
-            C.u1[i] = i < m ? a - C.H0 * b : 0.0;
-            C.u2h[i] = i < m ? C.H0 * (-c) : 0.0;
-        }
+        state_.lbfgs.coefficients(dir_kind_ == BZ_DIR_ANDERSON, C.H0, C.u1, C.u2h);
         return C;
-    }
-
-    void lbfgs_insert(T ys, T yty, const double* sy = nullptr, const double* yy = nullptr) {     // update!(H, s, y) when <s,y> > 0
-        if (M == 0) return;              // NoAcceleration: nothing is stored, H stays 1
-        if (compact_ok) {
-            double z[CM] = {0};
-            double a[CM], b[CM];
-            for (int i = 0; i < CM; ++i) { a[i] = sy ? sy[i] : z[i]; b[i] = yy ? yy[i] : z[i]; }
-            gram_insert(a, b, (double)ys, (double)yty);
-        }
-        order.push_front(spare);
-        ys_[spare] = ys;
-        if ((int)order.size() > M) { spare = order.back(); order.pop_back(); }
-        else { spare = freeslots.back(); freeslots.pop_back(); }
-        H = dir_kind_ == BZ_DIR_ANDERSON ? T(1) : ys / yty;
     }
 
     // d = H(-res) up to the last axpy, which the caller fuses with what follows
@@ -2337,12 +2210,12 @@ template <class T> class Solver final : public SolverBase {
         TailArgs<T> t;
         std::memset(&t, 0, sizeof(t));
         t.alphas = alphas_.p;
-        const int m = (int)order.size();
+        const int m = (int)state_.lbfgs.order.size();
         PersistArgs<T> a;
         std::memset(&a, 0, sizeof(a));
         a.res = RES_[rc].p;
-        for (int j = 0; j < m; ++j) { a.S[j] = S_[order[j]].p; a.Y[j] = Y_[order[j]].p; a.ys[j] = ys_[order[j]]; }
-        a.H = H; a.m = m; a.d_out = D_.p; a.n = n; a.parts = parts_.p; a.alphas = alphas_.p;
+        for (int j = 0; j < m; ++j) { a.S[j] = S_[state_.lbfgs.order[j]].p; a.Y[j] = Y_[state_.lbfgs.order[j]].p; a.ys[j] = state_.lbfgs.ys[state_.lbfgs.order[j]]; }
+        a.H = state_.lbfgs.H; a.m = m; a.d_out = D_.p; a.n = n; a.parts = parts_.p; a.alphas = alphas_.p;
         a.counter = pcounter_.p; a.base = pbase + (env_.test_persist_timeout ? 1ull : 0ull); a.timeout = ptimeout_dev_;
         a.abort_flag = pgflag_.p + 1;
         a.slot_loop1 = SL_LOOP1; a.slot_loop2 = SL_LOOP2;
@@ -2368,9 +2241,9 @@ template <class T> class Solver final : public SolverBase {
         default: throw Error(BZ_ERR_STATE, "persistent two-loop: no instantiation for this size");
         }
         slot_n[SL_LOOP2 + 0] = a.nb;
-        t.in = D_.p; t.sgn = T(1); t.v = S_[order[0]].p; t.mode = 1; t.j = 0; t.apply_H = 0; t.H = T(1);
+        t.in = D_.p; t.sgn = T(1); t.v = S_[state_.lbfgs.order[0]].p; t.mode = 1; t.j = 0; t.apply_H = 0; t.H = T(1);
         t.src = multi ? ScalarSrc{pglobal_.p + 2, 1, 1} : src(SL_LOOP2 + 0);
-        t.ys = ys_[order[0]];
+        t.ys = state_.lbfgs.ys[state_.lbfgs.order[0]];
         return t;
     }
     int persist_blocks() const { return pblocks; }
@@ -2413,24 +2286,24 @@ template <class T> class Solver final : public SolverBase {
         TailArgs<T> t;
         std::memset(&t, 0, sizeof(t));
         t.alphas = alphas_.p;
-        const int m = (int)order.size();
+        const int m = (int)state_.lbfgs.order.size();
         slot_n[SL_LOOP2 + 0] = grid;
         const T* res = RES_[rc].p;
         if (m == 0) {
-            t.in = res; t.v = nullptr; t.sgn = T(-1); t.mode = 2; t.apply_H = 1; t.H = H;
+            t.in = res; t.v = nullptr; t.sgn = T(-1); t.mode = 2; t.apply_H = 1; t.H = state_.lbfgs.H;
             t.src = ScalarSrc{parts_.p, 0, 1}; t.ys = T(1);
             return t;
         }
         mv(2);
-        launch(C_DOT, k_dot<T>, grid, (const T*)S_[order[0]].p, res, T(-1), n, parts_.p, SL_LOOP1 + 0);
+        launch(C_DOT, k_dot<T>, grid, (const T*)S_[state_.lbfgs.order[0]].p, res, T(-1), n, parts_.p, SL_LOOP1 + 0);
         gather(SL_LOOP1 + 0, 1, 0u);
         for (int j = 0; j + 1 < m; ++j) {        // loop 1: d -= alpha_j y_j ; <s_{j+1}, d>
             TailArgs<T> a = t;
             a.in = (j == 0) ? res : (const T*)D_.p; a.sgn = (j == 0) ? T(-1) : T(1);
-            a.v = Y_[order[j]].p; a.mode = 0; a.j = j; a.apply_H = 0; a.H = T(1);
-            a.src = src(SL_LOOP1 + j); a.ys = ys_[order[j]];
+            a.v = Y_[state_.lbfgs.order[j]].p; a.mode = 0; a.j = j; a.apply_H = 0; a.H = T(1);
+            a.src = src(SL_LOOP1 + j); a.ys = state_.lbfgs.ys[state_.lbfgs.order[j]];
             mv(4); nm("k_axpy_dot");
-            launch(C_TWOLOOP, k_axpy_dot<T>, grid, a, (const T*)S_[order[j + 1]].p, (const T*)nullptr,
+            launch(C_TWOLOOP, k_axpy_dot<T>, grid, a, (const T*)S_[state_.lbfgs.order[j + 1]].p, (const T*)nullptr,
                    D_.p, n, parts_.p, SL_LOOP1 + j + 1);
             gather(SL_LOOP1 + j + 1, 1, 0u);
         }
@@ -2438,24 +2311,24 @@ template <class T> class Solver final : public SolverBase {
             TailArgs<T> a = t;
             const int j = m - 1;
             a.in = (m == 1) ? res : (const T*)D_.p; a.sgn = (m == 1) ? T(-1) : T(1);
-            a.v = Y_[order[j]].p; a.mode = 0; a.j = j; a.apply_H = 1; a.H = H;
-            a.src = src(SL_LOOP1 + j); a.ys = ys_[order[j]];
+            a.v = Y_[state_.lbfgs.order[j]].p; a.mode = 0; a.j = j; a.apply_H = 1; a.H = state_.lbfgs.H;
+            a.src = src(SL_LOOP1 + j); a.ys = state_.lbfgs.ys[state_.lbfgs.order[j]];
             mv(3);
-            launch(C_TWOLOOP, k_axpy_dot<T>, grid, a, (const T*)Y_[order[j]].p, (const T*)nullptr, D_.p,
+            launch(C_TWOLOOP, k_axpy_dot<T>, grid, a, (const T*)Y_[state_.lbfgs.order[j]].p, (const T*)nullptr, D_.p,
                    n, parts_.p, SL_LOOP2 + j);
             gather(SL_LOOP2 + j, 1, 0u);
         }
         for (int j = m - 1; j >= 1; --j) {         // loop 2: d += (alpha_j - beta_j) s_j ; <y_{j-1}, d>
             TailArgs<T> a = t;
-            a.in = D_.p; a.sgn = T(1); a.v = S_[order[j]].p; a.mode = 1; a.j = j; a.apply_H = 0;
-            a.H = T(1); a.src = src(SL_LOOP2 + j); a.ys = ys_[order[j]];
+            a.in = D_.p; a.sgn = T(1); a.v = S_[state_.lbfgs.order[j]].p; a.mode = 1; a.j = j; a.apply_H = 0;
+            a.H = T(1); a.src = src(SL_LOOP2 + j); a.ys = state_.lbfgs.ys[state_.lbfgs.order[j]];
             mv(4);
-            launch(C_TWOLOOP, k_axpy_dot<T>, grid, a, (const T*)Y_[order[j - 1]].p, (const T*)nullptr,
+            launch(C_TWOLOOP, k_axpy_dot<T>, grid, a, (const T*)Y_[state_.lbfgs.order[j - 1]].p, (const T*)nullptr,
                    D_.p, n, parts_.p, SL_LOOP2 + j - 1);
             gather(SL_LOOP2 + j - 1, 1, 0u);
         }
-        t.in = D_.p; t.sgn = T(1); t.v = S_[order[0]].p; t.mode = 1; t.j = 0; t.apply_H = 0; t.H = T(1);
-        t.src = src(SL_LOOP2 + 0); t.ys = ys_[order[0]];
+        t.in = D_.p; t.sgn = T(1); t.v = S_[state_.lbfgs.order[0]].p; t.mode = 1; t.j = 0; t.apply_H = 0; t.H = T(1);
+        t.src = src(SL_LOOP2 + 0); t.ys = state_.lbfgs.ys[state_.lbfgs.order[0]];
         return t;
     }
 
@@ -2485,9 +2358,9 @@ template <class T> class Solver final : public SolverBase {
         stencil_fast_ = desc.f_kind == BZ_F_STENCIL5 && o.fuse && !lp_g && !slack;
         if (o.affine_refresh < 0) throw Error(BZ_ERR_ARG, "affine_refresh must be >= 0");
         aff_refresh_ = o.affine_refresh;
-        aff_track_ = affine_ok_ && aff_refresh_ > 0 && o.lbfgs_compact != 0 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS;
-        compact_ok = M >= 1 && (o.lbfgs_compact == 1 || dir_kind_ == BZ_DIR_ANDERSON ||
-                                (o.lbfgs_compact == 2 && (fused_ok || stencil_fast_ || aff_track_) && M <= CM));
+        aff_track_ = affine_ok_ && aff_refresh_ > 0 && o.lbfgs_compact != 0 && state_.lbfgs.M >= 1 && state_.lbfgs.M <= CM && dir_kind_ == BZ_DIR_LBFGS;
+        compact_ok = state_.lbfgs.M >= 1 && (o.lbfgs_compact == 1 || dir_kind_ == BZ_DIR_ANDERSON ||
+                                (o.lbfgs_compact == 2 && (fused_ok || stencil_fast_ || aff_track_) && state_.lbfgs.M <= CM));
         // persistent two-loop: d must fit the register files (<= 40 packs per thread, one 512-thread
         // block per CU) and the vector must be long enough for 2m-1 grid barriers to beat 2m launches;
         // with several ranks the phases need the p2p mailboxes (RCCL cannot be called from a kernel)
@@ -2495,7 +2368,7 @@ template <class T> class Solver final : public SolverBase {
                      !persist_broken_;
         if (ctx->nranks > 1 && !ctx->multi())
             throw Error(BZ_ERR_STATE, "nranks > 1 needs an RCCL communicator or connected p2p mailboxes");
-        if (ctx->nranks > 1 && o.persist && M >= 1) {
+        if (ctx->nranks > 1 && o.persist && state_.lbfgs.M >= 1) {
             // the shards may straddle a threshold (length, register budget): the phases of the persistent kernel
             // and the exchanges of the kernel chain do not talk to each other, so all ranks must take the same
             // form — the persistent one only if every rank can
@@ -2508,7 +2381,7 @@ template <class T> class Solver final : public SolverBase {
         // persistent kernel's register capacity — e.g. the lifted vector [x; s] of ALS at n = 1e7 — or too short for its
         // grid barriers) the compact form does the same work in two launches and 4m + 11 passes instead of 8m + 1
         // (ALS at n = 1e7: 741 against 519 it/s).  Several ranks keep the rule above: they must agree on one form.
-        if (!compact_ok && o.lbfgs_compact == 2 && M >= 1 && M <= CM && dir_kind_ == BZ_DIR_LBFGS && !ctx->multi() && !persist_ok &&
+        if (!compact_ok && o.lbfgs_compact == 2 && state_.lbfgs.M >= 1 && state_.lbfgs.M <= CM && dir_kind_ == BZ_DIR_LBFGS && !ctx->multi() && !persist_ok &&
             !generic_)
             compact_ok = true;
     }
@@ -2525,7 +2398,7 @@ template <class T> class Solver final : public SolverBase {
         if (o.lbfgs_memory < 0 || o.lbfgs_memory > MAX_MEM)
             throw Error(BZ_ERR_ARG, "lbfgs_memory must be in 0..16 (0 = NoAcceleration)");
         if (o.max_backtracks < 1) throw Error(BZ_ERR_ARG, "max_backtracks must be >= 1");
-        M = o.lbfgs_memory;
+        int M = o.lbfgs_memory;
         if (o.directions != BZ_DIR_LBFGS && o.directions != BZ_DIR_ANDERSON && o.directions != BZ_DIR_BROYDEN)
             throw Error(BZ_ERR_ARG, "unknown `directions`");
         dir_kind_ = o.directions;
@@ -2542,8 +2415,8 @@ template <class T> class Solver final : public SolverBase {
                 if (GT_.n < (size_t)b_nch_ * npad) GT_.alloc((size_t)b_nch_ * npad);
             }
         }
+        state_.lbfgs.reset_all(M);
         alloc_history();
-        lbfgs_reset_all();
         if (dir_kind_ == BZ_DIR_BROYDEN) broyden_reset();
         if (o.lbfgs_compact < 0 || o.lbfgs_compact > 2) throw Error(BZ_ERR_ARG, "lbfgs_compact must be 0, 1 or 2 (auto)");
         if (o.lbfgs_compact == 1 && M > CM) throw Error(BZ_ERR_ARG, "lbfgs_compact supports lbfgs_memory <= 5");
@@ -2556,11 +2429,11 @@ template <class T> class Solver final : public SolverBase {
         // size the estimate is always backtracked, whatever `adaptive` says)
         adaptive_ = !(gamma_given_ > T(0)) || o.adaptive == 1;
         select_paths(o);
-        aff_count_ = 0; n_affine_ = 0; n_affine_blends_ = 0; n_gated_ = 0; n_gate_aborts_ = 0; n_dense_onepass_ = 0;
+        state_.aff_count = 0; state_.n_affine = 0; state_.n_affine_blends = 0; n_gated_ = 0; n_gate_aborts_ = 0; n_dense_onepass_ = 0;
         t_begin = std::chrono::steady_clock::now();
-        k_ = 1; n_grad = n_prox = n_bt = n_halv = n_fused = n_skips = 0;
-        last_nbt = 0; last_fused = false; tau = T(0); last_ys = T(0); fbe_last = T(0);
-        xc = 0; rc = 0; zc = 0; z_valid = true; xr_run_ = 0; sy_stale_ = false; res_valid = true;
+        cnt_.k = 1; cnt_.n_grad = cnt_.n_prox = cnt_.n_bt = cnt_.n_halv = cnt_.n_fused = cnt_.n_skips = 0;
+        last_nbt = 0; last_fused = false; tau = T(0); last_ys = T(0); state_.fbe_last = T(0);
+        xc = 0; rc = 0; zc = 0; state_.z_valid = true; xr_run_ = 0; sy_stale_ = false; state_.res_valid = true;
         // BZ_GATE: 0 off; non-zero (default) the early launch queues behind the read-back on the solver's stream
         // Several ranks: off unless asked for (BZ_GATE=1).  A launch that misses its gate cannot be redone there (the peers
         // have consumed this rank's scalars: BZ_ERR_COMM), and gated launches on distinct devices have never run on
@@ -2583,16 +2456,16 @@ template <class T> class Solver final : public SolverBase {
             mv(2 + pstreams(true, true, false));
             launch(C_ALGRAD, k_begin_lip<T>, grid, (const T*)x, P, GX_.p, n, parts_.p, (int)SL_FXD, (int)SL_AUX);
             gather(SL_FXD, 2, 0u);
-            n_grad += 2; gx_valid = true;
+            cnt_.n_grad += 2; state_.gx_valid = true;
         } else {
             if (aff_track_) cx_keep_ = CXS_.p;
-            algrad(x, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
+            algrad(x, GX_.p, SL_FXD); ++cnt_.n_grad; state_.gx_valid = true;
             cx_keep_ = nullptr;
             if (!(gamma_given_ > T(0))) {
                 // gamma = alpha / lower_bound_smoothness_constant(f, I, x, grad_f_x)
                 mv(2);
                 launch(C_MISC, k_add_scalar<T>, grid, (const T*)x, T(1), TMP_.p, n);
-                algrad(TMP_.p, GZ_.p, SL_FZ); ++n_grad;
+                algrad(TMP_.p, GZ_.p, SL_FZ); ++cnt_.n_grad;
                 mv(4);
                 launch(C_MISC, k_diff_ss2<T>, grid, (const T*)GZ_.p, (const T*)GX_.p, (const T*)TMP_.p, (const T*)x, n,
                        parts_.p, (int)SL_AUX);
@@ -2601,15 +2474,15 @@ template <class T> class Solver final : public SolverBase {
         if (gamma_given_ > T(0)) {
             // gamma given (or Lf): no Lipschitz estimate; the one-pass start above computed it for free and it is ignored
             auto v = collect({SL_FXD, SL_PXD}, 0u);
-            f_x = al_value(v[0], v[1]);
-            gamma = gamma_given_;
+            state_.f_x = al_value(v[0], v[1]);
+            state_.gamma = gamma_given_;
         } else {
             slot_n[SL_AUX] = slot_n[SL_AUX + 1] = grid;
             gather(SL_AUX, 2, 0u);
             auto v = collect({SL_FXD, SL_PXD, SL_AUX, SL_AUX + 1}, 0u);
-            f_x = al_value(v[0], v[1]);
+            state_.f_x = al_value(v[0], v[1]);
             const T Lest = std::sqrt(T(v[2])) / std::sqrt(T(v[3]));
-            gamma = alpha / Lest;
+            state_.gamma = alpha / Lest;
         }
         // y = x - gamma grad ; z, g_z = prox(g, y, gamma) ; res = x - z ; backtrack_stepsize!
         T f_z = T(0);
@@ -2621,50 +2494,50 @@ template <class T> class Solver final : public SolverBase {
                 // FB step, gradient at z and stop norm in one pass (k_begin_fb)
                 for (int k = 0; k < 8; ++k) slot_n[SL_GSUM + k] = grid;
                 mv(4 + pstreams(true, true, true));
-                launch(C_FB, k_begin_fb<T>, grid, (const T*)x, (const T*)GX_.p, gamma, P, Z_[zc].p, RES_[rc].p, n,
+                launch(C_FB, k_begin_fb<T>, grid, (const T*)x, (const T*)GX_.p, state_.gamma, P, Z_[zc].p, RES_[rc].p, n,
                        parts_.p, (int)SL_GSUM);
                 gather(SL_GSUM, 8, 1u << 7);
-                ++n_prox; ++n_grad; gz_valid = false;
+                ++cnt_.n_prox; ++cnt_.n_grad; state_.gz_valid = false;
                 v = collect({SL_GSUM, SL_DOT, SL_SS, SL_FZ, SL_PZ, SL_STOP}, 1u << 5);
                 stop0 = v[5];
             } else {
-                fbstep(x, GX_.p, gamma, Z_[zc].p, RES_[rc].p, SL_GSUM);
+                fbstep(x, GX_.p, state_.gamma, Z_[zc].p, RES_[rc].p, SL_GSUM);
                 gather(SL_GSUM, 3, 0u);
-                ++n_prox;
+                ++cnt_.n_prox;
                 if (aff_track_) cx_keep_ = CZS_.p;
-                algrad(Z_[zc].p, GZ_.p, SL_FZ); ++n_grad; gz_valid = true;
+                algrad(Z_[zc].p, GZ_.p, SL_FZ); ++cnt_.n_grad; state_.gz_valid = true;
                 cx_keep_ = nullptr;
                 v = collect({SL_GSUM, SL_DOT, SL_SS, SL_FZ, SL_PZ}, 0u);
             }
-            g_z = g_value(v[0]); dot_gr = T(v[1]); ss_res = T(v[2]);
-            f_z = al_value(v[3], v[4]); fraw_last = f_value(v[3]); f_z_al = f_z;
-            const T nr = std::sqrt(ss_res);
-            const T f_z_upp = f_x - dot_gr + ((alpha / gamma) / T(2)) * (nr * nr);
+            state_.g_z = g_value(v[0]); state_.dot_gr = T(v[1]); state_.ss_res = T(v[2]);
+            f_z = al_value(v[3], v[4]); state_.fraw_last = f_value(v[3]); state_.f_z_al = f_z;
+            const T nr = std::sqrt(state_.ss_res);
+            const T f_z_upp = state_.f_x - state_.dot_gr + ((alpha / state_.gamma) / T(2)) * (nr * nr);
             const T tol = T(10) * eps * (T(1) + std::abs(f_z));
             // (upstream: `if (iter.gamma === nothing || iter.adaptive == true)` backtrack_stepsize!)
             // (an infinite gamma — a zero Lipschitz estimate: grad F(x + 1) = grad F(x), e.g. f = Zero in the slack form — cannot be
             // halved: the reference's loop compares NaNs there and leaves; here f(z) may come out +inf, so say it explicitly)
-            if (adaptive_ && std::isfinite((double)gamma) && f_z > f_z_upp + tol && gamma >= min_gamma) {
-                gamma = gamma / T(2); ++n_halv;
+            if (adaptive_ && std::isfinite((double)state_.gamma) && f_z > f_z_upp + tol && state_.gamma >= min_gamma) {
+                state_.gamma = state_.gamma / T(2); ++cnt_.n_halv;
                 continue;
             }
             break;
         }
-        if (gamma < min_gamma)
-            std::fprintf(stderr, "Warning: stepsize `gamma` became too small (%g)\n", (double)gamma);
+        if (state_.gamma < min_gamma)
+            std::fprintf(stderr, "Warning: stepsize `gamma` became too small (%g)\n", (double)state_.gamma);
         if (fused_fb) {
             stop_norm_ = stop0;
         } else {
             for (int k = 0; k < 3; ++k) slot_n[SL_YS + k] = grid;
             mv(4);
             launch(C_UPDATE, k_update<T>, grid, (const T*)x, (const T*)nullptr, (const T*)RES_[rc].p,
-                   (const T*)nullptr, (const T*)GX_.p, (const T*)GZ_.p, gamma, (T*)nullptr, (T*)nullptr, n,
+                   (const T*)nullptr, (const T*)GX_.p, (const T*)GZ_.p, state_.gamma, (T*)nullptr, (T*)nullptr, n,
                    parts_.p, (int)SL_YS);
             gather(SL_YS, 3, 4u);
             auto v = collect({SL_STOP}, 1u);
             stop_norm_ = v[0];
         }
-        gring_[xc] = (double)gamma;
+        gring_[xc] = (double)state_.gamma;
         active = true;
     }
 
@@ -2673,9 +2546,9 @@ template <class T> class Solver final : public SolverBase {
         for (;;) {
             const bool stop = should_stop();
             if (stop) gate_abort();              // (a pass pre-launched for an iteration that will not happen)
-            if (opt.verbose && (stop || (opt.freq > 0 && k_ % opt.freq == 0))) display();
+            if (opt.verbose && (stop || (opt.freq > 0 && cnt_.k % opt.freq == 0))) display();
             if (stop) break;
-            more_coming_ = k_ + 1 < opt.maxit;   // the solver's own loop: another iteration follows unless this one stops it
+            more_coming_ = cnt_.k + 1 < opt.maxit;      // the solver's own loop: another iteration follows unless this one stops it
             step();
         }
     }
@@ -2687,7 +2560,7 @@ template <class T> class Solver final : public SolverBase {
         launch(C_MISC, k_absmax<T>, grid, (const T*)RES_[rc].p, n, parts_.p, (int)SL_AUX);
         gather(SL_AUX, 1, 1u);
         auto v = collect({SL_AUX}, 1u);
-        std::printf("%5lld | %.3e | %.3e | %.3e\n", (long long)k_, (double)gamma, v[0] / (double)gamma,
+        std::printf("%5lld | %.3e | %.3e | %.3e\n", (long long)cnt_.k, (double)state_.gamma, v[0] / (double)state_.gamma,
                     (double)tau);
     }
 
@@ -2717,17 +2590,14 @@ template <class T> class Solver final : public SolverBase {
         // that gave up there (the host was descheduled for seconds, or the GPU has another tenant).  The iteration is
         // simply redone — with the kernel chain, without the gate — and the form that failed stays off for this
         // problem.  Whatever else goes wrong leaves with no launch waiting at a gate.
-        const int64_t sv[7] = {k_, n_grad, n_prox, n_bt, n_halv, n_fused, n_skips};
+        const IterCounters sv = cnt_;
         const unsigned long long sv_pseq = ctx->pseq;
-        auto restore = [&]() {
-            k_ = sv[0]; n_grad = sv[1]; n_prox = sv[2]; n_bt = sv[3]; n_halv = sv[4]; n_fused = sv[5]; n_skips = sv[6];
-            gx_valid = false; gz_valid = false;
-        };
+        auto restore = [&]() { cnt_ = sv; state_.gx_valid = false; state_.gz_valid = false; };
         // (a one-pass dense timeout is seen at a read-back of the iteration, possibly a later one than the first: by then the
         // attempt may have traded the image buffers, halved gamma, reset the memory and replaced the state's scalars)
         // (only the one-pass kernel reports such a timeout: other problems skip the snapshot)
-        std::optional<StepState> sv_state;
-        if (dense_fused_on()) sv_state = save_state();
+        std::optional<IterState> sv_state;
+        if (dense_fused_on()) sv_state = snapshot();
         try {
             try {
                 step_impl();
@@ -2748,9 +2618,9 @@ template <class T> class Solver final : public SolverBase {
                 gate_abort();
                 BZ_HIP(hipStreamSynchronize(ctx->stream));
                 *ptimeout_ = 0;
-                if (!sv_state || (dir_kind_ == BZ_DIR_BROYDEN && n_halv != sv[4])) throw;      // (a halving resets Broyden's operator itself)
+                if (!sv_state || (dir_kind_ == BZ_DIR_BROYDEN && cnt_.n_halv != sv.n_halv)) throw;      // (a halving resets Broyden's operator itself)
                 restore();
-                load_state(*sv_state);
+                put_back(*sv_state);
                 std::fprintf(stderr, "Warning: the one-pass dense kernel timed out (is the GPU shared?); using the two-kernel form\n");
                 step_impl();
             } catch (const PersistTimeout&) {
@@ -2773,51 +2643,25 @@ template <class T> class Solver final : public SolverBase {
         }
         if (!more_coming_) gate_abort();
     }
-    int64_t n_persist_fallbacks_ = 0;
    private:
-    // What step_impl changes before its last read-back (the ring indices, the pair insertion and the stop norm are committed
-    // after it): the state's scalars, the L-BFGS bookkeeping (a halving resets it), the affine-image buffers — traded by
-    // pointer, and only the candidates (GXN_, GZN_, CXD_, CZN_) and the spare pair's images are written — and the image
-    // counters.  Put back, the iteration can be redone from the state it started from, images and memory included.
-    struct StepState {
-        T gamma, f_x, g_z, dot_gr, ss_res, f_z_al, fraw_last, fbe_last, H;
-        std::deque<int> order;
-        std::vector<int> freeslots;
-        int gm, aff_count;
-        bool pw_valid, gx_valid, gz_valid, z_valid, res_valid;
-        double hp[CM], hw[CM];
-        int64_t n_affine, n_affine_verify, n_affine_blends;
-        T* img_p[8];
-        size_t img_n[8];
-    };
+    // the affine-image buffers in the order of IterState::img
     std::array<DBuf<T>*, 8> image_bufs() { return {&GX_, &GXN_, &GZ_, &GZN_, &CXS_, &CXD_, &CZS_, &CZN_}; }
-    StepState save_state() {
-        StepState st;
-        st.gamma = gamma; st.f_x = f_x; st.g_z = g_z; st.dot_gr = dot_gr; st.ss_res = ss_res; st.f_z_al = f_z_al;
-        st.fraw_last = fraw_last; st.fbe_last = fbe_last; st.H = H;
-        st.order = order; st.freeslots = freeslots; st.gm = gm; st.aff_count = aff_count_;
-        st.pw_valid = pw_valid; st.gx_valid = gx_valid; st.gz_valid = gz_valid; st.z_valid = z_valid; st.res_valid = res_valid;
-        for (int i = 0; i < CM; ++i) { st.hp[i] = hp_[i]; st.hw[i] = hw_[i]; }
-        st.n_affine = n_affine_; st.n_affine_verify = n_affine_verify_; st.n_affine_blends = n_affine_blends_;
+    IterState snapshot() {
+        IterState sv = state_;
         const auto b = image_bufs();
-        for (int i = 0; i < 8; ++i) { st.img_p[i] = b[i]->p; st.img_n[i] = b[i]->n; }
-        return st;
+        for (int i = 0; i < 8; ++i) sv.img[i] = ImageRef{b[i]->p, b[i]->n};
+        return sv;
     }
-    void load_state(const StepState& st) {
-        gamma = st.gamma; f_x = st.f_x; g_z = st.g_z; dot_gr = st.dot_gr; ss_res = st.ss_res; f_z_al = st.f_z_al;
-        fraw_last = st.fraw_last; fbe_last = st.fbe_last; H = st.H;
-        order = st.order; freeslots = st.freeslots; gm = st.gm; aff_count_ = st.aff_count;
-        pw_valid = st.pw_valid; z_valid = st.z_valid; res_valid = st.res_valid;
-        for (int i = 0; i < CM; ++i) { hp_[i] = st.hp[i]; hw_[i] = st.hw[i]; }
-        n_affine_ = st.n_affine; n_affine_verify_ = st.n_affine_verify; n_affine_blends_ = st.n_affine_blends;
+    void put_back(const IterState& sv) {
+        state_ = sv;
         const auto b = image_bufs();
-        for (int i = 0; i < 8; ++i) { b[i]->p = st.img_p[i]; b[i]->n = st.img_n[i]; }
+        for (int i = 0; i < 8; ++i) { b[i]->p = sv.img[i].p; b[i]->n = sv.img[i].n; }
         cx_keep_ = nullptr;
         // without images the attempt wrote grad L at its trial points into GX_ and GZ_ themselves (the redo evaluates them)
-        gx_valid = aff_track_ && st.gx_valid; gz_valid = aff_track_ && st.gz_valid;
+        state_.gx_valid = aff_track_ && sv.gx_valid; state_.gz_valid = aff_track_ && sv.gz_valid;
     }
     // ---- one iteration (step_impl), stage by stage.  Iter holds what lives inside the iteration only: the state it changes
-    // is in members, which save_state / load_state cover.
+    // is in state_ and cnt_, which step() snapshots.
     static constexpr int NFC = 10 + 4 * CM + 2;                          // slots of k_fused_compact
     static_assert(SL_TRIAL + NFC <= SL_AUX, "k_fused_compact's slots overlap the next group");
     struct Iter {
@@ -2846,7 +2690,7 @@ template <class T> class Solver final : public SolverBase {
         int m_gram;                  // ... measured against a memory of this many pairs
     };
     void step_impl() {
-        ++k_;
+        ++cnt_.k;
         Iter it;
         open_iteration(it);
         if (fused_ok && it.use_compact) trial_onepass(it);
@@ -2857,20 +2701,20 @@ template <class T> class Solver final : public SolverBase {
     }
     // the FBE at the current state, which paths apply, the direction d = H(-res) (all but the last axpy), the ring indices
     void open_iteration(Iter& it) {
-        it.nr0 = std::sqrt(ss_res);
-        it.FBE_x = (f_x - dot_gr + ((alpha / gamma) / T(2)) * (it.nr0 * it.nr0)) + g_z;
-        fbe_last = it.FBE_x;
+        it.nr0 = std::sqrt(state_.ss_res);
+        it.FBE_x = (state_.f_x - state_.dot_gr + ((alpha / state_.gamma) / T(2)) * (it.nr0 * it.nr0)) + state_.g_z;
+        state_.fbe_last = it.FBE_x;
         // (headline family: the one-pass kernel also serves an EMPTY memory — d = H0 (-res), all coefficients zero —
         // so the first iteration of a solve is a 3..5-stream pass too instead of k_fused_sep's 12)
         // (the stencil fast path also serves a row-sharded grid: the halo rows of x_d and of z travel before the two
         // passes, and with the compact form the iteration has ONE scalar exchange — the 32 slots of k_stencil_update_c)
         it.stencil_fast_now = stencil_fast_ && (!ctx->multi() || (ctx->p2p_on && compact_ok));
-        it.use_compact = compact_ok && (!order.empty() || (fused_ok && fused_family() >= 0) || it.stencil_fast_now || aff_track_);
-        const bool use_persist = persist_ok && !order.empty() && !it.use_compact;
+        it.use_compact = compact_ok && (!state_.lbfgs.order.empty() || (fused_ok && fused_family() >= 0) || it.stencil_fast_now || aff_track_);
+        const bool use_persist = persist_ok && !state_.lbfgs.order.empty() && !it.use_compact;
         if (it.use_compact) { it.CV = compact_vecs(); it.CC = compact_prepare(it.CV); std::memset(&it.tail, 0, sizeof(it.tail)); }
-        else if (dir_kind_ == BZ_DIR_BROYDEN) { if (!res_valid) ensure_z(); it.tail = broyden_dir(); }
+        else if (dir_kind_ == BZ_DIR_BROYDEN) { if (!state_.res_valid) ensure_z(); it.tail = broyden_dir(); }
         else it.tail = use_persist ? two_loop_persist() : two_loop();
-        it.m_at_trial = it.m_gram = (int)order.size();
+        it.m_at_trial = it.m_gram = (int)state_.lbfgs.order.size();
         tau = T(1);
         it.xp = xc; it.xd = (xc + 1) % NXR; it.xb = (xc + 2) % NXR;
         it.rp = rc; it.rn = (rc + 1) % NRR; it.zp = zc; it.zn = 1 - zc;
@@ -2897,24 +2741,24 @@ template <class T> class Solver final : public SolverBase {
         // with 180 inner iterations in all on cfg 2), and a stored z costs a tenth of re-materialising one
         // (tol = 0: the caller has said the solve never stops by itself — bench.py's timed region, the step-wise parity
         // tests — so no early stop is being prepared for; whoever asks for z gets it re-materialised, same bits)
-        const bool near_stop = (double)stop_norm_ <= 10.0 * opt.tol || (k_ <= 20 && opt.tol > 0.0);
+        const bool near_stop = (double)stop_norm_ <= 10.0 * opt.tol || (cnt_.k <= 20 && opt.tol > 0.0);
         T* const zstore = (env_.skipz && !near_stop) ? (T*)nullptr : Z_[it.zn].p;
         it.z_skipped = zstore == nullptr;
         const bool small = small_vectors();
         // 0: stored pairs; 2: pairs re-formed from the iterate ring, residuals re-evaluated — possible as soon as every
         // stored pair is a difference of ring neighbours, also with a partial memory (the absent pairs are x - x = 0 with
         // zero coefficients)
-        const int m_now = (int)order.size();
+        const int m_now = (int)state_.lbfgs.order.size();
         int xr = 0;
         // (the slack form of ALS has its own iterate-history kernel, k_fused_slack_xr: any element-wise kinds)
         if (env_.xr && small && (fam >= 0 || slack) && xr_run_ >= m_now) {
             xr = 2;
             // (only the oldest stored iterate may carry another gamma — see CompactCoef::gam0)
             for (int i = 1; i < m_now; ++i)
-                if (gring_[(xc - m_now + i + NXR) % NXR] != (double)gamma) xr = 0;
+                if (gring_[(xc - m_now + i + NXR) % NXR] != (double)state_.gamma) xr = 0;
         }
         if (sy_stale_ && !xr) materialize_pairs();
-        if (xr != 2 && !res_valid) ensure_z();
+        if (xr != 2 && !state_.res_valid) ensure_z();
         // the iterate-history form keeps two packs of loads in flight per wave and runs best with ONE wave per
         // SIMD (n = 1e7: 134 vs 140 us; 1.25e6: 28.5 vs 30.2 us): the wave has the vector ALU to itself and
         // the 32-scalar epilogue runs half as often.  (A different grid is a different summation tree: the
@@ -2938,8 +2782,8 @@ template <class T> class Solver final : public SolverBase {
         // (XR = 2 with the gate: the read-back kernel now, so that the next iteration's pass can queue right behind it)
         onepass_scalars(it, xr == 2 && gate_env_);
         if (xr == 2 && gate_env_ && more_coming_ && !opt.verbose && !prof_would_pick(C_FUSED_IT)) gate_prelaunch(it.xd, m_now);
-        it.have_trial = true; it.fused_this = true; gx_valid = false; gz_valid = false; it.gram_from_trial = true;
-        n_grad += 2; n_prox += 1;
+        it.have_trial = true; it.fused_this = true; state_.gx_valid = false; state_.gz_valid = false; it.gram_from_trial = true;
+        cnt_.n_grad += 2; cnt_.n_prox += 1;
     }
     // the one-pass trial's scalars: exchanged, folded over the ranks and read back in one launch (p2p, no k_collect), or
     // gathered and, with launch_now, their read-back launched at once (wait_host later)
@@ -2955,7 +2799,7 @@ template <class T> class Solver final : public SolverBase {
     // ALS: the iterate-history pass of the lifted vector (k_fused_slack_xr)
     void onepass_slack_xr(Iter& it, int gfc, T* zstore, bool fast, bool hk) {
         // the m + 1 last iterates of the lifted vector (both halves), the parameter vectors, y ; xs_d (z) out
-        const int m_now = (int)order.size();
+        const int m_now = (int)state_.lbfgs.order.size();
         SlackIterates<T, CM> SV;
         std::memset(&SV, 0, sizeof(SV));
         SV.m = m_now;
@@ -2968,7 +2812,7 @@ template <class T> class Solver final : public SolverBase {
         // (the fast instantiations: a full memory, f = DiagQuadratic, no vector-valued parameters of g or D)
         if (fast) form_[C_FUSED_IT] += hk ? "(fast,l1-box)" : "(fast)";
         auto go = [&](auto kernel) {
-            launch(C_FUSED_IT, kernel, gfc, SV, it.CC, P, (const T*)ymul_.p, gamma, X_[it.xd].p, zstore, nx, parts_.p, (int)SL_TRIAL);
+            launch(C_FUSED_IT, kernel, gfc, SV, it.CC, P, (const T*)ymul_.p, state_.gamma, X_[it.xd].p, zstore, nx, parts_.p, (int)SL_TRIAL);
         };
         with_bool(snt, [&](auto nt_) {
             constexpr bool NT = decltype(nt_)::value;
@@ -2987,7 +2831,7 @@ template <class T> class Solver final : public SolverBase {
     // the headline or family-table pass on the iterate history (k_fused_compact<XR=2>): released if it was pre-launched
     void onepass_xr2(Iter& it, T* zstore) {
         GatePlan cur;
-        if (!xr2_plan(xc, (int)order.size(), gring_, xr_run_, zstore != nullptr, cur))
+        if (!xr2_plan(xc, (int)state_.lbfgs.order.size(), gring_, xr_run_, zstore != nullptr, cur))
             throw Error(BZ_ERR_STATE, "the iterate-history pass does not apply");
         it.CC.gam0 = cur.gam0;
         if (gate_pending_ && cur == gate_plan_) {
@@ -3010,8 +2854,8 @@ template <class T> class Solver final : public SolverBase {
             form_[C_FUSED] = std::string("k_fused_slack") + (nt ? "<NT=1>" : "<NT=0>");
             with_bool(nt, [&](auto nt_) {
                 launch(C_FUSED, k_fused_slack<T, CM, decltype(nt_)::value>, gfc, it.CV, it.CC, (const T*)X_[it.xp].p,
-                       (const T*)RES_[it.rp].p, P, (const T*)ymul_.p, gamma, X_[it.xd].p, zstore, RES_[it.rn].p, S_[spare].p,
-                       Y_[spare].p, nx, parts_.p, (int)SL_TRIAL);
+                       (const T*)RES_[it.rp].p, P, (const T*)ymul_.p, state_.gamma, X_[it.xd].p, zstore, RES_[it.rn].p, S_[state_.lbfgs.spare].p,
+                       Y_[state_.lbfgs.spare].p, nx, parts_.p, (int)SL_TRIAL);
             });
             return;
         }
@@ -3019,8 +2863,8 @@ template <class T> class Solver final : public SolverBase {
         mv(2 + 2 * it.CV.m + pstreams(true, true, true) + 4 + (zstore ? 1 : 0));
         form_[C_FUSED] = std::string("k_fused_compact<XR=0") + (spec ? ",SPEC=1" : ",SPEC=0") + (nt ? ",NT=1>" : ",NT=0>");
         auto go = [&](auto kernel) {
-            launch(C_FUSED, kernel, gfc, it.CV, it.CC, (const T*)X_[it.xp].p, (const T*)RES_[it.rp].p, P, gamma, X_[it.xd].p,
-                   zstore, RES_[it.rn].p, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL);
+            launch(C_FUSED, kernel, gfc, it.CV, it.CC, (const T*)X_[it.xp].p, (const T*)RES_[it.rp].p, P, state_.gamma, X_[it.xd].p,
+                   zstore, RES_[it.rn].p, S_[state_.lbfgs.spare].p, Y_[state_.lbfgs.spare].p, n, parts_.p, (int)SL_TRIAL);
         };
         if (off32 && nt) go(k_fused_compact<T, CM, true, true, true>);
         else if (off32) go(k_fused_compact<T, CM, false, true, true>);
@@ -3031,26 +2875,26 @@ template <class T> class Solver final : public SolverBase {
     }
     // k_fused_sep: the one-pass kernel of the element-wise kinds with the two-loop / Broyden direction
     void trial_sep(Iter& it) {
-        if (!res_valid) ensure_z();
+        if (!state_.res_valid) ensure_z();
         for (int k = 0; k < 12; ++k) slot_n[SL_TRIAL + k] = grid;
         mv((it.tail.mode != 2 ? 2 : 1) + 2 + pstreams(true, true, true) + 5);
         form_[C_FUSED] = "k_fused_sep";
-        launch(C_FUSED, k_fused_sep<T>, grid, it.tail, (const T*)X_[it.xp].p, (const T*)RES_[it.rp].p, P, gamma,
-               X_[it.xd].p, Z_[it.zn].p, RES_[it.rn].p, S_[spare].p, Y_[spare].p, (T*)nullptr, (T*)nullptr, n,
+        launch(C_FUSED, k_fused_sep<T>, grid, it.tail, (const T*)X_[it.xp].p, (const T*)RES_[it.rp].p, P, state_.gamma,
+               X_[it.xd].p, Z_[it.zn].p, RES_[it.rn].p, S_[state_.lbfgs.spare].p, Y_[state_.lbfgs.spare].p, (T*)nullptr, (T*)nullptr, n,
                parts_.p, (int)SL_TRIAL);
         gather(SL_TRIAL, 12, 1u << 9);
         it.sep_trial = true;
-        it.have_trial = true; it.fused_this = true; gx_valid = false; gz_valid = false;
-        n_grad += 2; n_prox += 1;
+        it.have_trial = true; it.fused_this = true; state_.gx_valid = false; state_.gz_valid = false;
+        cnt_.n_grad += 2; cnt_.n_prox += 1;
     }
     // the kernel chain: x_d = x + d (k_dense_head, k_compact_xd or k_axpy_dot), then the stencil passes, or grad L at x_d
     // (affine images or an evaluation); the FB step and the rest follow in finish_chain_trial
     void trial_chain(Iter& it) {
-        if (!res_valid) ensure_z();
+        if (!state_.res_valid) ensure_z();
         // cfg 4 with images: x_d, its images under grad L and c, L(x_d) and the forward-backward step in ONE launch
         // (k_dense_head; single rank, element-wise f, the common prox kinds)
         it.head_on = env_.densesmall && it.use_compact && aff_track_ && !it.stencil_fast_now && !generic_ && !ctx->multi() && !lp_g &&
-                     !dense_f && gx_valid && gz_valid && aff_count_ + 1 < aff_refresh_ &&
+                     !dense_f && state_.gx_valid && state_.gz_valid && state_.aff_count + 1 < aff_refresh_ &&
                      (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
         // x_d = x + d ; gradient at x_d ; state.x = x_d
         const T *res = RES_[it.rp].p, *x = X_[it.xp].p;
@@ -3074,7 +2918,7 @@ template <class T> class Solver final : public SolverBase {
         } else if (aff_track_) {
             chain_images(it);
         } else {
-            algrad(X_[it.xd].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
+            algrad(X_[it.xd].p, GX_.p, SL_FXD); ++cnt_.n_grad; state_.gx_valid = true;
         }
     }
     // Stencil5pt: {AL gradient at x_d + FB step} and {AL gradient at z + pair + stop norm} as two passes; same partial
@@ -3093,7 +2937,7 @@ template <class T> class Solver final : public SolverBase {
         nm(fb_nt ? "k_stencil_fb<NT=1>" : "k_stencil_fb<NT=0>");
         with_bool(fb_nt, [&](auto nt_) {
             launch(C_STENCIL_FB, k_stencil_fb<T, decltype(nt_)::value>, grid, (const T*)X_[xd].p, P, (int64_t)desc.f_grid_nx,
-                   (int64_t)desc.f_grid_ny, gamma, GX_.p, Z_[zn].p, RES_[it.rn].p, n, parts_.p,
+                   (int64_t)desc.f_grid_ny, state_.gamma, GX_.p, Z_[zn].p, RES_[it.rn].p, n, parts_.p,
                    (int)SL_FXD, (int)SL_GSUM, halo_x);
         });
         const StencilHalo<T> halo_z = halo_exchange(Z_[zn].p);
@@ -3116,7 +2960,7 @@ template <class T> class Solver final : public SolverBase {
                 auto run = [&](auto kernel) {
                     launch(C_STENCIL_UPD, kernel, g_upd, CV, (const T*)Z_[zn].p, P, (int64_t)desc.f_grid_nx, (int64_t)desc.f_grid_ny,
                            (const T*)X_[xd].p, (const T*)X_[it.xp].p, (const T*)RES_[it.rn].p, (const T*)RES_[it.rp].p,
-                           (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL, halo_z);
+                           (const T*)GX_.p, state_.gamma, S_[state_.lbfgs.spare].p, Y_[state_.lbfgs.spare].p, n, parts_.p, (int)SL_TRIAL, halo_z);
                 };
                 if (regx == 1) run(k_stencil_update_c<T, CM, FULL, NT, 1>);
                 else run(k_stencil_update_c<T, CM, FULL, NT, 0>);
@@ -3135,19 +2979,19 @@ template <class T> class Solver final : public SolverBase {
             nm("k_stencil_update");
             launch(C_STENCIL_UPD, k_stencil_update<T>, grid, (const T*)Z_[zn].p, P, (int64_t)desc.f_grid_nx,
                    (int64_t)desc.f_grid_ny, (const T*)X_[xd].p, (const T*)X_[it.xp].p, (const T*)RES_[it.rn].p,
-                   (const T*)RES_[it.rp].p, (const T*)GX_.p, gamma, S_[spare].p, Y_[spare].p, (T*)nullptr, n, parts_.p,
+                   (const T*)RES_[it.rp].p, (const T*)GX_.p, state_.gamma, S_[state_.lbfgs.spare].p, Y_[state_.lbfgs.spare].p, (T*)nullptr, n, parts_.p,
                    (int)SL_FZ, (int)SL_YS, halo_z);
         }
-        it.have_trial = true; gx_valid = true; gz_valid = false;
-        n_grad += 2; n_prox += 1;
+        it.have_trial = true; state_.gx_valid = true; state_.gz_valid = false;
+        cnt_.n_grad += 2; cnt_.n_prox += 1;
     }
     // cfg 4: gradient (and c) at x_d into the candidate buffers — the same combination of the held images that forms x_d
     // (k_dense_head, or k_affine_image and the value L(x_d)), or an evaluation — then trade: GX_ = grad L(x_d),
     // GXN_ = grad L(x_prev)
     void chain_images(Iter& it) {
-        it.state_imgs = gx_valid && gz_valid;      // (the images of this state's x and z are what GX_, GZ_, CXS_, CZS_ hold)
-        if (it.use_compact && gx_valid && gz_valid && aff_count_ + 1 < aff_refresh_) {
-            ++aff_count_; ++n_affine_; it.img_trial = true;
+        it.state_imgs = state_.gx_valid && state_.gz_valid;      // (the images of this state's x and z are what GX_, GZ_, CXS_, CZS_ hold)
+        if (it.use_compact && state_.gx_valid && state_.gz_valid && state_.aff_count + 1 < aff_refresh_) {
+            ++state_.aff_count; ++state_.n_affine; it.img_trial = true;
             CompactVecs<T, CM> VA = image_vecs(true), VG = image_vecs(false);
             if (it.head_on) {
                 DenseHeadArgs<T, CM> a;
@@ -3156,7 +3000,7 @@ template <class T> class Solver final : public SolverBase {
                 a.res = RES_[it.rp].p; a.x = X_[it.xp].p; a.x_d = X_[it.xd].p;
                 a.gbase = GX_.p; a.gzimg = GZ_.p; a.gout = GXN_.p;
                 a.cbase = CXS_.p; a.czimg = CZS_.p; a.cout = CXD_.p; a.yupd = YU_.p;
-                a.z = Z_[it.zn].p; a.res_new = RES_[it.rn].p; a.gamma = gamma;
+                a.z = Z_[it.zn].p; a.res_new = RES_[it.rn].p; a.gamma = state_.gamma;
                 a.n = n; a.ny = ny; a.parts = parts_.p;
                 a.slot_f = SL_FXD; a.slot_pen = SL_PXD; a.slot_fb = SL_GSUM; a.gn = grid; a.gy = grid_y;
                 slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
@@ -3180,24 +3024,24 @@ template <class T> class Solver final : public SolverBase {
                 launch(C_MISC, k_yupd<T>, grid_y, (const T*)CXD_.p, P, YU_.p, ny, parts_.p, (int)SL_PXD);
             }
         } else {
-            aff_count_ = 0;
+            state_.aff_count = 0;
             cx_keep_ = CXD_.p;
             algrad(X_[it.xd].p, GXN_.p, SL_FXD);
             cx_keep_ = nullptr;
         }
-        std::swap(GX_.p, GXN_.p); std::swap(GX_.n, GXN_.n);
-        ++n_grad; gx_valid = true;
+        GX_.swap(GXN_);
+        ++cnt_.n_grad; state_.gx_valid = true;
     }
 
     // a trial of the kernel chain from grad L at the trial point on: the FB step, grad L at z, then k_dense_tail, or
     // k_update_c / k_update and the pair's images
     void finish_chain_trial(Iter& it) {
         const int zn = it.zn, rn = it.rn, xcur = it.xcur;
-        if (!gx_valid) { algrad(X_[xcur].p, GX_.p, SL_FXD); gx_valid = true; }
+        if (!state_.gx_valid) { algrad(X_[xcur].p, GX_.p, SL_FXD); state_.gx_valid = true; }
         if (it.head_fb) it.head_fb = false;      // (k_dense_head made this step already)
-        else fbstep(X_[xcur].p, GX_.p, gamma, Z_[zn].p, RES_[rn].p, SL_GSUM);
+        else fbstep(X_[xcur].p, GX_.p, state_.gamma, Z_[zn].p, RES_[rn].p, SL_GSUM);
         gather(SL_GSUM, 3, 0u);
-        ++n_prox;
+        ++cnt_.n_prox;
         T* const gz_dst = aff_track_ ? GZN_.p : GZ_.p;      // (affine images: grad L(z_prev) is still needed)
         if (aff_track_) cx_keep_ = CZN_.p;
         // cfg 4: the fold of the row-group partials, the pair with its products and the pair's images in ONE launch
@@ -3207,7 +3051,7 @@ template <class T> class Solver final : public SolverBase {
         if (tail_on) {
             slot_n[SL_FZ] = grid;
             dense_fused_launch(Z_[zn].p, SL_FZ + 1);
-            ++n_grad; gz_valid = true;
+            ++cnt_.n_grad; state_.gz_valid = true;
             cx_keep_ = nullptr;
             const CompactVecs<T, CM> VG = compact_vecs();
             DenseTailArgs<T, CM> a;
@@ -3215,10 +3059,10 @@ template <class T> class Solver final : public SolverBase {
             a.V = VG; a.part = GT_.p; a.nchunks = df_groups_; a.pstride = npad;
             a.z = Z_[zn].p; a.gz = gz_dst;
             a.x = X_[xcur].p; a.x_prev = X_[it.xp].p; a.res = RES_[rn].p; a.res_prev = RES_[it.rp].p; a.gx = GX_.p;
-            a.gamma = gamma; a.s_new = S_[spare].p; a.y_new = Y_[spare].p;
-            a.gx_prev = GXN_.p; a.gz_prev = GZ_.p; a.gs_img = GS_[spare].p; a.gy_img = GY_[spare].p;
+            a.gamma = state_.gamma; a.s_new = S_[state_.lbfgs.spare].p; a.y_new = Y_[state_.lbfgs.spare].p;
+            a.gx_prev = GXN_.p; a.gz_prev = GZ_.p; a.gs_img = GS_[state_.lbfgs.spare].p; a.gy_img = GY_[state_.lbfgs.spare].p;
             a.cx = CXD_.p; a.cx_prev = CXS_.p; a.cz = CZN_.p; a.cz_prev = CZS_.p;
-            a.cs_img = AS_[spare].p; a.cy_img = AY_[spare].p;
+            a.cs_img = AS_[state_.lbfgs.spare].p; a.cy_img = AY_[state_.lbfgs.spare].p;
             a.n = n; a.ny = ny; a.parts = parts_.p; a.slot_fz = SL_FZ; a.slot_upd = SL_YS; a.gn = grid; a.gy = grid_y;
             for (int kk = 0; kk < 3 + 4 * CM + 2; ++kk) slot_n[SL_YS + kk] = grid;
             // (what the four kernels move: the fold + f terms, k_update_c, the two image pairs)
@@ -3230,7 +3074,7 @@ template <class T> class Solver final : public SolverBase {
             it.gen_gram = true; it.m_gram = VG.m; it.tail_used = false;
             return;
         }
-        algrad(Z_[zn].p, gz_dst, SL_FZ); ++n_grad; gz_valid = true;
+        algrad(Z_[zn].p, gz_dst, SL_FZ); ++cnt_.n_grad; state_.gz_valid = true;
         cx_keep_ = nullptr;
         if (compact_ok) {
             // the pair, the stop norm AND the compact form's products (Gram products of the candidate pair, the
@@ -3239,26 +3083,26 @@ template <class T> class Solver final : public SolverBase {
             for (int kk = 0; kk < 3 + 4 * CM + 2; ++kk) slot_n[SL_YS + kk] = grid;
             mv(8 + 2 * VG.m); nm("k_update_c");
             launch(C_UPDATE, k_update_c<T, CM>, grid, VG, (const T*)X_[xcur].p, (const T*)X_[it.xp].p,
-                   (const T*)RES_[rn].p, (const T*)RES_[it.rp].p, (const T*)GX_.p, (const T*)gz_dst, gamma,
-                   S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_TRIAL);
+                   (const T*)RES_[rn].p, (const T*)RES_[it.rp].p, (const T*)GX_.p, (const T*)gz_dst, state_.gamma,
+                   S_[state_.lbfgs.spare].p, Y_[state_.lbfgs.spare].p, n, parts_.p, (int)SL_TRIAL);
             gather(SL_YS, 3 + 4 * CM + 2, 4u);
             it.gen_gram = true; it.m_gram = VG.m; it.tail_used = false;
         } else {
             for (int kk = 0; kk < 3; ++kk) slot_n[SL_YS + kk] = grid;
             mv(8);
             launch(C_UPDATE, k_update<T>, grid, (const T*)X_[xcur].p, (const T*)X_[it.xp].p,
-                   (const T*)RES_[rn].p, (const T*)RES_[it.rp].p, (const T*)GX_.p, (const T*)gz_dst, gamma,
-                   S_[spare].p, Y_[spare].p, n, parts_.p, (int)SL_YS);
+                   (const T*)RES_[rn].p, (const T*)RES_[it.rp].p, (const T*)GX_.p, (const T*)gz_dst, state_.gamma,
+                   S_[state_.lbfgs.spare].p, Y_[state_.lbfgs.spare].p, n, parts_.p, (int)SL_YS);
             gather(SL_YS, 3, 4u);
         }
         if (aff_track_) {
             // images of the candidate pair (s = x - x_prev, y = res - res_prev) under c and grad L
             mv(6, ny);
             launch(C_MISC, k_image_pair<T>, grid_y, (const T*)CXD_.p, (const T*)CXS_.p, (const T*)CZN_.p,
-                   (const T*)CZS_.p, AS_[spare].p, AY_[spare].p, ny);
+                   (const T*)CZS_.p, AS_[state_.lbfgs.spare].p, AY_[state_.lbfgs.spare].p, ny);
             mv(6);
             launch(C_MISC, k_image_pair<T>, grid, (const T*)GX_.p, (const T*)GXN_.p, (const T*)GZN_.p,
-                   (const T*)GZ_.p, GS_[spare].p, GY_[spare].p, n);
+                   (const T*)GZ_.p, GS_[state_.lbfgs.spare].p, GY_[state_.lbfgs.spare].p, n);
         }
     }
 
@@ -3267,7 +3111,7 @@ template <class T> class Solver final : public SolverBase {
     void step_size_test(Iter& it) {
         const T eps = std::numeric_limits<T>::epsilon();
         const int max_bt = opt.max_backtracks;
-        T sigma = beta * (T(0.5) / gamma) * (T(1) - alpha);
+        T sigma = beta * (T(0.5) / state_.gamma) * (T(1) - alpha);
         const T tol0 = T(10) * eps * (T(1) + std::abs(it.FBE_x));
         const T threshold = it.FBE_x - sigma * (it.nr0 * it.nr0) + tol0;
         std::vector<double>& v = it.v;
@@ -3292,28 +3136,28 @@ template <class T> class Solver final : public SolverBase {
                 it.gram_from_trial = false;
             }
             it.have_trial = false;
-            f_x = al_value(v[0], v[1]);
-            g_z = g_value(v[2]); dot_gr = T(v[3]); ss_res = T(v[4]);
+            state_.f_x = al_value(v[0], v[1]);
+            state_.g_z = g_value(v[2]); state_.dot_gr = T(v[3]); state_.ss_res = T(v[4]);
             const T f_z = al_value(v[5], v[6]);
-            fraw_last = f_value(v[5]); f_z_al = f_z;
-            const T nr = std::sqrt(ss_res);
-            const T f_z_upp = f_x - dot_gr + ((alpha / gamma) / T(2)) * (nr * nr);
+            state_.fraw_last = f_value(v[5]); state_.f_z_al = f_z;
+            const T nr = std::sqrt(state_.ss_res);
+            const T f_z_upp = state_.f_x - state_.dot_gr + ((alpha / state_.gamma) / T(2)) * (nr * nr);
             const T tol = T(10) * eps * (T(1) + std::abs(f_z));
-            const bool halve = adaptive_ && std::isfinite((double)gamma) && f_z > f_z_upp + tol && gamma >= min_gamma;
+            const bool halve = adaptive_ && std::isfinite((double)state_.gamma) && f_z > f_z_upp + tol && state_.gamma >= min_gamma;
             if (halve && it.img_trial) {
                 // The step-size test compares f(z) with a model built on f(x) and grad L(x) to within 10 eps: an image
                 // (a linear combination, not an evaluation) is not consistent with f(z) to that level near convergence,
                 // and a value a few ulps low would halve gamma again and again at the same point.  A FAILING test is
                 // therefore never trusted on images: evaluate f and grad L at this x with the two passes over A and
                 // run the trial again (this does not consume one of the max_backtracks trials).
-                it.img_trial = false; aff_count_ = 0; ++n_affine_verify_;
+                it.img_trial = false; state_.aff_count = 0; ++state_.n_affine_verify;
                 cx_keep_ = CXD_.p;
-                algrad(X_[it.xcur].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
+                algrad(X_[it.xcur].p, GX_.p, SL_FXD); ++cnt_.n_grad; state_.gx_valid = true;
                 cx_keep_ = nullptr;
                 --k;
                 continue;
             }
-            const T FBE_new = f_z_upp + g_z;
+            const T FBE_new = f_z_upp + state_.g_z;
             // not a plain iteration: z of the state this step started from may be needed (z_curr below), and
             // it must be formed with the gamma of that state
             // ... and the classic kernels that finish this iteration need the stored pairs (and the residual of
@@ -3322,12 +3166,12 @@ template <class T> class Solver final : public SolverBase {
             if (gate_pending_ && !(k == 1 && !halve && (FBE_new <= threshold || k >= max_bt) && T(v[7]) > T(0))) gate_abort();
             if (halve) it.trial_ok = false;
             if (sy_stale_ && !it.trial_ok && (halve || !(FBE_new <= threshold || k >= max_bt))) materialize_pairs();
-            if ((!z_valid || !res_valid) && (halve || !(FBE_new <= threshold || k >= max_bt))) ensure_z();
+            if ((!state_.z_valid || !state_.res_valid) && (halve || !(FBE_new <= threshold || k >= max_bt))) ensure_z();
             if (halve) {
                 it.halved_here = true;
-                gamma = gamma * T(0.5); ++n_halv;
-                if (gamma < min_gamma)
-                    std::fprintf(stderr, "Warning: stepsize `gamma` became too small (%g)\n", (double)gamma);
+                state_.gamma = state_.gamma * T(0.5); ++cnt_.n_halv;
+                if (state_.gamma < min_gamma)
+                    std::fprintf(stderr, "Warning: stepsize `gamma` became too small (%g)\n", (double)state_.gamma);
                 sigma = sigma * T(2);   // (as upstream: sigma is updated, the threshold is kept)
                 lbfgs_reset();
                 it.fused_this = false; it.reset_this = true;
@@ -3335,7 +3179,7 @@ template <class T> class Solver final : public SolverBase {
             }
             if (FBE_new <= threshold || k >= max_bt) break;
             tau = (k >= max_bt - 1) ? T(0) : tau / T(2);
-            ++it.nbt; ++n_bt;
+            ++it.nbt; ++cnt_.n_bt;
             retrial(it);
         }
     }
@@ -3355,31 +3199,31 @@ template <class T> class Solver final : public SolverBase {
             mv(xr2_streams(it.m_at_trial) + 2);
             launch_xr2(it.trial_plan, it.trial_coef, 1, X_[xb].p, Z_[it.zn].p, RES_[it.rn].p);
             onepass_scalars(it, false);
-            it.have_trial = true; it.gram_from_trial = true; gx_valid = false; gz_valid = false;
-            n_grad += 2; n_prox += 1;
-        } else if (env_.affine_blend && aff_track_ && it.state_imgs && gx_valid && it.nbt == 1 && !it.halved_here && compact_ok &&
-                   !generic_ && !ctx->multi() && aff_count_ + 1 < aff_refresh_) {
+            it.have_trial = true; it.gram_from_trial = true; state_.gx_valid = false; state_.gz_valid = false;
+            cnt_.n_grad += 2; cnt_.n_prox += 1;
+        } else if (env_.affine_blend && aff_track_ && it.state_imgs && state_.gx_valid && it.nbt == 1 && !it.halved_here && compact_ok &&
+                   !generic_ && !ctx->multi() && state_.aff_count + 1 < aff_refresh_) {
             // cfg 4, first tau backtrack of an iteration: the blended point is an affine combination of x_d and the state's z,
             // whose images under c and grad L are at hand — its images are the same combination (k_blend's operations), no
             // pass over A.  (As for x_d: a failing step-size test on images is re-run on evaluations, img_trial.)  The rejected
             // trial's z images (CZN_, GZN_) are dead: they take the results and trade places.
-            ++aff_count_; it.img_trial = true;      // (n_affine_images counts iterations whose trial point x + d went on images)
-            ++n_affine_blends_;
+            ++state_.aff_count; it.img_trial = true;      // (n_affine_images counts iterations whose trial point x + d went on images)
+            ++state_.n_affine_blends;
             mv(3, ny);
             launch(C_MISC, k_blend<T>, grid_y, (const T*)CXD_.p, (const T*)CZS_.p, tau, T(1) - tau, CZN_.p, ny);
-            std::swap(CXD_.p, CZN_.p); std::swap(CXD_.n, CZN_.n);
+            CXD_.swap(CZN_);
             mv(3);
             launch(C_MISC, k_blend<T>, grid, (const T*)GX_.p, (const T*)GZ_.p, tau, T(1) - tau, GZN_.p, n);
-            std::swap(GX_.p, GZN_.p); std::swap(GX_.n, GZN_.n);
+            GX_.swap(GZN_);
             slot_n[SL_FXD] = grid; slot_n[SL_PXD] = grid_y;
             mv(1 + pstreams(true, false, false));
             launch(C_MISC, k_fvalue_elem<T>, grid, (const T*)X_[xb].p, P, n, parts_.p, (int)SL_FXD, (const T*)nullptr);
             mv(2 + pstreams(false, true, false), ny);
             launch(C_MISC, k_yupd<T>, grid_y, (const T*)CXD_.p, P, YU_.p, ny, parts_.p, (int)SL_PXD);
-            ++n_grad; gx_valid = true;
+            ++cnt_.n_grad; state_.gx_valid = true;
         } else {
-            if (aff_track_) { cx_keep_ = CXD_.p; aff_count_ = 0; it.img_trial = false; }
-            algrad(X_[xb].p, GX_.p, SL_FXD); ++n_grad; gx_valid = true;
+            if (aff_track_) { cx_keep_ = CXD_.p; state_.aff_count = 0; it.img_trial = false; }
+            algrad(X_[xb].p, GX_.p, SL_FXD); ++cnt_.n_grad; state_.gx_valid = true;
             cx_keep_ = nullptr;
         }
     }
@@ -3389,50 +3233,49 @@ template <class T> class Solver final : public SolverBase {
     void commit(Iter& it) {
         if (aff_track_) {
             // the accepted state's images become the current ones
-            std::swap(GZ_.p, GZN_.p); std::swap(GZ_.n, GZN_.n);
-            std::swap(CZS_.p, CZN_.p); std::swap(CZS_.n, CZN_.n);
-            std::swap(CXS_.p, CXD_.p); std::swap(CXS_.n, CXD_.n);
+            GZ_.swap(GZN_);
+            CZS_.swap(CZN_);
+            CXS_.swap(CXD_);
         }
         // update!(H, x - x_prev, res - res_prev): the pair sits in the spare slot
         const T ys = T(it.v[7]), yty = T(it.v[8]);
         last_ys = ys;
         // p, w for the next application: valid iff the accepted point is the one the fused trial measured
         // and the memory was not reset meanwhile (gram_insert shifts them along with the Gram matrices)
-        pw_valid = compact_ok && it.gram_from_trial && (int)order.size() == it.m_gram;
-        if (pw_valid) {
-            for (int i = 0; i < CM; ++i) { hp_[i] = i < it.m_gram ? it.tp[i] : 0.0; hw_[i] = i < it.m_gram ? it.tw[i] : 0.0; }
-            p_new_ = it.tpn; w_new_ = it.twn;
-        } else if (compact_ok && it.sep_trial && it.fused_this && it.m_at_trial == 0 && order.empty()) {
+        state_.lbfgs.pw_valid = compact_ok && it.gram_from_trial && (int)state_.lbfgs.order.size() == it.m_gram;
+        if (state_.lbfgs.pw_valid) {
+            for (int i = 0; i < CM; ++i) { state_.lbfgs.hp[i] = i < it.m_gram ? it.tp[i] : 0.0; state_.lbfgs.hw[i] = i < it.m_gram ? it.tw[i] : 0.0; }
+            state_.lbfgs.p_new = it.tpn; state_.lbfgs.w_new = it.twn;
+        } else if (compact_ok && it.sep_trial && it.fused_this && it.m_at_trial == 0 && state_.lbfgs.order.empty()) {
             // first iteration of a solve (empty memory): the k_fused_sep pass measured the new pair's p and w
-            pw_valid = true;
-            for (int i = 0; i < CM; ++i) { hp_[i] = 0.0; hw_[i] = 0.0; }
-            p_new_ = it.sep_p; w_new_ = it.sep_w;
+            state_.lbfgs.pw_valid = true;
+            for (int i = 0; i < CM; ++i) { state_.lbfgs.hp[i] = 0.0; state_.lbfgs.hw[i] = 0.0; }
+            state_.lbfgs.p_new = it.sep_p; state_.lbfgs.w_new = it.sep_w;
         }
         if (dir_kind_ == BZ_DIR_BROYDEN) {
             broyden_update();                    // (no curvature test: every pair updates the operator)
         } else if (ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON) {
-            if (compact_ok && !it.gram_from_trial && !order.empty()) {
+            if (compact_ok && !it.gram_from_trial && !state_.lbfgs.order.empty()) {
                 // the accepted pair is not the one the fused trial measured: its Gram products with the
                 // stored pairs come from their own pass
                 for (int k = 0; k < 2 * CM; ++k) slot_n[SL_GU + k] = grid;
-                mv(2 * (int)order.size() + 1);
-                launch(C_DOT, k_gram_pair<T, CM>, grid, compact_vecs(), (const T*)Y_[spare].p, n, parts_.p,
+                mv(2 * (int)state_.lbfgs.order.size() + 1);
+                launch(C_DOT, k_gram_pair<T, CM>, grid, compact_vecs(), (const T*)Y_[state_.lbfgs.spare].p, n, parts_.p,
                        (int)SL_GU);
                 gather(SL_GU, 2 * CM, 0u);
                 auto gv = collect_range(SL_GU, 2 * CM, 0u);
                 for (int i = 0; i < CM; ++i) { it.gsy[i] = gv[i]; it.gyy[i] = gv[CM + i]; }
             }
-            lbfgs_insert(ys, yty, it.gsy, it.gyy);
+            state_.lbfgs.insert(ys, yty, it.gsy, it.gyy, compact_ok, dir_kind_ == BZ_DIR_ANDERSON);
         } else {
-            ++n_skips;
+            ++cnt_.n_skips;
             materialize_pairs();         // (history as iterates: the window stops being contiguous here)
         }
         // A tau-backtracked point sits in the blend buffer: trade the two buffers so that the accepted iterate is
         // the next one of the ring whatever produced it — the stored pairs stay the successive differences of
         // the ring's last iterates, and the run below goes on through backtracks
         if (it.xcur == it.xb && fused_ok && compact_ok) {
-            std::swap(X_[it.xd].p, X_[it.xb].p);
-            std::swap(X_[it.xd].n, X_[it.xb].n);
+            X_[it.xd].swap(X_[it.xb]);
             it.xcur = it.xd;
         }
         // history as iterates is possible after CM iterations in a row that each inserted their pair, with no
@@ -3441,31 +3284,31 @@ template <class T> class Solver final : public SolverBase {
         // iteration that halved gamma is one too — y = res_new(gamma/2) - res_prev(gamma), as upstream has it —
         // because every iterate in the ring remembers the gamma of its residual, gring_)
         xr_run_ = (fused_ok && compact_ok && (ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON) && it.xcur == it.xd) ? (it.reset_this ? 1 : xr_run_ + 1) : 0;
-        gring_[it.xcur] = (double)gamma;
+        gring_[it.xcur] = (double)state_.gamma;
         stop_norm_ = it.v[9];
         xc = it.xcur; rc = it.rn; zc = it.zn;
-        z_valid = !(it.z_skipped && it.fused_this);      // the generic trial writes z; an accepted fused one may not have
-        res_valid = !(it.res_skipped && it.fused_this);  // ... nor res
+        state_.z_valid = !(it.z_skipped && it.fused_this);      // the generic trial writes z; an accepted fused one may not have
+        state_.res_valid = !(it.res_skipped && it.fused_this);  // ... nor res
         last_nbt = it.nbt; last_fused = it.fused_this;
-        if (it.fused_this) ++n_fused;
+        if (it.fused_this) ++cnt_.n_fused;
     }
    private:
     void fill_stats(bz_panoc_stats* st) {
         std::memset(st, 0, sizeof(*st));
-        st->iters = k_; st->f_z = (double)fraw_last; st->g_z = (double)g_z; st->al_z = (double)f_z_al;
-        st->gamma = (double)gamma; st->tau = (double)tau; st->stop_norm = stop_norm_;
-        st->n_grad = n_grad; st->n_prox = n_prox; st->n_backtracks = n_bt; st->n_gamma_halvings = n_halv;
-        st->n_fused_iters = n_fused; st->n_lbfgs_skips = n_skips;
+        st->iters = cnt_.k; st->f_z = (double)state_.fraw_last; st->g_z = (double)state_.g_z; st->al_z = (double)state_.f_z_al;
+        st->gamma = (double)state_.gamma; st->tau = (double)tau; st->stop_norm = stop_norm_;
+        st->n_grad = cnt_.n_grad; st->n_prox = cnt_.n_prox; st->n_backtracks = cnt_.n_bt; st->n_gamma_halvings = cnt_.n_halv;
+        st->n_fused_iters = cnt_.n_fused; st->n_lbfgs_skips = cnt_.n_skips;
         st->elapsed_s = std::chrono::duration<double>(std::chrono::steady_clock::now() - t_begin).count();
-        st->status = std::isnan((double)f_x) ? 2 : ((double)stop_norm_ <= opt.tol ? 0 : 1);
+        st->status = std::isnan((double)state_.f_x) ? 2 : ((double)stop_norm_ <= opt.tol ? 0 : 1);
         st->persist_fallbacks = (int32_t)n_persist_fallbacks_;
-        st->n_affine_images = n_affine_;
+        st->n_affine_images = state_.n_affine;
         st->n_gated_launches = n_gated_;
         st->n_gate_aborts = n_gate_aborts_;
         st->n_gate_fallbacks = n_gate_fallbacks_;
         st->n_dense_onepass = n_dense_onepass_;
         st->n_dense_fallbacks = n_dense_fallbacks_;
-        st->n_affine_blends = n_affine_blends_;
+        st->n_affine_blends = state_.n_affine_blends;
     }
 };
 

@@ -956,16 +956,10 @@ class LBFGSCompactOperator:
                 M1[i, j] = acc
         return M1, Ri
 
-    def mul(self, d, v):
-        T = self.dtype.type
-        m = len(self.S)
-        H0 = float(self.H)
-        if m == 0:
-            d[...] = T(H0) * v
-            return d
-        p = [float(_dot(self.S[i], v)) for i in range(m)]
-        w = [float(_dot(self.Y[i], v)) for i in range(m)]
-        M1, M2 = self.coefficient_matrices(self.SY, self.YY, H0)
+    @staticmethod
+    def coefficients(M1, M2, H0, p, w):
+        """u1 = M1 p - H0 M2' w and u2 = -(M2 p) in float64, explicit loops (fixed order)."""
+        m = len(p)
         u1, u2 = [0.0] * m, [0.0] * m
         for i in range(m):
             a = 0.0
@@ -979,6 +973,19 @@ class LBFGSCompactOperator:
             for j in range(m):
                 c += M2[i, j] * p[j]
             u2[i] = -c
+        return u1, u2
+
+    def mul(self, d, v):
+        T = self.dtype.type
+        m = len(self.S)
+        H0 = float(self.H)
+        if m == 0:
+            d[...] = T(H0) * v
+            return d
+        p = [float(_dot(self.S[i], v)) for i in range(m)]
+        w = [float(_dot(self.Y[i], v)) for i in range(m)]
+        M1, M2 = self.coefficient_matrices(self.SY, self.YY, H0)
+        u1, u2 = self.coefficients(M1, M2, H0, p, w)
         d[...] = T(H0) * v
         for i in range(m):
             d += T(u1[i]) * self.S[i]

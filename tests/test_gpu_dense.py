@@ -332,7 +332,7 @@ def test_dense_one_pass_timeout_falls_back_to_two_kernels(bz, ref, monkeypatch, 
 # ---- a one-pass timeout inside an iteration, state by state ---------------------------------------------------------------
 # The timeout is seen at the iteration's read-back, after the attempt has traded the affine-image buffers (GX_ <-> GXN_, and
 # with a blended backtrack CXD_ <-> CZN_, GX_ <-> GZN_) and possibly replaced the state's scalars: step() puts the state the
-# iteration started from back (StepState) and redoes it in the two-kernel form.  A redo from a half-traded state leaves
+# iteration started from back (IterState) and redoes it in the two-kernel form.  A redo from a half-traded state leaves
 # GS_ = GX_ - GXN_ ~ 0 as the image of the new pair, and every image-built grad L(x_d) of the next CM iterations wrong.
 CM = 5
 _ST = ("n_dense_onepass", "n_dense_fallbacks", "n_affine_images", "n_affine_blends", "n_backtracks", "n_gamma_halvings", "n_grad")
