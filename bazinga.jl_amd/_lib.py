@@ -21,6 +21,7 @@ BZ_C_IDENTITY, BZ_C_DENSE_AFFINE, BZ_C_SPARSE_AFFINE = 0, 1, 3
 BZ_D_ZERO, BZ_D_FREE, BZ_D_BOX = 0, 1, 2
 BZ_D_VC_PAIRS, BZ_D_CC_PAIRS, BZ_D_EITHEROR_PAIRS, BZ_D_XOR_PAIRS = 3, 4, 5, 6
 BZ_F_CALLBACK, BZ_G_CALLBACK, BZ_C_CALLBACK, BZ_D_CALLBACK = 5, 8, 2, 7
+BZ_F_SPARSE_QUADRATIC = 6
 # host-callback oracle protocol (include/bazinga_hip.h)
 F_GRADIENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 G_PROX_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64)
@@ -60,6 +61,7 @@ class ProblemDesc(C.Structure):
         ("D_lo", C.c_double), ("D_hi", C.c_double), ("D_lo_vec", C.c_void_p), ("D_hi_vec", C.c_void_p),
         ("cb_user", C.c_void_p), ("cb_f_gradient", F_GRADIENT_FN), ("cb_g_prox", G_PROX_FN),
         ("cb_c_eval", C_EVAL_FN), ("cb_c_jtprod", C_JTPROD_FN), ("cb_D_proj", D_PROJ_FN),
+        ("f_sp_rowptr", C.c_void_p), ("f_sp_col", C.c_void_p), ("f_sp_val", C.c_void_p), ("f_sp_nnz", C.c_int64),
         ("c_sp_rowptr", C.c_void_p), ("c_sp_col", C.c_void_p), ("c_sp_val", C.c_void_p), ("c_sp_nnz", C.c_int64),
     ]
 

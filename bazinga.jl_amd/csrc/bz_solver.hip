@@ -135,7 +135,8 @@ struct CreateKnobs {
     std::optional<int> persist_blocks = env_opt("BZ_PERSIST_BLOCKS");    // the persistent kernel on b CUs (two ranks on one GPU)
     int dense_fused = env_int("BZ_DENSE_FUSED", 1);      // 0: the dense constraint through two products, not k_dense_fused
     std::optional<int> dense_kp = env_opt("BZ_DENSE_KP");                // k_dense_fused's packs per row and lane
-    std::optional<int> spmv_l = env_opt("BZ_SPMV_L");    // lanes per row of the sparse constraint's two passes (a power of two <= 64)
+    std::optional<int> spmv_l = env_opt("BZ_SPMV_L");    // lanes per row of the CSR row kernels (a power of two <= 64)
+    int spq_fused = env_int("BZ_SPQ_FUSED", 1);          // 0: the sparse quadratic f with c = Identity as product + k_algrad_elem
     // test-only
     int test_dense_timeout = env_int("BZ_TEST_DENSE_TIMEOUT", 0);        // the k-th k_dense_fused exchange is sabotaged
     unsigned dense_spin = (unsigned)env_ll("BZ_DENSE_SPIN", 0);          // k_dense_fused's poll bound (0: the default)
@@ -184,6 +185,19 @@ template <class T> class Solver final : public SolverBase {
         if (n <= 0 || ny < 0) throw Error(BZ_ERR_ARG, "n must be positive");
         if (d.c_kind == BZ_C_IDENTITY && ny != n)
             throw Error(BZ_ERR_ARG, "c = Identity requires ny == n");
+        sparse_f = d.f_kind == BZ_F_SPARSE_QUADRATIC;
+        if (sparse_f) {
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseQuadratic: the slack (ALS) form is not lowered with a sparse quadratic f");
+            if (d.c_kind == BZ_C_DENSE_AFFINE)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseQuadratic: a sparse quadratic f beside a dense c (DenseAffine) is not lowered");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseQuadratic: the sparse quadratic f is not sharded (one rank)");
+            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseQuadratic: the sparse quadratic f does not mix with host callbacks");
+            if (!d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
+                throw Error(BZ_ERR_ARG, "SparseQuadratic needs rowptr[n + 1], col[nnz], val[nnz] and q[n]");
+            if (n > (int64_t)std::numeric_limits<int32_t>::max())
+                throw Error(BZ_ERR_ARG, "SparseQuadratic: n must fit 32-bit column indices");
+        }
         if (d.c_kind == BZ_C_SPARSE_AFFINE) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: the slack (ALS) form is not lowered with a sparse c");
             if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine is not sharded (one rank)");
@@ -236,7 +250,7 @@ template <class T> class Solver final : public SolverBase {
             if (ctx->nranks > 1 && (!ctx->p2p_on || slack))
                 throw Error(BZ_ERR_UNSUPPORTED, "a row-sharded DenseAffine needs the p2p mailboxes and no slack");
         }
-        if ((d.f_kind < BZ_F_ZERO || d.f_kind > BZ_F_QUADRATIC) && !generic_)
+        if ((d.f_kind < BZ_F_ZERO || d.f_kind > BZ_F_QUADRATIC) && !sparse_f && !generic_)
             throw Error(BZ_ERR_UNSUPPORTED, "smooth-cost kind not lowered to the device");
         dense_f = d.f_kind == BZ_F_LEAST_SQUARES || d.f_kind == BZ_F_QUADRATIC;
         if (dense_f) {
@@ -320,6 +334,12 @@ template <class T> class Solver final : public SolverBase {
                 FGT_.alloc((size_t)f_nrowchunks * npadx);
             }
         }
+        if (sparse_f) {
+            // (the generic kernel chain: no one-pass family kernel, no affine images, no k_begin_lip)
+            sparse_f_create(d);
+            upload(fb_, d.f_b, nx);
+            FR_.alloc(nx);
+        }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             A_.alloc((size_t)ny * nx);
             BZ_HIP(hipMemcpyAsync(A_.p, d.c_A, (size_t)ny * nx * sizeof(T), hipMemcpyDefault, ctx->stream));
@@ -350,7 +370,7 @@ template <class T> class Solver final : public SolverBase {
             upload(q_, d.f_q, nx); upload(b_, d.f_b, nx);
             P.q = q_.p; P.b = b_.p;
         }
-        if (dense_f) P.b = fb_.p;                          // Quadratic: q, read by the element-wise kernels
+        if (dense_f || sparse_f) P.b = fb_.p;              // Quadratic: q, read by the element-wise kernels and the row epilogues
         if (d.f_kind == BZ_F_STENCIL5) {
             if (!d.f_b) throw Error(BZ_ERR_ARG, "Stencil5pt needs b");
             upload(b_, d.f_b, n);
@@ -799,7 +819,7 @@ template <class T> class Solver final : public SolverBase {
     DBuf<T> A_, cb_, CX_, YU_, GT_;          // DenseAffine c: A[ny][n], b, c(x), yupd, A'v row-chunk partials
     int rows_per_chunk = 1, nrowchunks = 1;
     DBuf<T> FA_, fb_, FR_, DFX_, FGT_;       // dense f: matrix, vector, residual / Qx, gradient of f, A_f'r row-chunk partials
-    bool dense_f = false, lp_g = false;
+    bool dense_f = false, sparse_f = false, lp_g = false;
     // generic oracles (host callbacks): host mirrors of the vectors the callbacks read and write
     bool generic_ = false;
     std::vector<T> hx_, hg_, hy_, hz_, hres_, hdfx_, hjtv_, hcx_, ht_, hs_, hmu_, hmuy_, hyv_;
@@ -1754,8 +1774,9 @@ template <class T> class Solver final : public SolverBase {
             return (double)nnz * (sizeof(T) + 4) + (double)(nv + 1) * 8 + (ncut ? (double)nv * 8 : 0.0) + (double)cols * sizeof(T);
         }
     };
-    SpCsr spA_, spAt_;
-    std::string sp_form_[2];
+    SpCsr spA_, spAt_, spQ_;               // (Q: the sparse quadratic f; symmetric, so no transpose)
+    DBuf<int64_t> spQ_rowptr_;             // a cut Q: the row pointers as given (k_spmv_q_algrad walks rows, not virtual rows)
+    std::string sp_form_[4];               // by the epilogue's MODE
     template <class V> static void sp_upload(DBuf<V>& dst, const std::vector<V>& src) {
         dst.alloc(src.size());
         if (!src.empty()) BZ_HIP(hipMemcpy(dst.p, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
@@ -1786,7 +1807,7 @@ template <class T> class Solver final : public SolverBase {
             nv += segs;
             if (segs > 1) { ++ncut; nparts += segs; }
         }
-        if (nv > (int64_t)std::numeric_limits<int32_t>::max()) throw Error(BZ_ERR_ARG, "SparseAffine: too many row segments");
+        if (nv > (int64_t)std::numeric_limits<int32_t>::max()) throw Error(BZ_ERR_ARG, "sparse matrix: too many row segments");
         m.nv = nv; m.ncut = ncut;
         if (ncut) {
             std::vector<int64_t> vp; std::vector<int32_t> vrow, vpart, crow, cptr;
@@ -1816,31 +1837,46 @@ template <class T> class Solver final : public SolverBase {
             m.L = l;
         }
     }
-    // validate the caller's CSR on a host copy, build A' by a stable counting sort (a column's entries stay in
-    // ascending row order) and put both in HBM
+    // a host copy of the caller's CSR (rows x n), validated; `what` is the kind and `rows_name` its row count in the messages
+    void sp_read(const std::string& what, const char* rows_name, int64_t rows, const int64_t* rowptr, const int32_t* colp,
+                 const void* valp, int64_t nnz, std::vector<int64_t>& rp, std::vector<int32_t>& col, std::vector<T>& val) {
+        rp.resize((size_t)rows + 1); col.resize((size_t)nnz); val.resize((size_t)nnz);
+        BZ_HIP(hipMemcpy(rp.data(), rowptr, rp.size() * sizeof(int64_t), hipMemcpyDefault));
+        if (nnz) {
+            BZ_HIP(hipMemcpy(col.data(), colp, col.size() * sizeof(int32_t), hipMemcpyDefault));
+            BZ_HIP(hipMemcpy(val.data(), valp, val.size() * sizeof(T), hipMemcpyDefault));
+        }
+        if (rp[0] != 0) throw Error(BZ_ERR_ARG, what + ": rowptr[0] must be 0 (row 0)");
+        for (int64_t r = 0; r < rows; ++r)
+            if (rp[r + 1] < rp[r] || rp[r + 1] > nnz)
+                throw Error(BZ_ERR_ARG, what + ": rowptr must be non-decreasing and end at nnz (row " + std::to_string(r) + ")");
+        if (rp[rows] != nnz)
+            throw Error(BZ_ERR_ARG, what + ": rowptr[" + rows_name + "] must equal nnz (row " + std::to_string(rows - 1) + ")");
+        for (int64_t r = 0; r < rows; ++r)
+            for (int64_t k = rp[r]; k < rp[r + 1]; ++k)
+                if (col[k] < 0 || (int64_t)col[k] >= n)
+                    throw Error(BZ_ERR_ARG, what + ": column index outside [0, n) (row " + std::to_string(r) + ")");
+    }
+    static std::string sp_form(const char* kernel, const SpCsr& m) {
+        return std::string(kernel) + "<L=" + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
+    }
+    // f = SparseQuadratic: Q validated on a host copy and put in HBM as one CSR matrix with A's segment and lane rules
+    void sparse_f_create(const bz_problem_desc& d) {
+        std::vector<int64_t> rp; std::vector<int32_t> col; std::vector<T> val;
+        sp_read("SparseQuadratic", "n", nx, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
+        sp_build(spQ_, nx, nx, rp, col, val);
+        if (spQ_.ncut) sp_upload(spQ_rowptr_, rp);        // (a cut matrix keeps the virtual rows in ptr: the rows as given too)
+        sp_form_[2] = sp_form("k_spmv_q_algrad", spQ_);
+        sp_form_[3] = sp_form("k_spmv_q", spQ_);
+    }
+    // c = SparseAffine: validate the caller's CSR on a host copy, build A' by a stable counting sort (a column's entries stay
+    // in ascending row order) and put both in HBM
     void sparse_create(const bz_problem_desc& d) {
         const int64_t nnz = d.c_sp_nnz;
-        std::vector<int64_t> rp((size_t)ny + 1);
-        std::vector<int32_t> col((size_t)nnz);
-        std::vector<T> val((size_t)nnz);
-        BZ_HIP(hipMemcpy(rp.data(), d.c_sp_rowptr, rp.size() * sizeof(int64_t), hipMemcpyDefault));
-        if (nnz) {
-            BZ_HIP(hipMemcpy(col.data(), d.c_sp_col, col.size() * sizeof(int32_t), hipMemcpyDefault));
-            BZ_HIP(hipMemcpy(val.data(), d.c_sp_val, val.size() * sizeof(T), hipMemcpyDefault));
-        }
-        if (rp[0] != 0) throw Error(BZ_ERR_ARG, "SparseAffine: rowptr[0] must be 0 (row 0)");
-        for (int64_t r = 0; r < ny; ++r)
-            if (rp[r + 1] < rp[r] || rp[r + 1] > nnz)
-                throw Error(BZ_ERR_ARG, "SparseAffine: rowptr must be non-decreasing and end at nnz (row " + std::to_string(r) + ")");
-        if (rp[ny] != nnz)
-            throw Error(BZ_ERR_ARG, "SparseAffine: rowptr[ny] must equal nnz (row " + std::to_string(ny - 1) + ")");
+        std::vector<int64_t> rp; std::vector<int32_t> col; std::vector<T> val;
+        sp_read("SparseAffine", "ny", ny, d.c_sp_rowptr, d.c_sp_col, d.c_sp_val, nnz, rp, col, val);
         std::vector<int64_t> tp((size_t)n + 1, 0);
-        for (int64_t r = 0; r < ny; ++r)
-            for (int64_t k = rp[r]; k < rp[r + 1]; ++k) {
-                if (col[k] < 0 || (int64_t)col[k] >= n)
-                    throw Error(BZ_ERR_ARG, "SparseAffine: column index outside [0, n) (row " + std::to_string(r) + ")");
-                ++tp[(size_t)col[k] + 1];
-            }
+        for (int64_t k = 0; k < nnz; ++k) ++tp[(size_t)col[k] + 1];
         for (int64_t j = 0; j < n; ++j) tp[j + 1] += tp[j];
         std::vector<int32_t> tcol((size_t)nnz);
         std::vector<T> tval((size_t)nnz);
@@ -1854,13 +1890,25 @@ template <class T> class Solver final : public SolverBase {
         }
         sp_build(spA_, ny, n, rp, col, val);
         sp_build(spAt_, n, ny, tp, tcol, tval);
-        for (int t = 0; t < 2; ++t) {
-            const SpCsr& m = t ? spAt_ : spA_;
-            sp_form_[t] = std::string(t ? "k_spmv_t_finish<L=" : "k_spmv_yupd<L=") + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
-        }
+        sp_form_[0] = sp_form("k_spmv_yupd", spA_);
+        sp_form_[1] = sp_form("k_spmv_t_finish", spAt_);
     }
-    // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A') and, for a cut matrix, the fold
-    // of its cut rows; returns the number of block partials left in `slot`
+    // go(L, NT) with the run-time lane count and stream policy as compile-time constants
+    template <class F> static void sp_with_lanes(int L, bool nt, F&& go) {
+        with_bool(nt, [&](auto nt_) {
+            switch (L) {
+            case 1: go(std::integral_constant<int, 1>{}, nt_); break;
+            case 2: go(std::integral_constant<int, 2>{}, nt_); break;
+            case 4: go(std::integral_constant<int, 4>{}, nt_); break;
+            case 8: go(std::integral_constant<int, 8>{}, nt_); break;
+            case 16: go(std::integral_constant<int, 16>{}, nt_); break;
+            case 32: go(std::integral_constant<int, 32>{}, nt_); break;
+            default: go(std::integral_constant<int, 64>{}, nt_); break;
+            }
+        });
+    }
+    // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A', 3: k_spmv_q over Q) and, for a cut
+    // matrix, the fold of its cut rows; returns the number of block partials left in `slot`
     template <int MODE> int sp_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
         const double bytes = m.bytes() + vec_bytes;
         const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
@@ -1874,19 +1922,10 @@ template <class T> class Solver final : public SolverBase {
             pending_bytes_ += bytes;
             nm(sp_form_[MODE].c_str());
             if constexpr (MODE == 0) launch(C_GEMV, k_spmv_yupd<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else launch(C_GEMV, k_spmv_t_finish<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else if constexpr (MODE == 1) launch(C_GEMV, k_spmv_t_finish<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else launch(C_GEMV, k_spmv_q<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
         };
-        with_bool(nt, [&](auto nt_) {
-            switch (m.L) {
-            case 1: go(std::integral_constant<int, 1>{}, nt_); break;
-            case 2: go(std::integral_constant<int, 2>{}, nt_); break;
-            case 4: go(std::integral_constant<int, 4>{}, nt_); break;
-            case 8: go(std::integral_constant<int, 8>{}, nt_); break;
-            case 16: go(std::integral_constant<int, 16>{}, nt_); break;
-            case 32: go(std::integral_constant<int, 32>{}, nt_); break;
-            default: go(std::integral_constant<int, 64>{}, nt_); break;
-            }
-        });
+        sp_with_lanes(m.L, nt, go);
         if (gfold) {
             pending_bytes_ += (double)m.part.n * 8 + (double)m.ncut * 8;
             launch(C_MISC, k_spmv_fold<T, MODE>, gfold, (const double*)m.part.p, (const int32_t*)m.crow.p,
@@ -1901,11 +1940,38 @@ template <class T> class Solver final : public SolverBase {
         return sp_pass<0>(spA_, x, E, slot, vecs);
     }
     // rows of A': grad = grad f(x) + A'yhat and the f partials -> slot
+    // (the sparse quadratic f: its terms from FR_ = Q x, which spq_product has left there)
     int spmv_t_finish(const T* x, T* grad, int slot) {
-        SpEpi<T> E{nullptr, nullptr, grad, x, P};
-        const double vecs = ((grad ? 1 : 0) + (P.f_kind == BZ_F_DIAG_QUADRATIC ? 3 : 0)) * (double)n * sizeof(T);
+        SpEpi<T> E{nullptr, nullptr, grad, x, P, sparse_f ? (const T*)FR_.p : (const T*)nullptr};
+        const double vecs = ((grad ? 1 : 0) + (P.f_kind == BZ_F_DIAG_QUADRATIC || sparse_f ? 3 : 0)) * (double)n * sizeof(T);
         return sp_pass<1>(spAt_, YU_.p, E, slot, vecs);
     }
+    // rows of Q, c = Identity: the whole AL gradient — grad = (Q x + q) + yhat, the f partials -> slot, the penalty
+    // partials -> slot + 1.  Per row: x, q, mu and mu*y (and D's vector bounds), the gradient.
+    // One launch on k_algrad_elem's grid, whose summation tree it keeps: the scalars too are bit for bit the two-launch
+    // form's.  (Accounted with the pass model of the matrix, as k_spmv_q; a cut Q reads the rows as given and its segment
+    // sums in place of the virtual-row tables.)
+    int spq_algrad(const T* x, T* grad, int slot) {
+        SpCsr& m = spQ_;
+        SpEpi<T> E{nullptr, nullptr, grad, x, P, nullptr};
+        const double bytes = m.bytes() + (2 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T);
+        const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
+        const SpRows R{m.ncut ? spQ_rowptr_.p : m.ptr.p, m.crow.p, m.cptr.p, m.ncut, m.S, n};
+        sp_with_lanes(m.L, nt, [&](auto l_, auto nt_) {
+            pending_bytes_ += bytes;
+            nm(sp_form_[2].c_str());
+            launch(C_GEMV, k_spmv_q_algrad<T, decltype(l_)::value, decltype(nt_)::value>, grid, m.mat(), R, x, E, parts_.p, slot);
+        });
+        return grid;
+    }
+    // rows of Q: Q x -> out (null: not kept) and, with_f, the f partials -> slot (otherwise zeros)
+    int spq_product(const T* x, T* out, bool with_f, int slot) {
+        SpEpi<T> E{nullptr, nullptr, out, with_f ? x : (const T*)nullptr, P, nullptr};
+        const double vecs = ((out ? 1 : 0) + (with_f ? 2 : 0)) * (double)n * sizeof(T);
+        return sp_pass<3>(spQ_, x, E, slot, vecs);
+    }
+    // (pairwise D: the projection of element i needs its partner, which a row's first lane does not have)
+    bool spq_fused_on() const { return cenv_.spq_fused && !(desc.D_kind >= BZ_D_VC_PAIRS && desc.D_kind <= BZ_D_XOR_PAIRS); }
 
     // gradient!(dlx, al, x) on the device; partials -> slot0 (f terms), slot0+1 (t^2/mu)
     // row chunks of the transposed product: enough blocks to fill the chip, fixed summation order
@@ -1969,7 +2035,9 @@ template <class T> class Solver final : public SolverBase {
     void algrad(const T* x, T* grad, int slot0) {
         if (generic_) { algrad_generic(x, grad, slot0); return; }
         if (desc.c_kind == BZ_C_SPARSE_AFFINE) {
-            // two launches: rows of A (c(x), yhat, the penalty partials), rows of A' (A'yhat, grad f, the f partials)
+            // two launches: rows of A (c(x), yhat, the penalty partials), rows of A' (A'yhat, grad f, the f partials);
+            // the sparse quadratic f: a third in front, rows of Q (Q x -> FR_)
+            if (sparse_f) spq_product(x, FR_.p, false, (int)SL_SCRATCH);
             slot_n[slot0 + 1] = spmv_yupd(x, cx_keep_, YU_.p, slot0 + 1);
             slot_n[slot0] = spmv_t_finish(x, grad, slot0);
             gather(slot0, 2, 0u, 2u);
@@ -2025,6 +2093,12 @@ template <class T> class Solver final : public SolverBase {
             gather(slot0, 2, 0u, 2u);         // slot0: f terms (x-space) ; slot0 + 1: penalty terms (this rank's rows)
             return;
         }
+        if (sparse_f && spq_fused_on()) {
+            // c = Identity: one launch over the rows of Q
+            slot_n[slot0] = slot_n[slot0 + 1] = spq_algrad(x, grad, slot0);
+            gather(slot0, 2, 0u);
+            return;
+        }
         slot_n[slot0] = slot_n[slot0 + 1] = grid;
         if (slack) {
             slot_n[slot0] = slot_n[slot0 + 1] = grid_y;
@@ -2033,7 +2107,12 @@ template <class T> class Solver final : public SolverBase {
             gather(slot0, 2, 0u);
             return;
         }
-        if (dense_f) {
+        if (sparse_f) {
+            // the two-launch form: Q x -> FR_, then the element-wise kernel in its mode 2
+            spq_product(x, FR_.p, false, (int)SL_SCRATCH);
+            mv(4 + pstreams(false, true, false));
+            launch(C_ALGRAD, k_algrad_elem<T>, grid, x, P, grad, n, parts_.p, slot0, 2, (const T*)FR_.p);
+        } else if (dense_f) {
             dense_f_eval(x, slot0, true);
             if (desc.f_kind == BZ_F_LEAST_SQUARES)
                 { mv(3 + pstreams(false, true, false)); launch(C_ALGRAD, k_algrad_elem<T>, grid, x, P, grad, n, parts_.p, slot0, 1, (const T*)DFX_.p); }
@@ -2070,7 +2149,14 @@ template <class T> class Solver final : public SolverBase {
             gather(slot0, 1, 0u);
             return;
         }
-        if (dense_f) {
+        if (sparse_f) {
+            if (cenv_.spq_fused) {
+                slot_n[slot0] = spq_product(x, nullptr, true, slot0);       // f(x) from the rows of Q, Q x not kept
+            } else {
+                spq_product(x, FR_.p, false, (int)SL_SCRATCH);
+                mv(3); launch(C_MISC, k_fvalue_elem<T>, grid, x, P, n, parts_.p, slot0, (const T*)FR_.p);
+            }
+        } else if (dense_f) {
             dense_f_eval(x, slot0, false);
             if (desc.f_kind == BZ_F_QUADRATIC)
                 { mv(3); launch(C_MISC, k_fvalue_elem<T>, grid, x, P, n, parts_.p, slot0, (const T*)FR_.p); }

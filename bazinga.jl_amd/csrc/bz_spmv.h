@@ -1,4 +1,5 @@
-// bz_spmv.h — the sparse affine constraint c(x) = A x - b (BZ_C_SPARSE_AFFINE): the two row kernels of its AL gradient.
+// bz_spmv.h — the CSR row kernels: the sparse affine constraint c(x) = A x - b (BZ_C_SPARSE_AFFINE), the two passes of its AL
+// gradient, and the sparse quadratic f(x) = 0.5 x'Qx + q'x (BZ_F_SPARSE_QUADRATIC), the pass over Q.
 //
 // A and A' are two CSR matrices in HBM (A' is built once, at bz_problem_create, by a stable counting sort).  Both passes
 // are the same row kernel: L lanes (compile time, 1..64, chosen at creation from the mean row length) walk one row, lane
@@ -7,6 +8,10 @@
 // nothing that depends on the grid or on timing.
 //   k_spmv_yupd      rows of A :  c_i = sum a_ij x_j - b_i, and on that value what k_yupd does with it
 //   k_spmv_t_finish  rows of A':  (A' yhat)_j, and on that value what k_gemv_t_finish does with it
+//   k_spmv_q_algrad  rows of Q, c = Identity:  (Q x)_i, and on that value what k_algrad_elem does in its mode 2 — the whole
+//                    AL gradient in one launch, on k_algrad_elem's grid and with its summation tree; Q x never goes to HBM
+//   k_spmv_q         rows of Q:  Q x -> FR (and / or the f terms) for the forms that finish element-wise or in k_spmv_t_finish
+// (Q is symmetric by the caller's contract: no transpose is built.)
 // Rows longer than S entries (S fixed at creation from the matrix alone) are cut into segments that run as rows of
 // their own ("virtual rows": the row pointers refined at the cuts); a segment leaves its sum in a side buffer and
 // k_spmv_fold, one wave per cut row, adds a row's segment sums in a fixed order and runs the row's epilogue.
@@ -29,22 +34,28 @@ template <class T> struct SpMat {
 };
 
 // what a row's value goes into.  MODE 0 (rows of A): cx (if kept), yupd (if wanted: null = eval!(cx, c, x) alone) and
-// the penalty term; MODE 1 (rows of A'): the gradient and the f term.
+// the penalty term; MODE 1 (rows of A'): the gradient and the f term; MODE 2 (rows of Q, c = Identity): the gradient, the
+// f term and the penalty term; MODE 3 (rows of Q): Q x (if kept) and the f term (if x is given).
 template <class T> struct SpEpi {
     const T* b;              // MODE 0: b[ny]
     T* cx;                   // MODE 0: c(x) for the caller that keeps it, or null
-    T* out;                  // MODE 0: yupd[ny] or null ; MODE 1: grad[n] or null
-    const T* x;              // MODE 1: x[n]
+    T* out;                  // MODE 0: yupd[ny] or null ; MODE 1, 2: grad[n] or null ; MODE 3: (Q x)[n] or null
+    const T* x;              // MODE 1, 2: x[n] ; MODE 3: x[n], or null for the product alone
     ElemParams<T> P;
+    const T* ext;            // MODE 1 with the sparse quadratic f: (Q x)[n], left by k_spmv_q
 };
 
+// scalars a mode leaves per row: MODE 2 the f term and the penalty term, the others one
+template <int MODE> constexpr int sp_nacc() { return MODE == 2 ? 2 : 1; }
+
+// (called by the row's first lane alone: the per-row parameters are loaded once per row)
 template <class T, int MODE>
-__device__ __forceinline__ double sp_epilogue(const SpEpi<T>& E, int64_t r, double d) {
+__device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double d, double (&acc)[sp_nacc<MODE>()]) {
     const ElemParams<T>& P = E.P;
     if constexpr (MODE == 0) {
         const T c = (T)d - E.b[r];                                  // eval!(cx, c, x)
         if (E.cx) E.cx[r] = c;
-        if (!E.out) return 0.0;
+        if (!E.out) return;
         // t = cx + muy ; s = proj_D(t) ; t -= s ; sum t^2/mu ; yupd = t/mu      (k_yupd)
         const T mu = P.uni >= 1 ? P.mu_uniform : P.mu[r];
         const T muy = P.uni >= 2 ? T(0) : P.muy[r];
@@ -55,18 +66,41 @@ __device__ __forceinline__ double sp_epilogue(const SpEpi<T>& E, int64_t r, doub
         t = t - sv;
         const T pterm = (t * t) / mu;
         E.out[r] = t / mu;
-        return (double)pterm;
-    } else {
+        acc[0] += (double)pterm;
+    } else if constexpr (MODE == 1) {
         // dlx = dfx + jtv ; f element-wise (Zero | DiagQuadratic)               (k_gemv_t_finish)
+        // or the sparse quadratic from ext = Q x, P.b = q                      (k_gemv_t_finish_ext, fext 2)
         T dfx = T(0), fterm = T(0);
         if (P.f_kind == BZ_F_DIAG_QUADRATIC) {
             const T xv = E.x[r];
             const T qx = P.q[r] * xv;
             dfx = qx - P.b[r];
             fterm = xv * (T(0.5) * qx - P.b[r]);
+        } else if (P.f_kind == BZ_F_SPARSE_QUADRATIC) {
+            const T xv = E.x[r], e = E.ext[r], qv = P.b[r];
+            dfx = e + qv;
+            fterm = xv * (T(0.5) * e + qv);
         }
         if (E.out) E.out[r] = dfx + (T)d;
-        return (double)fterm;
+        acc[0] += (double)fterm;
+    } else if constexpr (MODE == 2) {
+        // element r of k_algrad_elem in its mode 2 with ext[r] = d: the same operations in the same order (never launched
+        // with a pairwise D, whose projection needs the partner element)
+        const T xv = E.x[r], qv = P.b[r], e = (T)d;
+        const T mu = P.uni >= 1 ? P.mu_uniform : P.mu[r];
+        const T muy = P.uni >= 2 ? T(0) : P.muy[r];
+        const T lo = P.D_lo_vec ? P.D_lo_vec[r] : P.D_lo;
+        const T hi = P.D_hi_vec ? P.D_hi_vec[r] : P.D_hi;
+        const ALOut<T> o = al_elem(BZ_F_ZERO, P.D_kind, xv, T(0), T(0), mu, muy, lo, hi);
+        const T dfx = e + qv;
+        const T fterm = xv * (T(0.5) * e + qv);
+        if (E.out) E.out[r] = dfx + o.grad;
+        acc[0] += (double)fterm;
+        acc[1] += (double)o.pterm;
+    } else {
+        const T e = (T)d;
+        if (E.out) E.out[r] = e;
+        if (E.x) acc[0] += (double)(E.x[r] * (T(0.5) * e + P.b[r]));            // k_fvalue_elem with ext
     }
 }
 
@@ -108,12 +142,12 @@ __device__ __forceinline__ double spmv_row(const SpMat<T>& M, const T* __restric
 }
 
 // the row loop shared by the two passes: virtual row v belongs to the L lanes (blockIdx.x * BLOCK + threadIdx.x) / L,
-// then grid-strides.  Returns this thread's share of the pass's scalar (the row's first lane carries the row's term).
+// then grid-strides.  Adds this thread's share of the pass's scalars to acc (the row's first lane carries the row's terms).
 template <class T, int L, bool NT, int MODE>
-__device__ __forceinline__ double spmv_rows(const SpMat<T>& M, const T* __restrict__ g, const SpEpi<T>& E) {
+__device__ __forceinline__ void spmv_rows(const SpMat<T>& M, const T* __restrict__ g, const SpEpi<T>& E,
+                                          double (&acc)[sp_nacc<MODE>()]) {
     constexpr int RPB = BLOCK / L;
     const int sub = threadIdx.x % L;
-    double acc = 0.0;
     for (int64_t v = (int64_t)blockIdx.x * RPB + threadIdx.x / L; v < M.nv; v += (int64_t)gridDim.x * RPB) {
         const int64_t s = M.ptr[v], e = M.ptr[v + 1];
         const double d = spmv_row<T, L, NT>(M, g, s, e, sub);
@@ -122,43 +156,142 @@ __device__ __forceinline__ double spmv_rows(const SpMat<T>& M, const T* __restri
             int pi = -1;
             if (M.vrow) { pi = M.vpart[v]; r = M.vrow[v]; }
             if (pi >= 0) M.part[pi] = d;      // a segment of a cut row: k_spmv_fold finishes the row
-            else acc += sp_epilogue<T, MODE>(E, r, d);
+            else sp_epilogue<T, MODE>(E, r, d, acc);
         }
     }
-    return acc;
 }
 
 template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_yupd(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
-    double acc[1] = {spmv_rows<T, L, NT, 0>(M, x, E)};
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, 0>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
 template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_t_finish(SpMat<T> M, const T* __restrict__ yupd, SpEpi<T> E, double* __restrict__ parts, int slot0) {
-    double acc[1] = {spmv_rows<T, L, NT, 1>(M, yupd, E)};
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, 1>(M, yupd, E, acc);
+    block_reduce_store<1>(acc, 0u, parts, slot0);
+}
+
+// what k_spmv_q_algrad needs beside the entries: the rows as the caller gave them (not the virtual rows) and the cut rows
+struct SpRows {
+    const int64_t* rowptr;   // [n + 1]
+    const int32_t* crow;     // [ncut] the cut rows, ascending
+    const int32_t* cptr;     // [ncut + 1] where a cut row's segment sums start in `part`
+    int ncut;
+    int64_t S;               // segment length
+    int64_t n;
+};
+
+// rows of Q, c = Identity: grad = (Q x + q) + yhat ; partials: slot0 the f terms, slot0 + 1 the penalty terms.
+// The gradient AND the two scalars are bit for bit those of k_spmv_q followed by k_algrad_elem in its mode 2, so the
+// kernel is launched on k_algrad_elem's grid and keeps that kernel's summation tree: a workgroup owns the elements
+// k_algrad_elem's workgroup of the same number owns — tiles of BLOCK packs, tile k of workgroup b starting at pack
+// (b + k gridDim.x) BLOCK.  The L-lane groups walk the tile's rows (spmv_row: the row sums of the product kernel), each
+// row's first lane runs the row's epilogue and leaves the row's two terms in LDS; then thread t adds the terms of ITS pack
+// in element order, as k_algrad_elem's thread t does, and block_reduce_store<2> does the rest.
+// A cut row is summed as the product kernel and k_spmv_fold sum it: its segments by the L-lane groups of the whole
+// workgroup (spmv_row per segment, the sums into `part`), then one wave adds the segment sums (lane l the sums l, l + 64,
+// ..., the fixed xor tree) and runs the epilogue.  No second launch, no exchange between workgroups.
+template <class T, int L, bool NT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_q_algrad(SpMat<T> M, SpRows R, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    constexpr int N = PackN<T>::N, TILE = BLOCK * N, RPB = BLOCK / L;
+    __shared__ double shf[TILE], shp[TILE];
+    const int sub = threadIdx.x % L, grp = threadIdx.x / L, lane = threadIdx.x & 63;
+    const int64_t n = R.n, npacks = (n + N - 1) / N;
+    double acc[2] = {0.0, 0.0};
+    for (int64_t c0 = (int64_t)blockIdx.x * BLOCK; c0 < npacks; c0 += (int64_t)gridDim.x * BLOCK) {
+        const int64_t i0 = c0 * N;
+        const int64_t iend = i0 + TILE < n ? i0 + TILE : n;
+        for (int it = 0; it < N * L; ++it) {
+            const int lr = it * RPB + grp;
+            const int64_t r = i0 + lr;
+            const int64_t rc = r < n ? r : n - 1;                 // (unconditional loads; the row is dropped below)
+            const int64_t s = R.rowptr[rc];
+            int64_t e = R.rowptr[rc + 1];
+            const bool whole = r < n && !(R.ncut && e - s > R.S);
+            if (!whole) e = s;
+            const double d = spmv_row<T, L, NT>(M, x, s, e, sub);
+            if (sub == 0 && whole) {
+                double t2[2] = {0.0, 0.0};
+                sp_epilogue<T, 2>(E, r, d, t2);
+                shf[lr] = t2[0]; shp[lr] = t2[1];
+            }
+        }
+        if (R.ncut) {
+            int j = 0;
+            for (int hi = R.ncut; j < hi;) {                      // the first cut row at or behind i0
+                const int mid = (j + hi) >> 1;
+                if ((int64_t)R.crow[mid] < i0) j = mid + 1; else hi = mid;
+            }
+            for (; j < R.ncut && (int64_t)R.crow[j] < iend; ++j) {
+                const int64_t r = R.crow[j];
+                const int64_t s = R.rowptr[r], e = R.rowptr[r + 1];
+                const int k0 = R.cptr[j], k1 = R.cptr[j + 1];
+                for (int k = grp; k < k1 - k0; k += RPB) {
+                    const int64_t ss = s + (int64_t)k * R.S;
+                    const int64_t ee = ss + R.S < e ? ss + R.S : e;
+                    const double d = spmv_row<T, L, NT>(M, x, ss, ee, sub);
+                    if (sub == 0) M.part[k0 + k] = d;
+                }
+                __syncthreads();                                  // (the segment sums of this row are in `part`)
+                if (threadIdx.x < 64) {
+                    double a = 0.0;
+                    for (int k = k0 + lane; k < k1; k += 64) a += M.part[k];
+#pragma unroll
+                    for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
+                    if (lane == 0) {
+                        double t2[2] = {0.0, 0.0};
+                        sp_epilogue<T, 2>(E, r, a, t2);
+                        shf[r - i0] = t2[0]; shp[r - i0] = t2[1];
+                    }
+                }
+            }
+        }
+        __syncthreads();
+#pragma unroll
+        for (int e = 0; e < N; ++e) {
+            const int at = (int)threadIdx.x * N + e;
+            if (i0 + at < n) { acc[0] += shf[at]; acc[1] += shp[at]; }
+        }
+        __syncthreads();
+    }
+    block_reduce_store<2>(acc, 0u, parts, slot0);
+}
+
+// rows of Q: E.out = Q x (if kept) ; partials: slot0 the f terms (zeros when E.x is null)
+template <class T, int L, bool NT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_q(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, 3>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
 // the cut rows: one wave per row adds the row's segment sums (lane l the sums l, l + 64, ... in order, then the fixed
-// xor tree) and runs the row's epilogue; its block partials continue the slot behind the row kernel's (vb0).
+// xor tree) and runs the row's epilogue; its block partials continue the slot (MODE 2: the two slots) behind the row
+// kernel's (vb0).
 template <class T, int MODE>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_fold(const double* __restrict__ part, const int32_t* __restrict__ crow, const int32_t* __restrict__ cptr, int ncut,
             SpEpi<T> E, double* __restrict__ parts, int slot0, int vb0) {
     const int lane = threadIdx.x & 63;
-    double acc[1] = {0.0};
+    constexpr int K = sp_nacc<MODE>();
+    double acc[K] = {};
     for (int j = blockIdx.x * WAVES + (threadIdx.x >> 6); j < ncut; j += gridDim.x * WAVES) {
         const int k1 = cptr[j + 1];
         double a = 0.0;
         for (int k = cptr[j] + lane; k < k1; k += 64) a += part[k];
 #pragma unroll
         for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
-        if (lane == 0) acc[0] += sp_epilogue<T, MODE>(E, crow[j], a);
+        if (lane == 0) sp_epilogue<T, MODE>(E, crow[j], a, acc);
     }
-    block_reduce_store<1>(acc, 0u, parts, slot0, vb0 + (int)blockIdx.x);
+    block_reduce_store<K>(acc, 0u, parts, slot0, vb0 + (int)blockIdx.x);
 }
 
 }  // namespace bz

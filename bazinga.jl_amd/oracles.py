@@ -104,6 +104,97 @@ class Quadratic(ProximableFunction):
         return x.dtype.type(0.5) * np.dot(x, Qx) + np.dot(self.q, x)
 
 
+class SparseQuadratic(ProximableFunction):
+    """ProximalOperators.Quadratic(Q, q) with a sparse Q: f(x) = 0.5 x'Qx + q'x, Q symmetric n-by-n in CSR (indptr[n + 1],
+    indices[nnz] 0-based, data[nnz]), never densified.  The conventions of SparseAffine: the column indices of a row
+    need not be sorted, an index that occurs twice in a row contributes twice, an empty row gives (Qx)_i = 0.  Symmetry
+    is the caller's contract on the device; check_symmetric=True compares the summed (row, col) -> value maps of Q and
+    Q' exactly here.  __call__ / gradient below are numpy with ref.Quadratic's formulas (the host outer loop, and the
+    generic-oracle protocol); on the device the kind is BZ_F_SPARSE_QUADRATIC."""
+
+    def __init__(self, indptr, indices, data, q, *, check_symmetric=True):
+        ip, ix = np.asarray(indptr), np.asarray(indices)
+        self.data = np.ascontiguousarray(data)
+        self.q = np.ascontiguousarray(q)
+        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or self.q.ndim != 1:
+            raise ValueError("indptr, indices, data and q must be one-dimensional")
+        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr and indices must be integer arrays")
+        if self.data.dtype not in (np.float64, np.float32) or self.q.dtype not in (np.float64, np.float32):
+            raise ValueError("data and q must be float64 or float32")
+        self.n = self.q.shape[0]
+        if self.n <= 0 or self.n > 2 ** 31 - 1:
+            raise ValueError("n must be in 1 .. 2^31 - 1")
+        if ip.shape[0] != self.n + 1:
+            raise ValueError(f"indptr must have length n + 1 = {self.n + 1}")
+        if ix.shape[0] != self.data.shape[0]:
+            raise ValueError("indices and data must have the same length")
+        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
+        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
+            raise ValueError(f"column indices must lie in [0, {self.n})")
+        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
+        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
+        self._rows = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+        if check_symmetric and not self._is_symmetric():
+            raise ValueError("Q must be symmetric (the summed entries of Q and Q' differ)")
+
+    def _is_symmetric(self):
+        """the (row, col) -> summed value maps of Q and Q', compared exactly (the sums in float64, entry order)"""
+        def summed(r, c):
+            key = r * self.n + c
+            u, inv = np.unique(key, return_inverse=True)
+            return u, np.bincount(inv, weights=self.data.astype(np.float64), minlength=u.shape[0])
+        cols = self.indices.astype(np.int64)
+        (ka, va), (kb, vb) = summed(self._rows, cols), summed(cols, self._rows)
+        if np.array_equal(ka, kb):
+            return bool(np.array_equal(va, vb))
+        # (an entry stored on one side only counts as a zero on the other)
+        keys = np.union1d(ka, kb)
+        fa, fb = np.zeros(keys.shape[0]), np.zeros(keys.shape[0])
+        fa[np.searchsorted(keys, ka)] = va
+        fb[np.searchsorted(keys, kb)] = vb
+        return bool(np.array_equal(fa, fb))
+
+    @property
+    def nnz(self):
+        return int(self.indices.shape[0])
+
+    @classmethod
+    def from_dense(cls, Q, q, **kw):
+        Q = np.asarray(Q)
+        if Q.ndim != 2 or Q.shape[0] != Q.shape[1]:
+            raise ValueError("Q must be n-by-n")
+        mask = Q != 0
+        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
+        indices = np.nonzero(mask)[1].astype(np.int32)
+        return cls(indptr, indices, np.ascontiguousarray(Q[mask]), q, **kw)
+
+    @classmethod
+    def from_scipy(cls, M, q, **kw):
+        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        return cls(M.indptr, M.indices, M.data, q, **kw)
+
+    def toarray(self):
+        Q = np.zeros((self.n, self.n), self.data.dtype)
+        np.add.at(Q, (self._rows, self.indices), self.data)
+        return Q
+
+    def _Qx(self, x):
+        return np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.n).astype(x.dtype, copy=False)
+
+    def __call__(self, x):
+        return x.dtype.type(0.5) * np.dot(x, self._Qx(x)) + np.dot(x, self.q)
+
+    def gradient(self, dfx, x):
+        dfx[...] = self._Qx(x)
+        fx = x.dtype.type(0.5) * np.dot(x, dfx)
+        dfx += self.q
+        return fx + np.dot(x, self.q)
+
+
 class Stencil5ptQuadratic(ProximableFunction):
     """f(x) = 0.5 x'A_h x - b'x on an nx-by-ny grid (row-major), A_h the 5-point Laplacian
     (4,-1,-1,-1,-1) with homogeneous Dirichlet halo — the structured `Quadratic` of BASELINE
@@ -438,7 +529,7 @@ def _vec(a, dtype, n, name):
     return v
 
 
-_LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, Stencil5ptQuadratic))
+_LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, Stencil5ptQuadratic))
 _LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
@@ -558,6 +649,20 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.f_A = ptr(np.ascontiguousarray(f.Q, dtype=dtype))
         d.f_rows = n
         d.f_b = ptr(_vec(f.q, dtype, n, "q"))
+    elif isinstance(f, SparseQuadratic):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("SparseQuadratic is not lowered in the slack (ALS) form")
+        if isinstance(c, DenseAffine):
+            raise UnsupportedOracle("SparseQuadratic is not lowered beside a dense c (DenseAffine)")
+        if f.n != n:
+            raise ValueError(f"Q must be {n}-by-{n}")
+        d.f_kind = L.BZ_F_SPARSE_QUADRATIC
+        d.f_sp_rowptr = ptr(f.indptr)
+        d.f_sp_col = ptr(f.indices)
+        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
+        d.f_sp_nnz = f.nnz
+        d.f_b = ptr(_vec(f.q, dtype, n, "q"))
     elif isinstance(f, Stencil5ptQuadratic):
         d.f_kind = L.BZ_F_STENCIL5
         d.f_grid_nx, d.f_grid_ny = f.nx, f.ny
@@ -610,7 +715,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         # what the library refuses with this kind, refused here before any device call
         if slack:
             raise UnsupportedOracle("SparseAffine is not lowered in the slack (ALS) form")
-        if not isinstance(f, (Zero, DiagQuadratic)):
+        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic)):
             raise UnsupportedOracle(f"SparseAffine is lowered with an element-wise f (Zero, DiagQuadratic), not {type(f).__name__}")
         if isinstance(D, PairwiseSet):
             raise UnsupportedOracle("pairwise D sets need c = IdentityFunction")

@@ -113,6 +113,45 @@ def budget_bands(n: int, m: int, dtype=np.float64):
             "fb": (2.0 * uniform(2, n) - 1.0).astype(dtype)}
 
 
+def laplacian_2d(nx: int, ny: int, dtype=np.float64):
+    """The matrix of Stencil5ptQuadratic as CSR: the 5-point Laplacian (4, -1, -1, -1, -1) on an nx-by-ny grid (row-major,
+    index = i*ny + j) with the homogeneous Dirichlet halo dropped.  Entry order per row: centre, west, east, north, south."""
+    i, j = np.divmod(np.arange(nx * ny, dtype=np.int64), ny)
+    c = i * ny + j
+    cols = np.stack([c, c - 1, c + 1, c - ny, c + ny], axis=1)
+    keep = np.stack([np.ones(nx * ny, bool), j > 0, j < ny - 1, i > 0, i < nx - 1], axis=1)
+    vals = np.tile(np.array([4.0, -1.0, -1.0, -1.0, -1.0]), (nx * ny, 1))
+    indptr = np.concatenate(([0], np.cumsum(keep.sum(axis=1)))).astype(np.int64)
+    return {"indptr": indptr, "indices": cols[keep].astype(np.int32), "data": vals[keep].astype(dtype), "n": nx * ny}
+
+
+def sparse_qp(n: int, m: int, seed: int = SEED, dtype=np.float64):
+    """A sparse QP: min 0.5 x'Qx + q'x over the constraints of budget_bands(n, m), with g = IndBox(0, 1).  Q is symmetric
+    and strictly diagonally dominant (positive definite) with about seven entries per row: the off-diagonals at the
+    distances 1, 7 and 31, w_k(i) = -(0.1 + 0.4 u_k) between i and i + d_k, and the diagonal 0.5 + u4 plus the row's
+    absolute off-diagonal sum.  q_i = 2 u5 - 1.  The entries of a row are stored by ascending column."""
+    if n < 32:
+        raise ValueError("sparse_qp needs n >= 32")
+    i = np.arange(n, dtype=np.int64)
+    rows, cols, vals = [], [], []
+    offsum = np.zeros(n)
+    for k, dist in enumerate((1, 7, 31)):
+        w = -(0.1 + 0.4 * uniform(1 + k, n - dist, seed=seed))
+        rows += [i[:-dist], i[dist:]]
+        cols += [i[dist:], i[:-dist]]
+        vals += [w, w]
+        offsum[:-dist] += -w
+        offsum[dist:] += -w
+    rows.append(i); cols.append(i); vals.append(0.5 + uniform(4, n, seed=seed) + offsum)
+    rows, cols, vals = np.concatenate(rows), np.concatenate(cols), np.concatenate(vals)
+    order = np.lexsort((cols, rows))
+    indptr = np.concatenate(([0], np.cumsum(np.bincount(rows, minlength=n)))).astype(np.int64)
+    out = budget_bands(n, m, dtype)
+    out.update({"Q_indptr": indptr, "Q_indices": cols[order].astype(np.int32), "Q_data": vals[order].astype(dtype),
+                "fq": (2.0 * uniform(5, n, seed=seed) - 1.0).astype(dtype)})
+    return out
+
+
 def portfolio(n: int, dtype=np.float64, rank: int | None = None):
     """A stand-in for the absent demo/portfolio_data (demo/portfolio.jl:70-91: Q, rho, mu, ub), from the uniform stream:
 

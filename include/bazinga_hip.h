@@ -55,6 +55,13 @@ extern "C" {
                                     (test/problems/test_verbose.jl:22)                 */
 #define BZ_F_QUADRATIC       4   /* 0.5 x'Qx + q'x, dense symmetric Q, ProximalOperators.
                                     Quadratic (test/problems/test_nonconvex_qp.jl:14)  */
+#define BZ_F_SPARSE_QUADRATIC 6  /* 0.5 x'Qx + q'x, symmetric Q in CSR (f_sp_*), q in f_b: ProximalOperators.Quadratic
+                                    with a sparse Q, never densified.  The conventions of c_sp_*: the column indices of
+                                    a row need not be sorted; an index that occurs twice in a row contributes twice; an
+                                    empty row gives (Qx)_i = 0; n <= 2^31 - 1, nnz is 64-bit.  Symmetry is the caller's
+                                    contract (not checked).  c Identity or SparseAffine, slack = 0, one rank, D Zero /
+                                    Free / Box (and, with c = Identity, the pairwise sets); refused (BZ_ERR_UNSUPPORTED):
+                                    slack = 1, c = DenseAffine, more than one rank, callbacks mixed in.               */
 /* g: proximable cost.  prox!(z,g,x,gamma)->g(z)                                     */
 #define BZ_G_ZERO            0   /* zero.jl:22-25, ProximalOperators.Zero / IndFree   */
 #define BZ_G_NORM_L1         1   /* ProximalOperators.NormL1(lambda) (test_verbose.jl:23) */
@@ -71,8 +78,8 @@ extern "C" {
                                     demo/obstacle.jl:93-113 (c(x) = x1 + T x2 - x3, T = SymTridiagonal(2, -1)).
                                     The column indices of a row need not be sorted; an index that occurs twice in a
                                     row contributes twice; an empty row gives c_i = -b_i; an empty column gives
-                                    (A'v)_j = 0.  n <= 2^31 - 1, nnz is 64-bit.  slack = 0, one rank, f Zero or
-                                    DiagQuadratic, D Zero / Free / Box; affine_refresh is ignored (no images).    */
+                                    (A'v)_j = 0.  n <= 2^31 - 1, nnz is 64-bit.  slack = 0, one rank, f Zero,
+                                    DiagQuadratic or SparseQuadratic, D Zero / Free / Box; affine_refresh is ignored (no images).    */
 /* D: closed set.  proj!(s,D,v)                                                      */
 #define BZ_D_ZERO            0   /* src/projections/zeroSet.jl:17-20                  */
 #define BZ_D_FREE            1   /* src/projections/freeSet.jl:17-20                  */
@@ -172,7 +179,7 @@ typedef struct {
                                       (Zero | DiagQuadratic | LeastSquares | Quadratic, DenseAffine), where
                                       ny is arbitrary; n must be a whole number of 16-byte packs (2 fp64 /
                                       4 fp32 elements) so that s starts aligned.  Refused with slack = 1:
-                                      SparseAffine, Stencil5pt f, LeastSquares / Quadratic with c = Identity,
+                                      SparseAffine, Stencil5pt f, SparseQuadratic f, LeastSquares / Quadratic with c = Identity,
                                       pairwise D, callbacks, more than one rank */
     int64_t n;                     /* length of x (local shard)                       */
     int64_t ny;                    /* length of y / c(x) (local shard)                */
@@ -204,6 +211,12 @@ typedef struct {
     bz_c_eval_fn     cb_c_eval;
     bz_c_jtprod_fn   cb_c_jtprod;
     bz_D_proj_fn     cb_D_proj;
+    /* f, SPARSE_QUADRATIC (with q[n] in f_b): Q in CSR, copied (and validated: BZ_ERR_ARG) at bz_problem_create.
+       (These four sit in front of c_sp_*: the sparse constraint's fields stay the descriptor's last four.) */
+    const int64_t* f_sp_rowptr;    /* rowptr[n + 1], rowptr[0] = 0, non-decreasing, rowptr[n] = nnz */
+    const int32_t* f_sp_col;       /* col[nnz], 0-based, in [0, n)                    */
+    const void*    f_sp_val;       /* val[nnz]                                        */
+    int64_t        f_sp_nnz;
     /* c, SPARSE_AFFINE (with c_b[ny]): A in CSR, copied (and validated: BZ_ERR_ARG) at bz_problem_create */
     const int64_t* c_sp_rowptr;    /* rowptr[ny + 1], rowptr[0] = 0, non-decreasing, rowptr[ny] = nnz */
     const int32_t* c_sp_col;       /* col[nnz], 0-based, in [0, n)                    */

@@ -35,6 +35,8 @@ Base.@kwdef mutable struct ProblemDesc
     # generic oracles (all four kinds BZ_*_CALLBACK): host callbacks, see lower_generic!
     cb_user::Ptr{Cvoid} = C_NULL; cb_f_gradient::Ptr{Cvoid} = C_NULL; cb_g_prox::Ptr{Cvoid} = C_NULL
     cb_c_eval::Ptr{Cvoid} = C_NULL; cb_c_jtprod::Ptr{Cvoid} = C_NULL; cb_D_proj::Ptr{Cvoid} = C_NULL
+    # f = SparseQuadratic (BZ_F_SPARSE_QUADRATIC): symmetric Q in CSR, 0-based; q in f_b
+    f_sp_rowptr::Ptr{Cvoid} = C_NULL; f_sp_col::Ptr{Cvoid} = C_NULL; f_sp_val::Ptr{Cvoid} = C_NULL; f_sp_nnz::Int64 = 0
     # c = SparseAffine (BZ_C_SPARSE_AFFINE): A in CSR, 0-based
     c_sp_rowptr::Ptr{Cvoid} = C_NULL; c_sp_col::Ptr{Cvoid} = C_NULL; c_sp_val::Ptr{Cvoid} = C_NULL; c_sp_nnz::Int64 = 0
 end
@@ -121,6 +123,22 @@ end
 Bazinga.eval!(cx, c::SparseAffine, x) = (cx .= c.A * x .- c.b; nothing)
 Bazinga.jtprod!(jtv, c::SparseAffine, x, v) = (jtv .= c.A' * v; nothing)
 
+"""`SparseQuadratic(Q::SparseMatrixCSC, q)`: f(x) = 0.5 x'Qx + q'x with a sparse symmetric Q that is never densified
+(ProximalOperators.Quadratic with a sparse Q).  Symmetry is the caller's contract: the CSC arrays of a symmetric Q ARE its
+CSR arrays, made 0-based here."""
+struct SparseQuadratic{T} <: Bazinga.ProximableFunction
+    Q::SparseMatrixCSC{T,Int}; q::Vector{T}
+    rowptr::Vector{Int64}; col::Vector{Int32}; val::Vector{T}
+    SparseQuadratic(Q::SparseMatrixCSC{T}, q::Vector{T}) where {T} =
+        new{T}(Q, q, Int64.(Q.colptr .- 1), Int32.(Q.rowval .- 1), Vector{T}(Q.nzval))
+end
+function Bazinga.gradient!(dfx, f::SparseQuadratic, x)
+    dfx .= f.Q * x
+    fx = sum(x .* dfx) / 2
+    dfx .+= f.q
+    return fx + sum(x .* f.q)
+end
+
 "`LBFGS(M; compact = nothing)`: how the operator is evaluated (bz_panoc_opts.lbfgs_compact) — `false` the two-loop recursion in the reference's order, `true` the compact representation, `nothing` (default) compact where the one-pass kernel applies"
 struct LBFGS
     memory::Int; compact::Union{Nothing,Bool}
@@ -145,6 +163,8 @@ function lower_f!(d, f::ProximalOperators.LeastSquares)
 end
 lower_f!(d, f::ProximalOperators.Quadratic) = (d.f_kind = 4; d.f_A = pointer(f.Q); d.f_rows = size(f.Q, 1);
                                                d.f_b = pointer(f.q); nothing)      # Q symmetric: layout-agnostic
+lower_f!(d, f::SparseQuadratic) = (d.f_kind = 6; d.f_sp_rowptr = pointer(f.rowptr); d.f_sp_col = pointer(f.col);
+                                   d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val); d.f_b = pointer(f.q); nothing)
 lower_f!(d, f) = :generic
 
 lower_g!(d, g::Bazinga.Zero) = (d.g_kind = 0)
