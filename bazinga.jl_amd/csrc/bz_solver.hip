@@ -9,6 +9,7 @@
 #include "bz_solver.h"
 #include "bz_spmv.h"
 #include "bz_als_dense.h"
+#include "bz_csr_host.h"
 
 #include <hip/hip_ext.h>
 
@@ -137,6 +138,7 @@ struct CreateKnobs {
     std::optional<int> dense_kp = env_opt("BZ_DENSE_KP");                // k_dense_fused's packs per row and lane
     std::optional<int> spmv_l = env_opt("BZ_SPMV_L");    // lanes per row of the CSR row kernels (a power of two <= 64)
     int spq_fused = env_int("BZ_SPQ_FUSED", 1);          // 0: the sparse quadratic f with c = Identity as product + k_algrad_elem
+    int spls_fused = env_int("BZ_SPLS_FUSED", 1);        // 0: the sparse least squares f with c = Identity as two products + k_algrad_elem
     // test-only
     int test_dense_timeout = env_int("BZ_TEST_DENSE_TIMEOUT", 0);        // the k-th k_dense_fused exchange is sabotaged
     unsigned dense_spin = (unsigned)env_ll("BZ_DENSE_SPIN", 0);          // k_dense_fused's poll bound (0: the default)
@@ -198,6 +200,19 @@ template <class T> class Solver final : public SolverBase {
             if (n > (int64_t)std::numeric_limits<int32_t>::max())
                 throw Error(BZ_ERR_ARG, "SparseQuadratic: n must fit 32-bit column indices");
         }
+        sparse_ls = d.f_kind == BZ_F_SPARSE_LEAST_SQUARES;
+        if (sparse_ls) {
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: the slack (ALS) form is not lowered with a sparse least-squares f");
+            if (d.c_kind == BZ_C_DENSE_AFFINE)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: a sparse least-squares f beside a dense c (DenseAffine) is not lowered");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: the sparse least-squares f is not sharded (one rank)");
+            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: the sparse least-squares f does not mix with host callbacks");
+            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
+                throw Error(BZ_ERR_ARG, "SparseLeastSquares needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and b[m]");
+            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
+                throw Error(BZ_ERR_ARG, "SparseLeastSquares: n and m must fit 32-bit indices");
+        }
         if (d.c_kind == BZ_C_SPARSE_AFFINE) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: the slack (ALS) form is not lowered with a sparse c");
             if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine is not sharded (one rank)");
@@ -250,7 +265,7 @@ template <class T> class Solver final : public SolverBase {
             if (ctx->nranks > 1 && (!ctx->p2p_on || slack))
                 throw Error(BZ_ERR_UNSUPPORTED, "a row-sharded DenseAffine needs the p2p mailboxes and no slack");
         }
-        if ((d.f_kind < BZ_F_ZERO || d.f_kind > BZ_F_QUADRATIC) && !sparse_f && !generic_)
+        if ((d.f_kind < BZ_F_ZERO || d.f_kind > BZ_F_QUADRATIC) && !sparse_f && !sparse_ls && !generic_)
             throw Error(BZ_ERR_UNSUPPORTED, "smooth-cost kind not lowered to the device");
         dense_f = d.f_kind == BZ_F_LEAST_SQUARES || d.f_kind == BZ_F_QUADRATIC;
         if (dense_f) {
@@ -339,6 +354,15 @@ template <class T> class Solver final : public SolverBase {
             sparse_f_create(d);
             upload(fb_, d.f_b, nx);
             FR_.alloc(nx);
+        }
+        if (sparse_ls) {
+            // (the generic kernel chain too; the value convention of the dense LeastSquares: sum r^2, halved by fscale)
+            frows = d.f_rows;
+            sparse_ls_create(d);
+            upload(fb_, d.f_b, frows);
+            FR_.alloc(frows);
+            if (d.c_kind == BZ_C_SPARSE_AFFINE || !spls_fused_on()) DFX_.alloc(nx);
+            fscale = T(0.5);
         }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             A_.alloc((size_t)ny * nx);
@@ -819,7 +843,7 @@ template <class T> class Solver final : public SolverBase {
     DBuf<T> A_, cb_, CX_, YU_, GT_;          // DenseAffine c: A[ny][n], b, c(x), yupd, A'v row-chunk partials
     int rows_per_chunk = 1, nrowchunks = 1;
     DBuf<T> FA_, fb_, FR_, DFX_, FGT_;       // dense f: matrix, vector, residual / Qx, gradient of f, A_f'r row-chunk partials
-    bool dense_f = false, sparse_f = false, lp_g = false;
+    bool dense_f = false, sparse_f = false, lp_g = false;      // (sparse_f: the sparse quadratic; sparse_ls: at the end)
     // generic oracles (host callbacks): host mirrors of the vectors the callbacks read and write
     bool generic_ = false;
     std::vector<T> hx_, hg_, hy_, hz_, hres_, hdfx_, hjtv_, hcx_, ht_, hs_, hmu_, hmuy_, hyv_;
@@ -1776,7 +1800,7 @@ template <class T> class Solver final : public SolverBase {
     };
     SpCsr spA_, spAt_, spQ_;               // (Q: the sparse quadratic f; symmetric, so no transpose)
     DBuf<int64_t> spQ_rowptr_;             // a cut Q: the row pointers as given (k_spmv_q_algrad walks rows, not virtual rows)
-    std::string sp_form_[4];               // by the epilogue's MODE
+    std::string sp_form_[4];               // by the epilogue's MODE (MODE 4 .. 6: spls_form_)
     template <class V> static void sp_upload(DBuf<V>& dst, const std::vector<V>& src) {
         dst.alloc(src.size());
         if (!src.empty()) BZ_HIP(hipMemcpy(dst.p, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
@@ -1869,25 +1893,24 @@ template <class T> class Solver final : public SolverBase {
         sp_form_[2] = sp_form("k_spmv_q_algrad", spQ_);
         sp_form_[3] = sp_form("k_spmv_q", spQ_);
     }
-    // c = SparseAffine: validate the caller's CSR on a host copy, build A' by a stable counting sort (a column's entries stay
-    // in ascending row order) and put both in HBM
+    // f = SparseLeastSquares: A_f validated on a host copy; A_f and A_f' in HBM with the segment and lane rules of A and A'
+    void sparse_ls_create(const bz_problem_desc& d) {
+        std::vector<int64_t> rp, tp; std::vector<int32_t> col, tcol; std::vector<T> val, tval;
+        sp_read("SparseLeastSquares", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
+        csr_transpose(frows, nx, rp, col, val, tp, tcol, tval);
+        sp_build(spF_, frows, nx, rp, col, val);
+        sp_build(spFt_, nx, frows, tp, tcol, tval);
+        spls_form_[0] = sp_form("k_spmv_ls_r", spF_);
+        spls_form_[1] = sp_form("k_spmv_ls_t_algrad", spFt_);
+        spls_form_[2] = sp_form("k_spmv_ls_t", spFt_);
+    }
+    // c = SparseAffine: validate the caller's CSR on a host copy, build A' (csr_transpose: a column's entries stay in ascending row
+    // order) and put both in HBM
     void sparse_create(const bz_problem_desc& d) {
         const int64_t nnz = d.c_sp_nnz;
-        std::vector<int64_t> rp; std::vector<int32_t> col; std::vector<T> val;
+        std::vector<int64_t> rp, tp; std::vector<int32_t> col, tcol; std::vector<T> val, tval;
         sp_read("SparseAffine", "ny", ny, d.c_sp_rowptr, d.c_sp_col, d.c_sp_val, nnz, rp, col, val);
-        std::vector<int64_t> tp((size_t)n + 1, 0);
-        for (int64_t k = 0; k < nnz; ++k) ++tp[(size_t)col[k] + 1];
-        for (int64_t j = 0; j < n; ++j) tp[j + 1] += tp[j];
-        std::vector<int32_t> tcol((size_t)nnz);
-        std::vector<T> tval((size_t)nnz);
-        {
-            std::vector<int64_t> next(tp.begin(), tp.end() - 1);
-            for (int64_t r = 0; r < ny; ++r)
-                for (int64_t k = rp[r]; k < rp[r + 1]; ++k) {
-                    const int64_t at = next[col[k]]++;
-                    tcol[at] = (int32_t)r; tval[at] = val[k];
-                }
-        }
+        csr_transpose(ny, n, rp, col, val, tp, tcol, tval);
         sp_build(spA_, ny, n, rp, col, val);
         sp_build(spAt_, n, ny, tp, tcol, tval);
         sp_form_[0] = sp_form("k_spmv_yupd", spA_);
@@ -1907,8 +1930,9 @@ template <class T> class Solver final : public SolverBase {
             }
         });
     }
-    // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A', 3: k_spmv_q over Q) and, for a cut
-    // matrix, the fold of its cut rows; returns the number of block partials left in `slot`
+    // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A', 3: k_spmv_q over Q, 4: k_spmv_ls_r
+    // over A_f, 5: k_spmv_ls_t_algrad and 6: k_spmv_ls_t over A_f') and, for a cut matrix, the fold of its cut rows; returns
+    // the number of block partials left in `slot`
     template <int MODE> int sp_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
         const double bytes = m.bytes() + vec_bytes;
         const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
@@ -1920,10 +1944,13 @@ template <class T> class Solver final : public SolverBase {
             const int64_t rpb = BLOCK / L;
             g = (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - gfold, (m.nv + rpb - 1) / rpb));
             pending_bytes_ += bytes;
-            nm(sp_form_[MODE].c_str());
+            nm((MODE < 4 ? sp_form_[MODE & 3] : spls_form_[MODE >= 4 ? MODE - 4 : 0]).c_str());
             if constexpr (MODE == 0) launch(C_GEMV, k_spmv_yupd<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 1) launch(C_GEMV, k_spmv_t_finish<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else launch(C_GEMV, k_spmv_q<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else if constexpr (MODE == 3) launch(C_GEMV, k_spmv_q<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else if constexpr (MODE == 4) launch(C_GEMV, k_spmv_ls_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else if constexpr (MODE == 5) launch(C_GEMV, k_spmv_ls_t_algrad<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else launch(C_GEMV, k_spmv_ls_t<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
         };
         sp_with_lanes(m.L, nt, go);
         if (gfold) {
@@ -1940,10 +1967,11 @@ template <class T> class Solver final : public SolverBase {
         return sp_pass<0>(spA_, x, E, slot, vecs);
     }
     // rows of A': grad = grad f(x) + A'yhat and the f partials -> slot
-    // (the sparse quadratic f: its terms from FR_ = Q x, which spq_product has left there)
+    // (the sparse quadratic f: its terms from FR_ = Q x, which spq_product has left there ; the sparse least squares f: its
+    // gradient from DFX_ = A_f' r, which spls_product has left there, and no f term)
     int spmv_t_finish(const T* x, T* grad, int slot) {
-        SpEpi<T> E{nullptr, nullptr, grad, x, P, sparse_f ? (const T*)FR_.p : (const T*)nullptr};
-        const double vecs = ((grad ? 1 : 0) + (P.f_kind == BZ_F_DIAG_QUADRATIC || sparse_f ? 3 : 0)) * (double)n * sizeof(T);
+        SpEpi<T> E{nullptr, nullptr, grad, x, P, sparse_f ? (const T*)FR_.p : sparse_ls ? (const T*)DFX_.p : (const T*)nullptr};
+        const double vecs = ((grad ? 1 : 0) + (P.f_kind == BZ_F_DIAG_QUADRATIC || sparse_f ? 3 : 0) + (sparse_ls ? 1 : 0)) * (double)n * sizeof(T);
         return sp_pass<1>(spAt_, YU_.p, E, slot, vecs);
     }
     // rows of Q, c = Identity: the whole AL gradient — grad = (Q x + q) + yhat, the f partials -> slot, the penalty
@@ -1972,6 +2000,48 @@ template <class T> class Solver final : public SolverBase {
     }
     // (pairwise D: the projection of element i needs its partner, which a row's first lane does not have)
     bool spq_fused_on() const { return cenv_.spq_fused && !(desc.D_kind >= BZ_D_VC_PAIRS && desc.D_kind <= BZ_D_XOR_PAIRS); }
+
+    // ---- f = SparseLeastSquares
+    // rows of A_f: r = A_f x - b -> r_out (null: not kept) and the partials of sum r^2 -> slot.  Per row: b (and r).
+    int spls_residual(const T* x, T* r_out, int slot) {
+        SpEpi<T> E{fb_.p, nullptr, r_out, nullptr, P, nullptr};
+        return sp_pass<4>(spF_, x, E, slot, (1 + (r_out ? 1 : 0)) * (double)frows * sizeof(T));
+    }
+    // rows of A_f', c = Identity: grad = A_f' r + yhat (r in FR_) and the penalty partials -> slot.  Per row: x, mu and mu*y
+    // (and D's vector bounds), the gradient.
+    int spls_t_algrad(const T* x, T* grad, int slot) {
+        SpEpi<T> E{nullptr, nullptr, grad, x, P, nullptr};
+        return sp_pass<5>(spFt_, FR_.p, E, slot, (1 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T));
+    }
+    // rows of A_f': A_f' r -> DFX_ (r in FR_)
+    void spls_product() {
+        SpEpi<T> E{nullptr, nullptr, DFX_.p, nullptr, P, nullptr};
+        sp_pass<6>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
+    }
+    // (pairwise D: the projection of element j needs its partner, which a row's first lane does not have)
+    bool spls_fused_on() const { return cenv_.spls_fused && !(desc.D_kind >= BZ_D_VC_PAIRS && desc.D_kind <= BZ_D_XOR_PAIRS); }
+    void spls_algrad(const T* x, T* grad, int slot0) {
+        slot_n[slot0] = spls_residual(x, FR_.p, slot0);
+        if (desc.c_kind == BZ_C_SPARSE_AFFINE) {
+            // four launches: rows of A_f, rows of A_f' (grad f -> DFX_), rows of A, rows of A' (which adds DFX_ in)
+            spls_product();
+            slot_n[slot0 + 1] = spmv_yupd(x, cx_keep_, YU_.p, slot0 + 1);
+            spmv_t_finish(x, grad, (int)SL_SCRATCH);                  // (no f term here: slot0 is the first launch's)
+            gather(slot0, 2, 0u, 2u);
+            return;
+        }
+        if (spls_fused_on()) {
+            // c = Identity: two row launches, no element-wise kernel
+            slot_n[slot0 + 1] = spls_t_algrad(x, grad, slot0 + 1);
+        } else {
+            // the three-launch form: the plain product, then the element-wise kernel in its mode 1
+            spls_product();
+            slot_n[slot0 + 1] = grid;
+            mv(3 + pstreams(false, true, false));
+            launch(C_ALGRAD, k_algrad_elem<T>, grid, x, P, grad, n, parts_.p, slot0, 1, (const T*)DFX_.p);
+        }
+        gather(slot0, 2, 0u);
+    }
 
     // gradient!(dlx, al, x) on the device; partials -> slot0 (f terms), slot0+1 (t^2/mu)
     // row chunks of the transposed product: enough blocks to fill the chip, fixed summation order
@@ -2034,6 +2104,7 @@ template <class T> class Solver final : public SolverBase {
     }
     void algrad(const T* x, T* grad, int slot0) {
         if (generic_) { algrad_generic(x, grad, slot0); return; }
+        if (sparse_ls) { spls_algrad(x, grad, slot0); return; }
         if (desc.c_kind == BZ_C_SPARSE_AFFINE) {
             // two launches: rows of A (c(x), yhat, the penalty partials), rows of A' (A'yhat, grad f, the f partials);
             // the sparse quadratic f: a third in front, rows of Q (Q x -> FR_)
@@ -2149,7 +2220,9 @@ template <class T> class Solver final : public SolverBase {
             gather(slot0, 1, 0u);
             return;
         }
-        if (sparse_f) {
+        if (sparse_ls) {
+            slot_n[slot0] = spls_residual(x, nullptr, slot0);               // f(x) from the rows of A_f, r not kept
+        } else if (sparse_f) {
             if (cenv_.spq_fused) {
                 slot_n[slot0] = spq_product(x, nullptr, true, slot0);       // f(x) from the rows of Q, Q x not kept
             } else {
@@ -3396,6 +3469,11 @@ template <class T> class Solver final : public SolverBase {
         st->n_dense_fallbacks = n_dense_fallbacks_;
         st->n_affine_blends = state_.n_affine_blends;
     }
+
+    // ---- f = SparseLeastSquares (kept behind every older member: their layout is the parent's)
+    bool sparse_ls = false;
+    SpCsr spF_, spFt_;                     // A_f (m x n) and A_f' (n x m)
+    std::string spls_form_[3];             // by the epilogue's MODE - 4
 };
 
 // one-pass kernel of an oracle family: the instantiations live in bz_families_dk*.hip (one file per D class, so that

@@ -1,5 +1,6 @@
 // bz_spmv.h — the CSR row kernels: the sparse affine constraint c(x) = A x - b (BZ_C_SPARSE_AFFINE), the two passes of its AL
-// gradient, and the sparse quadratic f(x) = 0.5 x'Qx + q'x (BZ_F_SPARSE_QUADRATIC), the pass over Q.
+// gradient, the sparse quadratic f(x) = 0.5 x'Qx + q'x (BZ_F_SPARSE_QUADRATIC), the pass over Q, and the sparse least squares
+// f(x) = 0.5 ||A_f x - b||^2 (BZ_F_SPARSE_LEAST_SQUARES), the passes over A_f and A_f'.
 //
 // A and A' are two CSR matrices in HBM (A' is built once, at bz_problem_create, by a stable counting sort).  Both passes
 // are the same row kernel: L lanes (compile time, 1..64, chosen at creation from the mean row length) walk one row, lane
@@ -12,6 +13,10 @@
 //                    AL gradient in one launch, on k_algrad_elem's grid and with its summation tree; Q x never goes to HBM
 //   k_spmv_q         rows of Q:  Q x -> FR (and / or the f terms) for the forms that finish element-wise or in k_spmv_t_finish
 // (Q is symmetric by the caller's contract: no transpose is built.)
+//   k_spmv_ls_r         rows of A_f :  r_i = sum a_ij x_j - b_i -> R (if kept) and the terms r_i^2 (halved on the host)
+//   k_spmv_ls_t_algrad  rows of A_f', c = Identity:  (A_f' r)_j = grad f_j, and on that value what k_algrad_elem does in its
+//                       mode 1 — with k_spmv_ls_r the whole AL gradient in two launches; grad f never goes to HBM
+//   k_spmv_ls_t         rows of A_f':  A_f' r -> DFX for the forms that finish element-wise or in k_spmv_t_finish
 // Rows longer than S entries (S fixed at creation from the matrix alone) are cut into segments that run as rows of
 // their own ("virtual rows": the row pointers refined at the cuts); a segment leaves its sum in a side buffer and
 // k_spmv_fold, one wave per cut row, adds a row's segment sums in a fixed order and runs the row's epilogue.
@@ -35,14 +40,18 @@ template <class T> struct SpMat {
 
 // what a row's value goes into.  MODE 0 (rows of A): cx (if kept), yupd (if wanted: null = eval!(cx, c, x) alone) and
 // the penalty term; MODE 1 (rows of A'): the gradient and the f term; MODE 2 (rows of Q, c = Identity): the gradient, the
-// f term and the penalty term; MODE 3 (rows of Q): Q x (if kept) and the f term (if x is given).
+// f term and the penalty term; MODE 3 (rows of Q): Q x (if kept) and the f term (if x is given); MODE 4 (rows of A_f): the
+// residual (if kept) and its square; MODE 5 (rows of A_f', c = Identity): the gradient and the penalty term; MODE 6 (rows
+// of A_f'): the product alone.
 template <class T> struct SpEpi {
-    const T* b;              // MODE 0: b[ny]
+    const T* b;              // MODE 0: b[ny] ; MODE 4: b[m] of f
     T* cx;                   // MODE 0: c(x) for the caller that keeps it, or null
-    T* out;                  // MODE 0: yupd[ny] or null ; MODE 1, 2: grad[n] or null ; MODE 3: (Q x)[n] or null
-    const T* x;              // MODE 1, 2: x[n] ; MODE 3: x[n], or null for the product alone
+    T* out;                  // MODE 0: yupd[ny] or null ; MODE 1, 2, 5: grad[n] or null ; MODE 3: (Q x)[n] or null ;
+                             // MODE 4: r[m] or null ; MODE 6: (A_f' r)[n]
+    const T* x;              // MODE 1, 2, 5: x[n] ; MODE 3: x[n], or null for the product alone
     ElemParams<T> P;
-    const T* ext;            // MODE 1 with the sparse quadratic f: (Q x)[n], left by k_spmv_q
+    const T* ext;            // MODE 1 with the sparse quadratic f: (Q x)[n], left by k_spmv_q ; with the sparse least
+                             // squares f: (A_f' r)[n], left by k_spmv_ls_t
 };
 
 // scalars a mode leaves per row: MODE 2 the f term and the penalty term, the others one
@@ -80,6 +89,8 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
             const T xv = E.x[r], e = E.ext[r], qv = P.b[r];
             dfx = e + qv;
             fterm = xv * (T(0.5) * e + qv);
+        } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES) {
+            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r)
         }
         if (E.out) E.out[r] = dfx + (T)d;
         acc[0] += (double)fterm;
@@ -97,10 +108,27 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
         if (E.out) E.out[r] = dfx + o.grad;
         acc[0] += (double)fterm;
         acc[1] += (double)o.pterm;
-    } else {
+    } else if constexpr (MODE == 3) {
         const T e = (T)d;
         if (E.out) E.out[r] = e;
         if (E.x) acc[0] += (double)(E.x[r] * (T(0.5) * e + P.b[r]));            // k_fvalue_elem with ext
+    } else if constexpr (MODE == 4) {
+        const T rv = (T)d - E.b[r];                                 // r = A_f x - b ; sum r^2, halved on the host (fscale)
+        if (E.out) E.out[r] = rv;
+        acc[0] += (double)(rv * rv);
+    } else if constexpr (MODE == 5) {
+        // element r of k_algrad_elem in its mode 1 with ext[r] = d: MODE 2's operations in MODE 2's order without the f
+        // term (never launched with a pairwise D, whose projection needs the partner element)
+        const T xv = E.x[r], e = (T)d;
+        const T mu = P.uni >= 1 ? P.mu_uniform : P.mu[r];
+        const T muy = P.uni >= 2 ? T(0) : P.muy[r];
+        const T lo = P.D_lo_vec ? P.D_lo_vec[r] : P.D_lo;
+        const T hi = P.D_hi_vec ? P.D_hi_vec[r] : P.D_hi;
+        const ALOut<T> o = al_elem(BZ_F_ZERO, P.D_kind, xv, T(0), T(0), mu, muy, lo, hi);
+        if (E.out) E.out[r] = e + o.grad;
+        acc[0] += (double)o.pterm;
+    } else {
+        if (E.out) E.out[r] = (T)d;
     }
 }
 
@@ -270,6 +298,33 @@ __global__ void __launch_bounds__(BLOCK)
 k_spmv_q(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
     spmv_rows<T, L, NT, 3>(M, x, E, acc);
+    block_reduce_store<1>(acc, 0u, parts, slot0);
+}
+
+// rows of A_f: r = A_f x - b -> E.out (if kept) ; partials: slot0 the terms r_i^2
+template <class T, int L, bool NT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_ls_r(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, 4>(M, x, E, acc);
+    block_reduce_store<1>(acc, 0u, parts, slot0);
+}
+
+// rows of A_f', c = Identity: grad = A_f' r + yhat ; partials: slot0 the penalty terms
+template <class T, int L, bool NT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_ls_t_algrad(SpMat<T> M, const T* __restrict__ r, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, 5>(M, r, E, acc);
+    block_reduce_store<1>(acc, 0u, parts, slot0);
+}
+
+// rows of A_f': E.out = A_f' r ; partials: slot0 zeros
+template <class T, int L, bool NT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_ls_t(SpMat<T> M, const T* __restrict__ r, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, 6>(M, r, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 

@@ -195,6 +195,78 @@ class SparseQuadratic(ProximableFunction):
         return fx + np.dot(x, self.q)
 
 
+class SparseLeastSquares(ProximableFunction):
+    """ProximalOperators.LeastSquares(A, b) with a sparse A: f(x) = 0.5||A x - b||^2, A m-by-n in CSR (indptr[m + 1],
+    indices[nnz] 0-based, data[nnz]), never densified and never squared into A'A.  The conventions of SparseAffine: the
+    column indices of a row need not be sorted, an index that occurs twice in a row contributes twice, an empty row gives
+    r_i = -b_i and an empty column a zero gradient entry; nnz = 0 is accepted.  __call__ / gradient below are numpy with
+    ref.LeastSquares' formulas (the generic-oracle protocol); on the device the kind is BZ_F_SPARSE_LEAST_SQUARES."""
+
+    def __init__(self, indptr, indices, data, b, n):
+        ip, ix = np.asarray(indptr), np.asarray(indices)
+        self.data = np.ascontiguousarray(data)
+        self.b = np.ascontiguousarray(b)
+        self.n = int(n)
+        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or self.b.ndim != 1:
+            raise ValueError("indptr, indices, data and b must be one-dimensional")
+        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr and indices must be integer arrays")
+        if self.data.dtype not in (np.float64, np.float32) or self.b.dtype not in (np.float64, np.float32):
+            raise ValueError("data and b must be float64 or float32")
+        self.m = self.b.shape[0]
+        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+            raise ValueError("n and the length of b must be in 1 .. 2^31 - 1")
+        if ip.shape[0] != self.m + 1:
+            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
+        if ix.shape[0] != self.data.shape[0]:
+            raise ValueError("indices and data must have the same length")
+        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
+        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
+            raise ValueError(f"column indices must lie in [0, {self.n})")
+        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
+        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
+        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+
+    @property
+    def nnz(self):
+        return int(self.indices.shape[0])
+
+    @classmethod
+    def from_dense(cls, A, b):
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise ValueError("A must be m-by-n")
+        mask = A != 0
+        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
+        indices = np.nonzero(mask)[1].astype(np.int32)
+        return cls(indptr, indices, np.ascontiguousarray(A[mask]), b, A.shape[1])
+
+    @classmethod
+    def from_scipy(cls, M, b):
+        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        return cls(M.indptr, M.indices, M.data, b, M.shape[1])
+
+    def toarray(self):
+        A = np.zeros((self.m, self.n), self.data.dtype)
+        np.add.at(A, (self._rows, self.indices), self.data)
+        return A
+
+    def _residual(self, x):
+        return (np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.m) - self.b).astype(x.dtype, copy=False)
+
+    def __call__(self, x):
+        r = self._residual(x)
+        return x.dtype.type(0.5) * np.dot(r, r)
+
+    def gradient(self, dfx, x):
+        r = self._residual(x)
+        dfx[...] = np.bincount(self.indices, weights=self.data * r[self._rows], minlength=self.n)
+        return x.dtype.type(0.5) * np.dot(r, r)
+
+
 class Stencil5ptQuadratic(ProximableFunction):
     """f(x) = 0.5 x'A_h x - b'x on an nx-by-ny grid (row-major), A_h the 5-point Laplacian
     (4,-1,-1,-1,-1) with homogeneous Dirichlet halo — the structured `Quadratic` of BASELINE
@@ -529,7 +601,8 @@ def _vec(a, dtype, n, name):
     return v
 
 
-_LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, Stencil5ptQuadratic))
+_LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, SparseLeastSquares,
+                                      Stencil5ptQuadratic))
 _LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
@@ -663,6 +736,21 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
         d.f_sp_nnz = f.nnz
         d.f_b = ptr(_vec(f.q, dtype, n, "q"))
+    elif isinstance(f, SparseLeastSquares):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("SparseLeastSquares is not lowered in the slack (ALS) form")
+        if isinstance(c, DenseAffine):
+            raise UnsupportedOracle("SparseLeastSquares is not lowered beside a dense c (DenseAffine)")
+        if f.n != n:
+            raise ValueError(f"A must have {n} columns")
+        d.f_kind = L.BZ_F_SPARSE_LEAST_SQUARES
+        d.f_rows = f.m
+        d.f_sp_rowptr = ptr(f.indptr)
+        d.f_sp_col = ptr(f.indices)
+        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
+        d.f_sp_nnz = f.nnz
+        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "b")))
     elif isinstance(f, Stencil5ptQuadratic):
         d.f_kind = L.BZ_F_STENCIL5
         d.f_grid_nx, d.f_grid_ny = f.nx, f.ny
@@ -715,7 +803,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         # what the library refuses with this kind, refused here before any device call
         if slack:
             raise UnsupportedOracle("SparseAffine is not lowered in the slack (ALS) form")
-        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic)):
+        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares)):
             raise UnsupportedOracle(f"SparseAffine is lowered with an element-wise f (Zero, DiagQuadratic), not {type(f).__name__}")
         if isinstance(D, PairwiseSet):
             raise UnsupportedOracle("pairwise D sets need c = IdentityFunction")

@@ -152,6 +152,31 @@ def sparse_qp(n: int, m: int, seed: int = SEED, dtype=np.float64):
     return out
 
 
+def sparse_lasso(m: int, n: int, k: int = 5, dtype=np.float64, seed: int = SEED):
+    """A sparse Lasso: min 0.5||A x - b||^2 + lam ||x||_1 with A m-by-n in CSR, k entries per row at distinct random columns:
+    [0, n) is cut into k strata [j n div k, (j + 1) n div k), row i takes the column floor(u1 w_j) of stratum j, shifted by
+    the row's offset floor(u2 n) modulo n, and stores its k entries in the order of the keys u3 (the columns are unsorted).
+    a_ij = (2 u4 - 1) / sqrt(k).  A planted x* with max(1, n div 20) entries 1 + u6 of random sign (u7) at the columns of
+    the smallest keys u5; b = A x* + 0.01 (2 u8 - 1)."""
+    if not 1 <= k <= n or m < 1:
+        raise ValueError("sparse_lasso needs m >= 1 and 1 <= k <= n")
+    lo = (np.arange(k + 1, dtype=np.int64) * n) // k
+    width = np.diff(lo)
+    inside = np.floor(uniform(1, m * k, seed=seed).reshape(m, k) * width).astype(np.int64)
+    shift = np.floor(uniform(2, m, seed=seed) * n).astype(np.int64)
+    cols = (lo[:-1] + inside + shift[:, None]) % n
+    order = np.argsort(uniform(3, m * k, seed=seed).reshape(m, k), axis=1, kind="stable")
+    cols = np.take_along_axis(cols, order, axis=1)
+    data = ((2.0 * uniform(4, m * k, seed=seed) - 1.0) / np.sqrt(k)).astype(dtype)
+    nz = max(1, n // 20)
+    support = np.argsort(uniform(5, n, seed=seed), kind="stable")[:nz]
+    xstar = np.zeros(n)
+    xstar[support] = (1.0 + uniform(6, nz, seed=seed)) * np.where(uniform(7, nz, seed=seed) < 0.5, -1.0, 1.0)
+    b = (data.astype(np.float64).reshape(m, k) * xstar[cols]).sum(axis=1) + 0.01 * (2.0 * uniform(8, m, seed=seed) - 1.0)
+    return {"indptr": k * np.arange(m + 1, dtype=np.int64), "indices": cols.reshape(-1).astype(np.int32), "data": data,
+            "b": b.astype(dtype), "m": m, "n": n, "xstar": xstar.astype(dtype)}
+
+
 def portfolio(n: int, dtype=np.float64, rank: int | None = None):
     """A stand-in for the absent demo/portfolio_data (demo/portfolio.jl:70-91: Q, rho, mu, ub), from the uniform stream:
 

@@ -62,6 +62,14 @@ extern "C" {
                                     contract (not checked).  c Identity or SparseAffine, slack = 0, one rank, D Zero /
                                     Free / Box (and, with c = Identity, the pairwise sets); refused (BZ_ERR_UNSUPPORTED):
                                     slack = 1, c = DenseAffine, more than one rank, callbacks mixed in.               */
+#define BZ_F_SPARSE_LEAST_SQUARES 7 /* 0.5||A x - b||^2, A[f_rows][n] in CSR (f_sp_*), b[f_rows] in f_b: ProximalOperators.
+                                    LeastSquares (lambda = 1, as BZ_F_LEAST_SQUARES has it) with a sparse A, never densified
+                                    and never squared.  The conventions of c_sp_*: the column indices of a row need not be
+                                    sorted; an index that occurs twice in a row contributes twice; an empty row gives
+                                    r_i = -b_i, an empty column a zero gradient entry; nnz = 0 is accepted; n and f_rows
+                                    <= 2^31 - 1, nnz is 64-bit.  c Identity or SparseAffine, slack = 0, one rank, D Zero /
+                                    Free / Box (and, with c = Identity, the pairwise sets); refused (BZ_ERR_UNSUPPORTED):
+                                    slack = 1, c = DenseAffine, more than one rank, callbacks mixed in.               */
 /* g: proximable cost.  prox!(z,g,x,gamma)->g(z)                                     */
 #define BZ_G_ZERO            0   /* zero.jl:22-25, ProximalOperators.Zero / IndFree   */
 #define BZ_G_NORM_L1         1   /* ProximalOperators.NormL1(lambda) (test_verbose.jl:23) */
@@ -212,6 +220,7 @@ typedef struct {
     bz_c_jtprod_fn   cb_c_jtprod;
     bz_D_proj_fn     cb_D_proj;
     /* f, SPARSE_QUADRATIC (with q[n] in f_b): Q in CSR, copied (and validated: BZ_ERR_ARG) at bz_problem_create.
+       f, SPARSE_LEAST_SQUARES (with f_rows = m and b[m] in f_b): A in CSR with m rows (rowptr[m + 1], rowptr[m] = nnz).
        (These four sit in front of c_sp_*: the sparse constraint's fields stay the descriptor's last four.) */
     const int64_t* f_sp_rowptr;    /* rowptr[n + 1], rowptr[0] = 0, non-decreasing, rowptr[n] = nnz */
     const int32_t* f_sp_col;       /* col[nnz], 0-based, in [0, n)                    */

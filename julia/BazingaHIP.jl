@@ -36,6 +36,7 @@ Base.@kwdef mutable struct ProblemDesc
     cb_user::Ptr{Cvoid} = C_NULL; cb_f_gradient::Ptr{Cvoid} = C_NULL; cb_g_prox::Ptr{Cvoid} = C_NULL
     cb_c_eval::Ptr{Cvoid} = C_NULL; cb_c_jtprod::Ptr{Cvoid} = C_NULL; cb_D_proj::Ptr{Cvoid} = C_NULL
     # f = SparseQuadratic (BZ_F_SPARSE_QUADRATIC): symmetric Q in CSR, 0-based; q in f_b
+    # f = SparseLeastSquares (BZ_F_SPARSE_LEAST_SQUARES): A (f_rows x n) in CSR, 0-based; b in f_b
     f_sp_rowptr::Ptr{Cvoid} = C_NULL; f_sp_col::Ptr{Cvoid} = C_NULL; f_sp_val::Ptr{Cvoid} = C_NULL; f_sp_nnz::Int64 = 0
     # c = SparseAffine (BZ_C_SPARSE_AFFINE): A in CSR, 0-based
     c_sp_rowptr::Ptr{Cvoid} = C_NULL; c_sp_col::Ptr{Cvoid} = C_NULL; c_sp_val::Ptr{Cvoid} = C_NULL; c_sp_nnz::Int64 = 0
@@ -139,6 +140,23 @@ function Bazinga.gradient!(dfx, f::SparseQuadratic, x)
     return fx + sum(x .* f.q)
 end
 
+"""`SparseLeastSquares(A::SparseMatrixCSC, b)`: f(x) = 0.5||A x - b||^2 with a sparse A that is never densified and never
+squared into A'A (ProximalOperators.LeastSquares, lambda = 1, with a sparse A).  The library takes CSR: the CSC arrays of
+`sparse(A')` ARE the CSR arrays of A, made 0-based here."""
+struct SparseLeastSquares{T} <: Bazinga.ProximableFunction
+    A::SparseMatrixCSC{T,Int}; b::Vector{T}
+    rowptr::Vector{Int64}; col::Vector{Int32}; val::Vector{T}
+    function SparseLeastSquares(A::SparseMatrixCSC{T}, b::Vector{T}) where {T}
+        At = sparse(A')
+        new{T}(A, b, Int64.(At.colptr .- 1), Int32.(At.rowval .- 1), Vector{T}(At.nzval))
+    end
+end
+function Bazinga.gradient!(dfx, f::SparseLeastSquares, x)
+    r = f.A * x .- f.b
+    dfx .= f.A' * r
+    return sum(r .* r) / 2
+end
+
 "`LBFGS(M; compact = nothing)`: how the operator is evaluated (bz_panoc_opts.lbfgs_compact) — `false` the two-loop recursion in the reference's order, `true` the compact representation, `nothing` (default) compact where the one-pass kernel applies"
 struct LBFGS
     memory::Int; compact::Union{Nothing,Bool}
@@ -165,6 +183,9 @@ lower_f!(d, f::ProximalOperators.Quadratic) = (d.f_kind = 4; d.f_A = pointer(f.Q
                                                d.f_b = pointer(f.q); nothing)      # Q symmetric: layout-agnostic
 lower_f!(d, f::SparseQuadratic) = (d.f_kind = 6; d.f_sp_rowptr = pointer(f.rowptr); d.f_sp_col = pointer(f.col);
                                    d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val); d.f_b = pointer(f.q); nothing)
+lower_f!(d, f::SparseLeastSquares) = (d.f_kind = 7; d.f_rows = length(f.b); d.f_sp_rowptr = pointer(f.rowptr);
+                                      d.f_sp_col = pointer(f.col); d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val);
+                                      d.f_b = pointer(f.b); nothing)
 lower_f!(d, f) = :generic
 
 lower_g!(d, g::Bazinga.Zero) = (d.g_kind = 0)

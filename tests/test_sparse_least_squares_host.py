@@ -1,0 +1,177 @@
+"""f(x) = 0.5||A x - b||^2 with a sparse A in CSR (bz.SparseLeastSquares, BZ_F_SPARSE_LEAST_SQUARES), everything that needs no
+GPU: the class's validation and host mirrors, its lowering to the C descriptor, the generator bz.synth.sparse_lasso, and the
+launch plans that the case lists of tests/test_gpu_sparse_least_squares.py take."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+from bazinga_jl_amd.oracles import lower
+from tests.test_gpu_sparse import CASES32, CASES64, csr_of, plan, structured, transpose_ptr
+
+# fp32 shapes whose rows are cut on each side (tests/test_gpu_sparse_least_squares.py, real data)
+CUT32 = [(3, 1200, 0.9), (1200, 3, 0.9)]
+
+
+def small():
+    indptr, indices, data = np.array([0, 2, 3, 5]), np.array([0, 3, 1, 2, 3]), np.arange(1.0, 6.0)
+    return indptr, indices, data, np.array([1.0, -2.0, 3.0]), 4
+
+
+def test_validation_errors(bz):
+    indptr, indices, data, b, n = small()
+    f = bz.SparseLeastSquares(indptr, indices, data, b, n)
+    assert f.nnz == 5 and f.n == 4 and f.m == 3
+    with pytest.raises(ValueError, match="indptr"):
+        bz.SparseLeastSquares(np.array([0, 3, 2, 5]), indices, data, b, n)
+    with pytest.raises(ValueError, match="indptr"):
+        bz.SparseLeastSquares(np.array([1, 2, 3, 5]), indices, data, b, n)
+    with pytest.raises(ValueError, match="indptr"):
+        bz.SparseLeastSquares(np.array([0, 2, 3, 4]), indices, data, b, n)           # does not end at nnz
+    with pytest.raises(ValueError, match="indptr"):
+        bz.SparseLeastSquares(np.array([0, 2, 5]), indices, data, b, n)              # not m + 1 long
+    with pytest.raises(ValueError, match="column indices"):
+        bz.SparseLeastSquares(indptr, np.array([0, 3, 1, 4, 3]), data, b, n)
+    with pytest.raises(ValueError, match="column indices"):
+        bz.SparseLeastSquares(indptr, np.array([0, -1, 1, 2, 3]), data, b, n)
+    with pytest.raises(ValueError, match="same length"):
+        bz.SparseLeastSquares(indptr, indices, data[:4], b, n)
+    with pytest.raises(ValueError, match="integer"):
+        bz.SparseLeastSquares(indptr.astype(np.float64), indices, data, b, n)
+    with pytest.raises(ValueError, match="float64 or float32"):
+        bz.SparseLeastSquares(indptr, indices, data.astype(np.int64), b, n)
+    with pytest.raises(ValueError, match="2\\^31"):
+        bz.SparseLeastSquares(indptr, indices, data, b, 2 ** 31)
+    with pytest.raises(ValueError, match="2\\^31"):
+        bz.SparseLeastSquares(np.array([0]), indices[:0], data[:0], b[:0], n)        # no rows
+    # a duplicated index contributes twice; nnz = 0 is accepted
+    g = bz.SparseLeastSquares(np.array([0, 2, 3]), np.array([1, 1, 0]), np.array([2.0, 3.0, 5.0]), np.zeros(2), 2)
+    assert np.array_equal(g.toarray(), np.array([[0.0, 5.0], [5.0, 0.0]]))
+    e = bz.SparseLeastSquares(np.zeros(4, np.int64), np.zeros(0, np.int32), np.zeros(0), b, n)
+    dfx = np.ones(n)
+    assert e.gradient(dfx, np.ones(n)) == 0.5 * np.dot(b, b) and not np.any(dfx)
+
+
+def test_from_dense_round_trip(bz):
+    for m, n, p in CASES64[:5]:
+        A = structured(m, n, p, np.random.default_rng(m + n), False, np.float64)
+        f = bz.SparseLeastSquares.from_dense(A, np.zeros(m))
+        assert np.array_equal(f.toarray(), A) and f.nnz == np.count_nonzero(A) and (f.m, f.n) == (m, n)
+        assert f.indptr.dtype == np.int64 and f.indices.dtype == np.int32
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_host_gradient_equals_the_dense_one_on_integer_data(bz, ref, dtype):
+    """integer data (every product and sum exact): value and gradient equal ref.LeastSquares' on the densified matrix bit
+    for bit, unsorted rows and a duplicated entry included"""
+    rng = np.random.default_rng(11)
+    m, n = 41, 121
+    A = structured(m, n, 0.1, rng, True, dtype)
+    indptr, indices, data = csr_of(A, np.random.default_rng(1))
+    # duplicate the first entry of row 2: 2 a = a + a
+    k = indptr[2]
+    indices, data = np.insert(indices, k, indices[k]), np.insert(data, k, data[k])
+    indptr[3:] += 1
+    A[2, indices[k]] *= 2
+    b = rng.integers(-3, 4, m).astype(dtype)
+    f = bz.SparseLeastSquares(indptr, indices, data, b, n)
+    assert np.array_equal(f.toarray(), A)
+    o = ref.LeastSquares(A, b)
+    for _ in range(3):
+        x = rng.integers(-4, 5, n).astype(dtype)
+        ga, gb = np.empty(n, dtype), np.empty(n, dtype)
+        fa, fb = f.gradient(ga, x), o.gradient(gb, x)
+        assert ga.dtype == dtype and np.array_equal(ga, gb)
+        assert fa == fb == f(x) == o(x) and fb < 2.0 ** 22
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+def test_lower_fills_the_descriptor(bz, dtype):
+    L = bz._lib
+    indptr, indices, data, b, n = small()
+    m, ny = 3, 2
+    f = bz.SparseLeastSquares(indptr, indices, data.astype(dtype), b.astype(dtype), n)
+    A = np.zeros((ny, n), dtype)
+    A[0, :] = 1
+    A[1, 3] = 2
+    cs = bz.SparseAffine.from_dense(A, np.zeros(ny, dtype))
+    for c, rows in ((bz.IdentityFunction(), n), (cs, ny)):
+        desc, keep = lower(f, bz.NormL1(0.1), c, bz.ZeroSet(), n, rows, dtype)
+        assert desc.f_kind == L.BZ_F_SPARSE_LEAST_SQUARES == 7 and desc.f_sp_nnz == f.nnz == 5 and desc.f_rows == m
+        assert desc.c_kind == (L.BZ_C_SPARSE_AFFINE if c is cs else L.BZ_C_IDENTITY)
+        rp = np.ctypeslib.as_array(C.cast(desc.f_sp_rowptr, C.POINTER(C.c_int64)), shape=(m + 1,))
+        col = np.ctypeslib.as_array(C.cast(desc.f_sp_col, C.POINTER(C.c_int32)), shape=(f.nnz,))
+        ct = C.c_double if dtype == np.float64 else C.c_float
+        val = np.ctypeslib.as_array(C.cast(desc.f_sp_val, C.POINTER(ct)), shape=(f.nnz,))
+        bb = np.ctypeslib.as_array(C.cast(desc.f_b, C.POINTER(ct)), shape=(m,))
+        assert np.array_equal(rp, f.indptr) and np.array_equal(col, f.indices) and np.array_equal(val, f.data)
+        assert np.array_equal(bb, b) and not desc.f_A and not desc.f_q
+    # a float64 object lowered to a float32 problem: the values are converted
+    f64 = bz.SparseLeastSquares(indptr, indices, data, b, n)
+    desc, keep = lower(f64, bz.NormL1(0.1), bz.IdentityFunction(), bz.ZeroSet(), n, n, np.float32)
+    val = np.ctypeslib.as_array(C.cast(desc.f_sp_val, C.POINTER(C.c_float)), shape=(5,))
+    assert np.array_equal(val, data.astype(np.float32))
+
+
+def test_lower_refuses_before_any_device_call(bz):
+    indptr, indices, data, b, n = small()
+    f = bz.SparseLeastSquares(indptr, indices, data, b, n)
+    A = np.ones((2, n))
+    with pytest.raises(bz.UnsupportedOracle, match="SparseLeastSquares.*slack"):
+        lower(f, bz.NormL1(0.1), bz.IdentityFunction(), bz.ZeroSet(), n, n, np.float64, slack=True)
+    with pytest.raises(bz.UnsupportedOracle, match="SparseLeastSquares.*DenseAffine"):
+        lower(f, bz.NormL1(0.1), bz.DenseAffine(A, np.zeros(2)), bz.ZeroSet(), n, 2, np.float64)
+    with pytest.raises(bz.UnsupportedOracle, match="pairwise"):
+        cs = bz.SparseAffine.from_dense(A, np.zeros(2))
+        lower(f, bz.NormL1(0.1), cs, bz.XorPairs(), n, 2, np.float64)
+    with pytest.raises(ValueError, match="columns"):
+        lower(f, bz.NormL1(0.1), bz.IdentityFunction(), bz.ZeroSet(), n + 1, n + 1, np.float64)
+    # the same through bz.Problem, which lowers before it opens a context
+    with pytest.raises(bz.UnsupportedOracle):
+        bz.Problem(f, bz.NormL1(1.0), bz.IdentityFunction(), bz.ZeroSet(), n, n, np.float64, slack=True)
+    with pytest.raises(bz.UnsupportedOracle):
+        bz.Problem(f, bz.NormL1(1.0), bz.DenseAffine(A, np.zeros(2)), bz.ZeroSet(), n, 2, np.float64)
+    # a g that is not lowered sends the same object through the callback kinds
+    class MyL1:
+        def prox(self, z, x, gamma):
+            z[...] = x
+            return 0.0
+    desc, keep = lower(f, MyL1(), bz.IdentityFunction(), bz.ZeroSet(), n, n, np.float64)
+    assert desc.f_kind == bz._lib.BZ_F_CALLBACK
+
+
+def test_sparse_lasso_is_reproducible(bz):
+    m, n, k = 60, 128, 5
+    a, b = bz.synth.sparse_lasso(m, n, k), bz.synth.sparse_lasso(m, n, k)
+    assert all(np.array_equal(a[key], b[key]) for key in a)
+    assert not np.array_equal(a["data"], bz.synth.sparse_lasso(m, n, k, seed=7)["data"])
+    cols = a["indices"].reshape(m, k)
+    assert np.array_equal(a["indptr"], k * np.arange(m + 1)) and a["indptr"].dtype == np.int64 and a["indices"].dtype == np.int32
+    assert all(len(set(r)) == k for r in cols) and cols.min() >= 0 and cols.max() < n
+    assert np.any(np.diff(cols, axis=1) < 0)                                         # unsorted columns
+    assert np.count_nonzero(a["xstar"]) == n // 20
+    f = bz.SparseLeastSquares(a["indptr"], a["indices"], a["data"], a["b"], n)
+    assert np.max(np.abs(f.toarray() @ a["xstar"] - a["b"])) <= 0.01                 # b = A x* + small noise
+    c = bz.synth.sparse_lasso(m, n, k, np.float32)
+    assert c["data"].dtype == c["b"].dtype == np.float32 and np.array_equal(c["indices"], a["indices"])
+    with pytest.raises(ValueError):
+        bz.synth.sparse_lasso(4, 3, 5)
+
+
+def test_case_lists_take_every_lane_count_and_cut_rows_on_both_matrices():
+    """the (m, n, density) lists of tests/test_gpu_sparse.py as A_f: L = 1 .. 64 on A_f and on A_f'; in fp64 cut rows on each
+    side; the two extra fp32 shapes are cut on each side"""
+    for cases in (CASES64, CASES32):
+        la, lt, cut_a, cut_t = set(), set(), False, False
+        for m, n, p in cases:
+            A = structured(m, n, p, np.random.default_rng(m * 7 + n), True, np.float64)
+            indptr, indices, data = csr_of(A, np.random.default_rng(1))
+            a, t = plan(indptr, data.shape[0]), plan(transpose_ptr(indices, n), data.shape[0])
+            la.add(a[0]); lt.add(t[0]); cut_a, cut_t = cut_a or a[2], cut_t or t[2]
+        assert la == lt == {1, 2, 4, 8, 16, 32, 64}, (la, lt)
+        assert (cut_a and cut_t) or cases is CASES32
+    for (m, n, p), side in zip(CUT32, (0, 1)):
+        A = structured(m, n, p, np.random.default_rng(m * 11 + n), False, np.float32)
+        indptr, indices, data = csr_of(A, np.random.default_rng(2))
+        cuts = (plan(indptr, data.shape[0])[2], plan(transpose_ptr(indices, n), data.shape[0])[2])
+        assert cuts[side] and not cuts[1 - side]
