@@ -23,6 +23,7 @@ BZ_D_VC_PAIRS, BZ_D_CC_PAIRS, BZ_D_EITHEROR_PAIRS, BZ_D_XOR_PAIRS = 3, 4, 5, 6
 BZ_F_CALLBACK, BZ_G_CALLBACK, BZ_C_CALLBACK, BZ_D_CALLBACK = 5, 8, 2, 7
 BZ_F_SPARSE_QUADRATIC = 6
 BZ_F_SPARSE_LEAST_SQUARES = 7
+BZ_F_SPARSE_LOGISTIC = 8
 # host-callback oracle protocol (include/bazinga_hip.h)
 F_GRADIENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 G_PROX_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64)

@@ -138,7 +138,7 @@ struct CreateKnobs {
     std::optional<int> dense_kp = env_opt("BZ_DENSE_KP");                // k_dense_fused's packs per row and lane
     std::optional<int> spmv_l = env_opt("BZ_SPMV_L");    // lanes per row of the CSR row kernels (a power of two <= 64)
     int spq_fused = env_int("BZ_SPQ_FUSED", 1);          // 0: the sparse quadratic f with c = Identity as product + k_algrad_elem
-    int spls_fused = env_int("BZ_SPLS_FUSED", 1);        // 0: the sparse least squares f with c = Identity as two products + k_algrad_elem
+    int spls_fused = env_int("BZ_SPLS_FUSED", 1);        // 0: the sparse least squares (or logistic) f with c = Identity as two products + k_algrad_elem
     // test-only
     int test_dense_timeout = env_int("BZ_TEST_DENSE_TIMEOUT", 0);        // the k-th k_dense_fused exchange is sabotaged
     unsigned dense_spin = (unsigned)env_ll("BZ_DENSE_SPIN", 0);          // k_dense_fused's poll bound (0: the default)
@@ -212,6 +212,21 @@ template <class T> class Solver final : public SolverBase {
                 throw Error(BZ_ERR_ARG, "SparseLeastSquares needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and b[m]");
             if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
                 throw Error(BZ_ERR_ARG, "SparseLeastSquares: n and m must fit 32-bit indices");
+        }
+        sparse_logit = d.f_kind == BZ_F_SPARSE_LOGISTIC;
+        if (sparse_logit) {
+            // (from here on the logistic f is a `sparse_ls` problem whose first launch has another epilogue)
+            sparse_ls = true;
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: the slack (ALS) form is not lowered with a sparse logistic f");
+            if (d.c_kind == BZ_C_DENSE_AFFINE)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: a sparse logistic f beside a dense c (DenseAffine) is not lowered");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: the sparse logistic f is not sharded (one rank)");
+            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: the sparse logistic f does not mix with host callbacks");
+            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
+                throw Error(BZ_ERR_ARG, "SparseLogistic needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and the labels b[m]");
+            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
+                throw Error(BZ_ERR_ARG, "SparseLogistic: n and m must fit 32-bit indices");
         }
         if (d.c_kind == BZ_C_SPARSE_AFFINE) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: the slack (ALS) form is not lowered with a sparse c");
@@ -356,13 +371,14 @@ template <class T> class Solver final : public SolverBase {
             FR_.alloc(nx);
         }
         if (sparse_ls) {
-            // (the generic kernel chain too; the value convention of the dense LeastSquares: sum r^2, halved by fscale)
+            // (the generic kernel chain too; the value convention of the dense LeastSquares: sum r^2, halved by fscale ;
+            // the logistic f: the plain sum of the rows' losses)
             frows = d.f_rows;
             sparse_ls_create(d);
             upload(fb_, d.f_b, frows);
             FR_.alloc(frows);
             if (d.c_kind == BZ_C_SPARSE_AFFINE || !spls_fused_on()) DFX_.alloc(nx);
-            fscale = T(0.5);
+            fscale = sparse_logit ? T(1) : T(0.5);
         }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             A_.alloc((size_t)ny * nx);
@@ -1800,7 +1816,7 @@ template <class T> class Solver final : public SolverBase {
     };
     SpCsr spA_, spAt_, spQ_;               // (Q: the sparse quadratic f; symmetric, so no transpose)
     DBuf<int64_t> spQ_rowptr_;             // a cut Q: the row pointers as given (k_spmv_q_algrad walks rows, not virtual rows)
-    std::string sp_form_[4];               // by the epilogue's MODE (MODE 4 .. 6: spls_form_)
+    std::string sp_form_[4];               // by the epilogue's MODE (MODE 4 .. 6: spls_form_ ; MODE 7: splogit_form_)
     template <class V> static void sp_upload(DBuf<V>& dst, const std::vector<V>& src) {
         dst.alloc(src.size());
         if (!src.empty()) BZ_HIP(hipMemcpy(dst.p, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
@@ -1893,16 +1909,18 @@ template <class T> class Solver final : public SolverBase {
         sp_form_[2] = sp_form("k_spmv_q_algrad", spQ_);
         sp_form_[3] = sp_form("k_spmv_q", spQ_);
     }
-    // f = SparseLeastSquares: A_f validated on a host copy; A_f and A_f' in HBM with the segment and lane rules of A and A'
+    // f = SparseLeastSquares or SparseLogistic: A_f validated on a host copy; A_f and A_f' in HBM with the segment and lane
+    // rules of A and A'
     void sparse_ls_create(const bz_problem_desc& d) {
         std::vector<int64_t> rp, tp; std::vector<int32_t> col, tcol; std::vector<T> val, tval;
-        sp_read("SparseLeastSquares", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
+        sp_read(sparse_logit ? "SparseLogistic" : "SparseLeastSquares", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
         csr_transpose(frows, nx, rp, col, val, tp, tcol, tval);
         sp_build(spF_, frows, nx, rp, col, val);
         sp_build(spFt_, nx, frows, tp, tcol, tval);
         spls_form_[0] = sp_form("k_spmv_ls_r", spF_);
         spls_form_[1] = sp_form("k_spmv_ls_t_algrad", spFt_);
         spls_form_[2] = sp_form("k_spmv_ls_t", spFt_);
+        if (sparse_logit) splogit_form_ = sp_form("k_spmv_logit_r", spF_);
     }
     // c = SparseAffine: validate the caller's CSR on a host copy, build A' (csr_transpose: a column's entries stay in ascending row
     // order) and put both in HBM
@@ -1931,7 +1949,7 @@ template <class T> class Solver final : public SolverBase {
         });
     }
     // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A', 3: k_spmv_q over Q, 4: k_spmv_ls_r
-    // over A_f, 5: k_spmv_ls_t_algrad and 6: k_spmv_ls_t over A_f') and, for a cut matrix, the fold of its cut rows; returns
+    // over A_f, 5: k_spmv_ls_t_algrad and 6: k_spmv_ls_t over A_f', 7: k_spmv_logit_r over A_f) and, for a cut matrix, the fold of its cut rows; returns
     // the number of block partials left in `slot`
     template <int MODE> int sp_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
         const double bytes = m.bytes() + vec_bytes;
@@ -1944,13 +1962,14 @@ template <class T> class Solver final : public SolverBase {
             const int64_t rpb = BLOCK / L;
             g = (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - gfold, (m.nv + rpb - 1) / rpb));
             pending_bytes_ += bytes;
-            nm((MODE < 4 ? sp_form_[MODE & 3] : spls_form_[MODE >= 4 ? MODE - 4 : 0]).c_str());
+            nm((MODE < 4 ? sp_form_[MODE & 3] : MODE == 7 ? splogit_form_ : spls_form_[MODE >= 4 && MODE < 7 ? MODE - 4 : 0]).c_str());
             if constexpr (MODE == 0) launch(C_GEMV, k_spmv_yupd<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 1) launch(C_GEMV, k_spmv_t_finish<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 3) launch(C_GEMV, k_spmv_q<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 4) launch(C_GEMV, k_spmv_ls_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 5) launch(C_GEMV, k_spmv_ls_t_algrad<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else launch(C_GEMV, k_spmv_ls_t<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else if constexpr (MODE == 6) launch(C_GEMV, k_spmv_ls_t<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else launch(C_GEMV, k_spmv_logit_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
         };
         sp_with_lanes(m.L, nt, go);
         if (gfold) {
@@ -1967,8 +1986,8 @@ template <class T> class Solver final : public SolverBase {
         return sp_pass<0>(spA_, x, E, slot, vecs);
     }
     // rows of A': grad = grad f(x) + A'yhat and the f partials -> slot
-    // (the sparse quadratic f: its terms from FR_ = Q x, which spq_product has left there ; the sparse least squares f: its
-    // gradient from DFX_ = A_f' r, which spls_product has left there, and no f term)
+    // (the sparse quadratic f: its terms from FR_ = Q x, which spq_product has left there ; the sparse least squares or
+    // logistic f: its gradient from DFX_ = A_f' r, which spls_product has left there, and no f term)
     int spmv_t_finish(const T* x, T* grad, int slot) {
         SpEpi<T> E{nullptr, nullptr, grad, x, P, sparse_f ? (const T*)FR_.p : sparse_ls ? (const T*)DFX_.p : (const T*)nullptr};
         const double vecs = ((grad ? 1 : 0) + (P.f_kind == BZ_F_DIAG_QUADRATIC || sparse_f ? 3 : 0) + (sparse_ls ? 1 : 0)) * (double)n * sizeof(T);
@@ -2001,10 +2020,12 @@ template <class T> class Solver final : public SolverBase {
     // (pairwise D: the projection of element i needs its partner, which a row's first lane does not have)
     bool spq_fused_on() const { return cenv_.spq_fused && !(desc.D_kind >= BZ_D_VC_PAIRS && desc.D_kind <= BZ_D_XOR_PAIRS); }
 
-    // ---- f = SparseLeastSquares
+    // ---- f = SparseLeastSquares / SparseLogistic
     // rows of A_f: r = A_f x - b -> r_out (null: not kept) and the partials of sum r^2 -> slot.  Per row: b (and r).
+    // The logistic f: r_i = -b_i sigma(-b_i a_i'x) and the partials of the rows' losses, the same streams.
     int spls_residual(const T* x, T* r_out, int slot) {
         SpEpi<T> E{fb_.p, nullptr, r_out, nullptr, P, nullptr};
+        if (sparse_logit) return sp_pass<7>(spF_, x, E, slot, (1 + (r_out ? 1 : 0)) * (double)frows * sizeof(T));
         return sp_pass<4>(spF_, x, E, slot, (1 + (r_out ? 1 : 0)) * (double)frows * sizeof(T));
     }
     // rows of A_f', c = Identity: grad = A_f' r + yhat (r in FR_) and the penalty partials -> slot.  Per row: x, mu and mu*y
@@ -3474,6 +3495,9 @@ template <class T> class Solver final : public SolverBase {
     bool sparse_ls = false;
     SpCsr spF_, spFt_;                     // A_f (m x n) and A_f' (n x m)
     std::string spls_form_[3];             // by the epilogue's MODE - 4
+    // ---- f = SparseLogistic: a sparse_ls problem (both flags set) whose rows of A_f run k_spmv_logit_r
+    bool sparse_logit = false;
+    std::string splogit_form_;
 };
 
 // one-pass kernel of an oracle family: the instantiations live in bz_families_dk*.hip (one file per D class, so that

@@ -1,6 +1,7 @@
 // bz_spmv.h — the CSR row kernels: the sparse affine constraint c(x) = A x - b (BZ_C_SPARSE_AFFINE), the two passes of its AL
 // gradient, the sparse quadratic f(x) = 0.5 x'Qx + q'x (BZ_F_SPARSE_QUADRATIC), the pass over Q, and the sparse least squares
-// f(x) = 0.5 ||A_f x - b||^2 (BZ_F_SPARSE_LEAST_SQUARES), the passes over A_f and A_f'.
+// f(x) = 0.5 ||A_f x - b||^2 (BZ_F_SPARSE_LEAST_SQUARES), the passes over A_f and A_f', and the sparse logistic
+// f(x) = sum_i log(1 + exp(-b_i a_i'x)) (BZ_F_SPARSE_LOGISTIC), the same two passes with another epilogue on the rows of A_f.
 //
 // A and A' are two CSR matrices in HBM (A' is built once, at bz_problem_create, by a stable counting sort).  Both passes
 // are the same row kernel: L lanes (compile time, 1..64, chosen at creation from the mean row length) walk one row, lane
@@ -17,6 +18,8 @@
 //   k_spmv_ls_t_algrad  rows of A_f', c = Identity:  (A_f' r)_j = grad f_j, and on that value what k_algrad_elem does in its
 //                       mode 1 — with k_spmv_ls_r the whole AL gradient in two launches; grad f never goes to HBM
 //   k_spmv_ls_t         rows of A_f':  A_f' r -> DFX for the forms that finish element-wise or in k_spmv_t_finish
+//   k_spmv_logit_r      rows of A_f, the logistic f:  r_i = -b_i sigma(-b_i a_i'x) -> R (if kept) and the terms
+//                       softplus(-b_i a_i'x); the two kernels over A_f' then run on that r as they do on a residual
 // Rows longer than S entries (S fixed at creation from the matrix alone) are cut into segments that run as rows of
 // their own ("virtual rows": the row pointers refined at the cuts); a segment leaves its sum in a side buffer and
 // k_spmv_fold, one wave per cut row, adds a row's segment sums in a fixed order and runs the row's epilogue.
@@ -42,20 +45,26 @@ template <class T> struct SpMat {
 // the penalty term; MODE 1 (rows of A'): the gradient and the f term; MODE 2 (rows of Q, c = Identity): the gradient, the
 // f term and the penalty term; MODE 3 (rows of Q): Q x (if kept) and the f term (if x is given); MODE 4 (rows of A_f): the
 // residual (if kept) and its square; MODE 5 (rows of A_f', c = Identity): the gradient and the penalty term; MODE 6 (rows
-// of A_f'): the product alone.
+// of A_f'): the product alone; MODE 7 (rows of A_f, logistic): the derivative of the row's loss (if kept) and the loss.
 template <class T> struct SpEpi {
-    const T* b;              // MODE 0: b[ny] ; MODE 4: b[m] of f
+    const T* b;              // MODE 0: b[ny] ; MODE 4: b[m] of f ; MODE 7: the labels b[m] of f
     T* cx;                   // MODE 0: c(x) for the caller that keeps it, or null
     T* out;                  // MODE 0: yupd[ny] or null ; MODE 1, 2, 5: grad[n] or null ; MODE 3: (Q x)[n] or null ;
-                             // MODE 4: r[m] or null ; MODE 6: (A_f' r)[n]
+                             // MODE 4, 7: r[m] or null ; MODE 6: (A_f' r)[n]
     const T* x;              // MODE 1, 2, 5: x[n] ; MODE 3: x[n], or null for the product alone
     ElemParams<T> P;
     const T* ext;            // MODE 1 with the sparse quadratic f: (Q x)[n], left by k_spmv_q ; with the sparse least
-                             // squares f: (A_f' r)[n], left by k_spmv_ls_t
+                             // squares or logistic f: (A_f' r)[n], left by k_spmv_ls_t
 };
 
-// scalars a mode leaves per row: MODE 2 the f term and the penalty term, the others one
+// scalars a mode leaves per row: MODE 2 the f term and the penalty term, the others (MODE 7: the loss) one
 template <int MODE> constexpr int sp_nacc() { return MODE == 2 ? 2 : 1; }
+
+// exp and log1p in T: an fp32 problem takes the fp32 functions
+__device__ __forceinline__ float sp_exp(float v) { return expf(v); }
+__device__ __forceinline__ double sp_exp(double v) { return exp(v); }
+__device__ __forceinline__ float sp_log1p(float v) { return log1pf(v); }
+__device__ __forceinline__ double sp_log1p(double v) { return log1p(v); }
 
 // (called by the row's first lane alone: the per-row parameters are loaded once per row)
 template <class T, int MODE>
@@ -89,8 +98,8 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
             const T xv = E.x[r], e = E.ext[r], qv = P.b[r];
             dfx = e + qv;
             fterm = xv * (T(0.5) * e + qv);
-        } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES) {
-            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r)
+        } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES || P.f_kind == BZ_F_SPARSE_LOGISTIC) {
+            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r / k_spmv_logit_r)
         }
         if (E.out) E.out[r] = dfx + (T)d;
         acc[0] += (double)fterm;
@@ -127,6 +136,17 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
         const ALOut<T> o = al_elem(BZ_F_ZERO, P.D_kind, xv, T(0), T(0), mu, muy, lo, hi);
         if (E.out) E.out[r] = e + o.grad;
         acc[0] += (double)o.pterm;
+    } else if constexpr (MODE == 7) {
+        // u = b_i a_i'x ; loss = softplus(-u), r_i = -b_i sigma(-u), both from e = exp(-|u|) in [0, 1]: nothing overflows and
+        // nothing cancels.  Ordered compares and arithmetic alone (no fmax / fmin, which drop a NaN): a NaN in u makes every
+        // compare false, e NaN, and reaches the loss and r_i.
+        const T bv = E.b[r];
+        const T u = bv * (T)d;
+        const T e = sp_exp(u < T(0) ? u : -u);
+        const T loss = (u < T(0) ? -u : T(0)) + sp_log1p(e);
+        const T s = u >= T(0) ? e / (T(1) + e) : T(1) / (T(1) + e);
+        if (E.out) E.out[r] = -bv * s;
+        acc[0] += (double)loss;
     } else {
         if (E.out) E.out[r] = (T)d;
     }
@@ -307,6 +327,15 @@ __global__ void __launch_bounds__(BLOCK)
 k_spmv_ls_r(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
     spmv_rows<T, L, NT, 4>(M, x, E, acc);
+    block_reduce_store<1>(acc, 0u, parts, slot0);
+}
+
+// rows of A_f, the logistic f: r_i = -b_i sigma(-b_i a_i'x) -> E.out (if kept) ; partials: slot0 the terms softplus(-b_i a_i'x)
+template <class T, int L, bool NT>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_logit_r(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, 7>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 

@@ -267,6 +267,93 @@ class SparseLeastSquares(ProximableFunction):
         return x.dtype.type(0.5) * np.dot(r, r)
 
 
+class SparseLogistic(ProximableFunction):
+    """The logistic loss of a sparse design matrix: f(x) = sum_i log(1 + exp(-b_i a_i'x)), A m-by-n in CSR (indptr[m + 1],
+    indices[nnz] 0-based, data[nnz]), labels b in {-1, +1}^m, never densified.  The plain sum: no 1/2 and no 1/m.  The matrix
+    conventions of SparseLeastSquares (unsorted and repeated column indices, empty rows and columns, nnz = 0).  With
+    u = b_i a_i'x the row's loss is softplus(-u) = max(-u, 0) + log1p(exp(-|u|)) and the gradient is A'r with
+    r_i = -b_i sigma(-u), sigma(-u) = e / (1 + e) for u >= 0 and 1 / (1 + e) otherwise, e = exp(-|u|): nothing overflows,
+    nothing cancels, and a NaN in u reaches both.  __call__ / gradient below are numpy with these formulas in the dtype of x
+    (the generic-oracle protocol); on the device the kind is BZ_F_SPARSE_LOGISTIC."""
+
+    def __init__(self, indptr, indices, data, labels, n):
+        ip, ix = np.asarray(indptr), np.asarray(indices)
+        self.data = np.ascontiguousarray(data)
+        lab = np.asarray(labels)
+        self.n = int(n)
+        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or lab.ndim != 1:
+            raise ValueError("indptr, indices, data and labels must be one-dimensional")
+        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr and indices must be integer arrays")
+        if self.data.dtype not in (np.float64, np.float32):
+            raise ValueError("data must be float64 or float32")
+        if not (np.issubdtype(lab.dtype, np.integer) or lab.dtype in (np.float64, np.float32)):
+            raise ValueError("labels must be float64, float32 or integers")
+        if not np.all(np.abs(lab) == 1):
+            raise ValueError("labels must be -1 or +1")
+        self.b = np.ascontiguousarray(lab, dtype=self.data.dtype if np.issubdtype(lab.dtype, np.integer) else lab.dtype)
+        self.m = self.b.shape[0]
+        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+            raise ValueError("n and the number of labels must be in 1 .. 2^31 - 1")
+        if ip.shape[0] != self.m + 1:
+            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
+        if ix.shape[0] != self.data.shape[0]:
+            raise ValueError("indices and data must have the same length")
+        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
+        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
+            raise ValueError(f"column indices must lie in [0, {self.n})")
+        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
+        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
+        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+
+    @property
+    def nnz(self):
+        return int(self.indices.shape[0])
+
+    @classmethod
+    def from_dense(cls, A, labels):
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise ValueError("A must be m-by-n")
+        mask = A != 0
+        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
+        indices = np.nonzero(mask)[1].astype(np.int32)
+        return cls(indptr, indices, np.ascontiguousarray(A[mask]), labels, A.shape[1])
+
+    @classmethod
+    def from_scipy(cls, M, labels):
+        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        return cls(M.indptr, M.indices, M.data, labels, M.shape[1])
+
+    def toarray(self):
+        A = np.zeros((self.m, self.n), self.data.dtype)
+        np.add.at(A, (self._rows, self.indices), self.data)
+        return A
+
+    def _loss_r(self, x):
+        """the rows' losses softplus(-u) and r = -b sigma(-u), u = b * (A x), in the dtype of x"""
+        dt = x.dtype.type
+        t = np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.m).astype(x.dtype, copy=False)
+        b = self.b.astype(x.dtype, copy=False)
+        u = b * t
+        with np.errstate(over="ignore", invalid="ignore"):
+            e = np.exp(-np.abs(u))
+            loss = np.where(u < 0, -u, dt(0)) + np.log1p(e)
+            s = np.where(u >= 0, e / (dt(1) + e), dt(1) / (dt(1) + e))
+        return loss, -b * s
+
+    def __call__(self, x):
+        return x.dtype.type(np.sum(self._loss_r(x)[0]))
+
+    def gradient(self, dfx, x):
+        loss, r = self._loss_r(x)
+        dfx[...] = np.bincount(self.indices, weights=self.data * r[self._rows], minlength=self.n)
+        return x.dtype.type(np.sum(loss))
+
+
 class Stencil5ptQuadratic(ProximableFunction):
     """f(x) = 0.5 x'A_h x - b'x on an nx-by-ny grid (row-major), A_h the 5-point Laplacian
     (4,-1,-1,-1,-1) with homogeneous Dirichlet halo — the structured `Quadratic` of BASELINE
@@ -602,7 +689,7 @@ def _vec(a, dtype, n, name):
 
 
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, SparseLeastSquares,
-                                      Stencil5ptQuadratic))
+                                      SparseLogistic, Stencil5ptQuadratic))
 _LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
@@ -751,6 +838,21 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
         d.f_sp_nnz = f.nnz
         d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "b")))
+    elif isinstance(f, SparseLogistic):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("SparseLogistic is not lowered in the slack (ALS) form")
+        if isinstance(c, DenseAffine):
+            raise UnsupportedOracle("SparseLogistic is not lowered beside a dense c (DenseAffine)")
+        if f.n != n:
+            raise ValueError(f"A must have {n} columns")
+        d.f_kind = L.BZ_F_SPARSE_LOGISTIC
+        d.f_rows = f.m
+        d.f_sp_rowptr = ptr(f.indptr)
+        d.f_sp_col = ptr(f.indices)
+        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
+        d.f_sp_nnz = f.nnz
+        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "labels")))
     elif isinstance(f, Stencil5ptQuadratic):
         d.f_kind = L.BZ_F_STENCIL5
         d.f_grid_nx, d.f_grid_ny = f.nx, f.ny
@@ -803,7 +905,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         # what the library refuses with this kind, refused here before any device call
         if slack:
             raise UnsupportedOracle("SparseAffine is not lowered in the slack (ALS) form")
-        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares)):
+        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares, SparseLogistic)):
             raise UnsupportedOracle(f"SparseAffine is lowered with an element-wise f (Zero, DiagQuadratic), not {type(f).__name__}")
         if isinstance(D, PairwiseSet):
             raise UnsupportedOracle("pairwise D sets need c = IdentityFunction")

@@ -152,14 +152,8 @@ def sparse_qp(n: int, m: int, seed: int = SEED, dtype=np.float64):
     return out
 
 
-def sparse_lasso(m: int, n: int, k: int = 5, dtype=np.float64, seed: int = SEED):
-    """A sparse Lasso: min 0.5||A x - b||^2 + lam ||x||_1 with A m-by-n in CSR, k entries per row at distinct random columns:
-    [0, n) is cut into k strata [j n div k, (j + 1) n div k), row i takes the column floor(u1 w_j) of stratum j, shifted by
-    the row's offset floor(u2 n) modulo n, and stores its k entries in the order of the keys u3 (the columns are unsorted).
-    a_ij = (2 u4 - 1) / sqrt(k).  A planted x* with max(1, n div 20) entries 1 + u6 of random sign (u7) at the columns of
-    the smallest keys u5; b = A x* + 0.01 (2 u8 - 1)."""
-    if not 1 <= k <= n or m < 1:
-        raise ValueError("sparse_lasso needs m >= 1 and 1 <= k <= n")
+def _sparse_rows(m: int, n: int, k: int, dtype, seed: int):
+    """the matrix and the planted x* that sparse_lasso describes: (cols[m][k], data[m k], x* in float64, A x* in float64)"""
     lo = (np.arange(k + 1, dtype=np.int64) * n) // k
     width = np.diff(lo)
     inside = np.floor(uniform(1, m * k, seed=seed).reshape(m, k) * width).astype(np.int64)
@@ -172,9 +166,33 @@ def sparse_lasso(m: int, n: int, k: int = 5, dtype=np.float64, seed: int = SEED)
     support = np.argsort(uniform(5, n, seed=seed), kind="stable")[:nz]
     xstar = np.zeros(n)
     xstar[support] = (1.0 + uniform(6, nz, seed=seed)) * np.where(uniform(7, nz, seed=seed) < 0.5, -1.0, 1.0)
-    b = (data.astype(np.float64).reshape(m, k) * xstar[cols]).sum(axis=1) + 0.01 * (2.0 * uniform(8, m, seed=seed) - 1.0)
+    return cols, data, xstar, (data.astype(np.float64).reshape(m, k) * xstar[cols]).sum(axis=1)
+
+
+def sparse_lasso(m: int, n: int, k: int = 5, dtype=np.float64, seed: int = SEED):
+    """A sparse Lasso: min 0.5||A x - b||^2 + lam ||x||_1 with A m-by-n in CSR, k entries per row at distinct random columns:
+    [0, n) is cut into k strata [j n div k, (j + 1) n div k), row i takes the column floor(u1 w_j) of stratum j, shifted by
+    the row's offset floor(u2 n) modulo n, and stores its k entries in the order of the keys u3 (the columns are unsorted).
+    a_ij = (2 u4 - 1) / sqrt(k).  A planted x* with max(1, n div 20) entries 1 + u6 of random sign (u7) at the columns of
+    the smallest keys u5; b = A x* + 0.01 (2 u8 - 1)."""
+    if not 1 <= k <= n or m < 1:
+        raise ValueError("sparse_lasso needs m >= 1 and 1 <= k <= n")
+    cols, data, xstar, Axstar = _sparse_rows(m, n, k, dtype, seed)
+    b = Axstar + 0.01 * (2.0 * uniform(8, m, seed=seed) - 1.0)
     return {"indptr": k * np.arange(m + 1, dtype=np.int64), "indices": cols.reshape(-1).astype(np.int32), "data": data,
             "b": b.astype(dtype), "m": m, "n": n, "xstar": xstar.astype(dtype)}
+
+
+def sparse_logistic(m: int, n: int, k: int = 5, dtype=np.float64, seed: int = SEED):
+    """Sparse logistic regression: min sum_i log(1 + exp(-b_i a_i'x)) + lam ||x||_1 with the matrix and the planted x* of
+    sparse_lasso(m, n, k, dtype, seed) and the labels b_i = +1 if (A x*)_i + 0.1 (2 u9 - 1) >= 0 else -1 (a tenth of the
+    margins' scale in noise: a few labels near the boundary are flipped, so the classes are not separable by x*)."""
+    if not 1 <= k <= n or m < 1:
+        raise ValueError("sparse_logistic needs m >= 1 and 1 <= k <= n")
+    cols, data, xstar, Axstar = _sparse_rows(m, n, k, dtype, seed)
+    labels = np.where(Axstar + 0.1 * (2.0 * uniform(9, m, seed=seed) - 1.0) >= 0, 1.0, -1.0)
+    return {"indptr": k * np.arange(m + 1, dtype=np.int64), "indices": cols.reshape(-1).astype(np.int32), "data": data,
+            "labels": labels.astype(dtype), "m": m, "n": n, "xstar": xstar.astype(dtype)}
 
 
 def portfolio(n: int, dtype=np.float64, rank: int | None = None):

@@ -70,6 +70,15 @@ extern "C" {
                                     <= 2^31 - 1, nnz is 64-bit.  c Identity or SparseAffine, slack = 0, one rank, D Zero /
                                     Free / Box (and, with c = Identity, the pairwise sets); refused (BZ_ERR_UNSUPPORTED):
                                     slack = 1, c = DenseAffine, more than one rank, callbacks mixed in.               */
+#define BZ_F_SPARSE_LOGISTIC 8   /* sum_i log(1 + exp(-b_i a_i'x)), A[f_rows][n] in CSR (f_sp_*), the labels b[f_rows] in f_b:
+                                    the logistic loss of a sparse design matrix, never densified.  The plain sum: no 1/2 and
+                                    no 1/m.  The labels are used as given (b_i multiplies the row sum; +-1 is the caller's
+                                    contract, not checked here).  Per row, with u = b_i a_i'x: the loss is softplus(-u) =
+                                    max(-u, 0) + log1p(exp(-|u|)), the gradient A'r with r_i = -b_i sigma(-u); a NaN in u
+                                    reaches the value and the gradient, u = +inf gives loss 0 and r_i = 0, u = -inf loss
+                                    +inf and r_i = -b_i.  Computed in the problem's type (fp32: the fp32 exp / log1p), summed
+                                    in double.  The matrix conventions, the limits, the supported c / D and the refusals of
+                                    BZ_F_SPARSE_LEAST_SQUARES (an empty row gives u = 0: loss log 2, r_i = -b_i / 2).      */
 /* g: proximable cost.  prox!(z,g,x,gamma)->g(z)                                     */
 #define BZ_G_ZERO            0   /* zero.jl:22-25, ProximalOperators.Zero / IndFree   */
 #define BZ_G_NORM_L1         1   /* ProximalOperators.NormL1(lambda) (test_verbose.jl:23) */
@@ -221,6 +230,7 @@ typedef struct {
     bz_D_proj_fn     cb_D_proj;
     /* f, SPARSE_QUADRATIC (with q[n] in f_b): Q in CSR, copied (and validated: BZ_ERR_ARG) at bz_problem_create.
        f, SPARSE_LEAST_SQUARES (with f_rows = m and b[m] in f_b): A in CSR with m rows (rowptr[m + 1], rowptr[m] = nnz).
+       f, SPARSE_LOGISTIC (with f_rows = m and the labels b[m] in f_b): A in CSR with m rows, as SPARSE_LEAST_SQUARES.
        (These four sit in front of c_sp_*: the sparse constraint's fields stay the descriptor's last four.) */
     const int64_t* f_sp_rowptr;    /* rowptr[n + 1], rowptr[0] = 0, non-decreasing, rowptr[n] = nnz */
     const int32_t* f_sp_col;       /* col[nnz], 0-based, in [0, n)                    */

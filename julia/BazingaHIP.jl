@@ -37,6 +37,7 @@ Base.@kwdef mutable struct ProblemDesc
     cb_c_eval::Ptr{Cvoid} = C_NULL; cb_c_jtprod::Ptr{Cvoid} = C_NULL; cb_D_proj::Ptr{Cvoid} = C_NULL
     # f = SparseQuadratic (BZ_F_SPARSE_QUADRATIC): symmetric Q in CSR, 0-based; q in f_b
     # f = SparseLeastSquares (BZ_F_SPARSE_LEAST_SQUARES): A (f_rows x n) in CSR, 0-based; b in f_b
+    # f = SparseLogistic (BZ_F_SPARSE_LOGISTIC): A (f_rows x n) in CSR, 0-based; the labels in f_b
     f_sp_rowptr::Ptr{Cvoid} = C_NULL; f_sp_col::Ptr{Cvoid} = C_NULL; f_sp_val::Ptr{Cvoid} = C_NULL; f_sp_nnz::Int64 = 0
     # c = SparseAffine (BZ_C_SPARSE_AFFINE): A in CSR, 0-based
     c_sp_rowptr::Ptr{Cvoid} = C_NULL; c_sp_col::Ptr{Cvoid} = C_NULL; c_sp_val::Ptr{Cvoid} = C_NULL; c_sp_nnz::Int64 = 0
@@ -157,6 +158,30 @@ function Bazinga.gradient!(dfx, f::SparseLeastSquares, x)
     return sum(r .* r) / 2
 end
 
+"""`SparseLogistic(A::SparseMatrixCSC, labels)`: f(x) = sum_i log(1 + exp(-b_i a_i'x)), the logistic loss of a sparse design
+matrix that is never densified, labels b in {-1, +1} (checked here).  The plain sum: no 1/2 and no 1/m.  The library takes CSR:
+the CSC arrays of `sparse(A')` ARE the CSR arrays of A, made 0-based here."""
+struct SparseLogistic{T} <: Bazinga.ProximableFunction
+    A::SparseMatrixCSC{T,Int}; b::Vector{T}
+    rowptr::Vector{Int64}; col::Vector{Int32}; val::Vector{T}
+    function SparseLogistic(A::SparseMatrixCSC{T}, labels::Vector{T}) where {T}
+        all(v -> abs(v) == 1, labels) || throw(ArgumentError("labels must be -1 or +1"))
+        length(labels) == size(A, 1) || throw(ArgumentError("one label per row of A"))
+        At = sparse(A')
+        new{T}(A, labels, Int64.(At.colptr .- 1), Int32.(At.rowval .- 1), Vector{T}(At.nzval))
+    end
+end
+# u = b .* (A x) ; loss = softplus(-u) = max(-u, 0) + log1p(exp(-|u|)) ; r = -b sigma(-u): ordered compares and arithmetic
+# alone, so that a NaN in u reaches both
+function Bazinga.gradient!(dfx, f::SparseLogistic{T}, x) where {T}
+    u = f.b .* (f.A * x)
+    e = exp.(.-abs.(u))
+    loss = ifelse.(u .< 0, .-u, zero(T)) .+ log1p.(e)
+    s = ifelse.(u .>= 0, e ./ (one(T) .+ e), one(T) ./ (one(T) .+ e))
+    dfx .= f.A' * (.-f.b .* s)
+    return sum(loss)
+end
+
 "`LBFGS(M; compact = nothing)`: how the operator is evaluated (bz_panoc_opts.lbfgs_compact) — `false` the two-loop recursion in the reference's order, `true` the compact representation, `nothing` (default) compact where the one-pass kernel applies"
 struct LBFGS
     memory::Int; compact::Union{Nothing,Bool}
@@ -186,6 +211,9 @@ lower_f!(d, f::SparseQuadratic) = (d.f_kind = 6; d.f_sp_rowptr = pointer(f.rowpt
 lower_f!(d, f::SparseLeastSquares) = (d.f_kind = 7; d.f_rows = length(f.b); d.f_sp_rowptr = pointer(f.rowptr);
                                       d.f_sp_col = pointer(f.col); d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val);
                                       d.f_b = pointer(f.b); nothing)
+lower_f!(d, f::SparseLogistic) = (d.f_kind = 8; d.f_rows = length(f.b); d.f_sp_rowptr = pointer(f.rowptr);
+                                  d.f_sp_col = pointer(f.col); d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val);
+                                  d.f_b = pointer(f.b); nothing)
 lower_f!(d, f) = :generic
 
 lower_g!(d, g::Bazinga.Zero) = (d.g_kind = 0)
