@@ -133,12 +133,12 @@ def _err(a, b):
 
 
 def run_traces(bz, ref, dev, orc, n, mu, y, x0, iters, fuse=True, minimum_gamma=1e-7, dtype=np.float64,
-               ny=None, compact=None, affine_refresh=16, forms=None):
+               ny=None, compact=None, affine_refresh=16, forms=None, form_key="k_fused_iterates"):
     """Step the device solver and the oracle side by side.  Returns rows
     (k, err_x, err_z, gamma_dev, gamma_ref, stop_dev, stop_ref, fused, self_sensitivity).
-    forms: a list that receives the form of the one-pass launch after every device step.  (It is the form of the LAST
-    launch: a step that launches no one-pass kernel repeats the previous step's form, so a fallback step is visible
-    only in the rows' `fused` flags.)"""
+    forms: a list that receives the form of the one-pass launch (of the kernel category `form_key`) after every device
+    step.  (It is the form of the LAST launch: a step that launches no one-pass kernel repeats the previous step's form,
+    so a fallback step is visible only in the rows' `fused` flags.)"""
     ny = n if ny is None else ny
     prob = bz.Problem(*dev, n, ny, dtype)
     prob.set_multipliers(mu, y)
@@ -165,7 +165,7 @@ def run_traces(bz, ref, dev, orc, n, mu, y, x0, iters, fuse=True, minimum_gamma=
         if k + 1 < iters:
             prob.panoc_step()
             if forms is not None:
-                forms.append(prob.profile2()["k_fused_iterates"]["form"])
+                forms.append(prob.profile2()[form_key]["form"])
             sts[0] = its[0].step(sts[0])
             ref.set_reducer(LongDoubleReducer())
             sts[1] = its[1].step(sts[1])
