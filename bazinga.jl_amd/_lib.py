@@ -24,6 +24,8 @@ BZ_F_CALLBACK, BZ_G_CALLBACK, BZ_C_CALLBACK, BZ_D_CALLBACK = 5, 8, 2, 7
 BZ_F_SPARSE_QUADRATIC = 6
 BZ_F_SPARSE_LEAST_SQUARES = 7
 BZ_F_SPARSE_LOGISTIC = 8
+BZ_F_SPARSE_GLM = 9
+BZ_LOSS_LEAST_SQUARES, BZ_LOSS_LOGISTIC, BZ_LOSS_HUBER, BZ_LOSS_SQUARED_HINGE, BZ_LOSS_POISSON = 0, 1, 2, 3, 4
 # host-callback oracle protocol (include/bazinga_hip.h)
 F_GRADIENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
 G_PROX_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_double, C.c_void_p, C.c_int64)
@@ -64,6 +66,7 @@ class ProblemDesc(C.Structure):
         ("cb_user", C.c_void_p), ("cb_f_gradient", F_GRADIENT_FN), ("cb_g_prox", G_PROX_FN),
         ("cb_c_eval", C_EVAL_FN), ("cb_c_jtprod", C_JTPROD_FN), ("cb_D_proj", D_PROJ_FN),
         ("f_sp_rowptr", C.c_void_p), ("f_sp_col", C.c_void_p), ("f_sp_val", C.c_void_p), ("f_sp_nnz", C.c_int64),
+        ("f_loss", C.c_int32), ("f_loss_delta", C.c_double), ("f_w", C.c_void_p), ("f_scale", C.c_double),
         ("c_sp_rowptr", C.c_void_p), ("c_sp_col", C.c_void_p), ("c_sp_val", C.c_void_p), ("c_sp_nnz", C.c_int64),
     ]
 

@@ -228,6 +228,31 @@ template <class T> class Solver final : public SolverBase {
             if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
                 throw Error(BZ_ERR_ARG, "SparseLogistic: n and m must fit 32-bit indices");
         }
+        sparse_glm = d.f_kind == BZ_F_SPARSE_GLM;
+        if (sparse_glm) {
+            // (a `sparse_ls` problem too; the plain least-squares and logistic losses run the epilogues of kinds 7 and 8)
+            sparse_ls = true;
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: the slack (ALS) form is not lowered with a sparse GLM f");
+            if (d.c_kind == BZ_C_DENSE_AFFINE)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: a sparse GLM f beside a dense c (DenseAffine) is not lowered");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: the sparse GLM f is not sharded (one rank)");
+            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: the sparse GLM f does not mix with host callbacks");
+            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
+                throw Error(BZ_ERR_ARG, "SparseGLM needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and b[m]");
+            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
+                throw Error(BZ_ERR_ARG, "SparseGLM: n and m must fit 32-bit indices");
+            if (d.f_loss < BZ_LOSS_LEAST_SQUARES || d.f_loss > BZ_LOSS_POISSON)
+                throw Error(BZ_ERR_ARG, "SparseGLM: f_loss must be one of BZ_LOSS_* (0 .. 4)");
+            if (d.f_loss == BZ_LOSS_HUBER && !(std::isfinite(d.f_loss_delta) && d.f_loss_delta > 0))
+                throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0");
+            if (!(std::isfinite(d.f_scale) && d.f_scale > 0))
+                throw Error(BZ_ERR_ARG, "SparseGLM: f_scale must be finite and > 0 (1 for the plain sum)");
+            glm_loss_ = d.f_loss;
+            // without weights and with scale 1 the least-squares and logistic losses ARE kinds 7 and 8
+            glm_weighted_ = d.f_w != nullptr || d.f_scale != 1.0;
+            sparse_logit = d.f_loss == BZ_LOSS_LOGISTIC && !glm_weighted_;
+        }
         if (d.c_kind == BZ_C_SPARSE_AFFINE) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: the slack (ALS) form is not lowered with a sparse c");
             if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine is not sharded (one rank)");
@@ -378,7 +403,8 @@ template <class T> class Solver final : public SolverBase {
             upload(fb_, d.f_b, frows);
             FR_.alloc(frows);
             if (d.c_kind == BZ_C_SPARSE_AFFINE || !spls_fused_on()) DFX_.alloc(nx);
-            fscale = sparse_logit ? T(1) : T(0.5);
+            fscale = sparse_logit || (sparse_glm && glm_loss_ != BZ_LOSS_LEAST_SQUARES) ? T(1) : T(0.5);
+            if (sparse_glm) glm_weights_create(d);
         }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             A_.alloc((size_t)ny * nx);
@@ -1913,7 +1939,7 @@ template <class T> class Solver final : public SolverBase {
     // rules of A and A'
     void sparse_ls_create(const bz_problem_desc& d) {
         std::vector<int64_t> rp, tp; std::vector<int32_t> col, tcol; std::vector<T> val, tval;
-        sp_read(sparse_logit ? "SparseLogistic" : "SparseLeastSquares", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
+        sp_read(sparse_glm ? "SparseGLM" : sparse_logit ? "SparseLogistic" : "SparseLeastSquares", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
         csr_transpose(frows, nx, rp, col, val, tp, tcol, tval);
         sp_build(spF_, frows, nx, rp, col, val);
         sp_build(spFt_, nx, frows, tp, tcol, tval);
@@ -1921,7 +1947,36 @@ template <class T> class Solver final : public SolverBase {
         spls_form_[1] = sp_form("k_spmv_ls_t_algrad", spFt_);
         spls_form_[2] = sp_form("k_spmv_ls_t", spFt_);
         if (sparse_logit) splogit_form_ = sp_form("k_spmv_logit_r", spF_);
+        if (glm_own_kernel()) {
+            static const char* const names[] = {"least_squares", "logistic", "huber", "squared_hinge", "poisson"};
+            glm_form_ = std::string("k_spmv_glm_r<LOSS=") + names[glm_loss_] + ",W=" + (desc.f_w ? "1" : "0") + ",L=" +
+                        std::to_string(spF_.L) + ",SEG=" + (spF_.ncut ? "1" : "0") + ">";
+        }
     }
+    // the GLM f: w^_i = T(scale * w_i), the product in double and rounded once; without a weight vector the one number T(scale).
+    // Every w_i finite and >= 0, checked on a host copy.
+    void glm_weights_create(const bz_problem_desc& d) {
+        glm_w_uniform_ = (T)d.f_scale;
+        glm_delta_ = (T)d.f_loss_delta;
+        // (what the kernel multiplies by is the ROUNDED number: an fp32 problem can overflow where the double was finite)
+        if (!std::isfinite((double)glm_w_uniform_))
+            throw Error(BZ_ERR_ARG, "SparseGLM: f_scale must be finite and > 0 in the problem's type");
+        if (d.f_loss == BZ_LOSS_HUBER && !(std::isfinite((double)glm_delta_) && glm_delta_ > T(0)))
+            throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0 in the problem's type");
+        if (!d.f_w) return;
+        std::vector<T> w((size_t)frows);
+        BZ_HIP(hipMemcpy(w.data(), d.f_w, w.size() * sizeof(T), hipMemcpyDefault));
+        for (int64_t r = 0; r < frows; ++r) {
+            if (!(std::isfinite((double)w[r]) && w[r] >= T(0)))
+                throw Error(BZ_ERR_ARG, "SparseGLM: the weights must be finite and >= 0 (row " + std::to_string(r) + ")");
+            w[r] = (T)(d.f_scale * (double)w[r]);
+            if (!std::isfinite((double)w[r]))
+                throw Error(BZ_ERR_ARG, "SparseGLM: the weights times f_scale must be finite in the problem's type (row " + std::to_string(r) + ")");
+        }
+        sp_upload(glm_w_, w);
+    }
+    // (the plain least-squares and logistic losses run k_spmv_ls_r / k_spmv_logit_r)
+    bool glm_own_kernel() const { return sparse_glm && (glm_weighted_ || glm_loss_ >= BZ_LOSS_HUBER); }
     // c = SparseAffine: validate the caller's CSR on a host copy, build A' (csr_transpose: a column's entries stay in ascending row
     // order) and put both in HBM
     void sparse_create(const bz_problem_desc& d) {
@@ -1949,7 +2004,7 @@ template <class T> class Solver final : public SolverBase {
         });
     }
     // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A', 3: k_spmv_q over Q, 4: k_spmv_ls_r
-    // over A_f, 5: k_spmv_ls_t_algrad and 6: k_spmv_ls_t over A_f', 7: k_spmv_logit_r over A_f) and, for a cut matrix, the fold of its cut rows; returns
+    // over A_f, 5: k_spmv_ls_t_algrad and 6: k_spmv_ls_t over A_f', 7: k_spmv_logit_r and 8 .. 12: k_spmv_glm_r over A_f) and, for a cut matrix, the fold of its cut rows; returns
     // the number of block partials left in `slot`
     template <int MODE> int sp_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
         const double bytes = m.bytes() + vec_bytes;
@@ -1962,14 +2017,15 @@ template <class T> class Solver final : public SolverBase {
             const int64_t rpb = BLOCK / L;
             g = (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - gfold, (m.nv + rpb - 1) / rpb));
             pending_bytes_ += bytes;
-            nm((MODE < 4 ? sp_form_[MODE & 3] : MODE == 7 ? splogit_form_ : spls_form_[MODE >= 4 && MODE < 7 ? MODE - 4 : 0]).c_str());
+            nm((MODE < 4 ? sp_form_[MODE & 3] : MODE >= SP_GLM_MODE0 ? glm_form_ : MODE == 7 ? splogit_form_ : spls_form_[MODE >= 4 && MODE < 7 ? MODE - 4 : 0]).c_str());
             if constexpr (MODE == 0) launch(C_GEMV, k_spmv_yupd<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 1) launch(C_GEMV, k_spmv_t_finish<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 3) launch(C_GEMV, k_spmv_q<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 4) launch(C_GEMV, k_spmv_ls_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 5) launch(C_GEMV, k_spmv_ls_t_algrad<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
             else if constexpr (MODE == 6) launch(C_GEMV, k_spmv_ls_t<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else launch(C_GEMV, k_spmv_logit_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else if constexpr (MODE == 7) launch(C_GEMV, k_spmv_logit_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
+            else launch(C_GEMV, k_spmv_glm_r<T, L, NT, MODE>, g, m.mat(), gathered, E, parts_.p, slot);
         };
         sp_with_lanes(m.L, nt, go);
         if (gfold) {
@@ -2020,11 +2076,23 @@ template <class T> class Solver final : public SolverBase {
     // (pairwise D: the projection of element i needs its partner, which a row's first lane does not have)
     bool spq_fused_on() const { return cenv_.spq_fused && !(desc.D_kind >= BZ_D_VC_PAIRS && desc.D_kind <= BZ_D_XOR_PAIRS); }
 
-    // ---- f = SparseLeastSquares / SparseLogistic
+    // ---- f = SparseLeastSquares / SparseLogistic / SparseGLM
     // rows of A_f: r = A_f x - b -> r_out (null: not kept) and the partials of sum r^2 -> slot.  Per row: b (and r).
     // The logistic f: r_i = -b_i sigma(-b_i a_i'x) and the partials of the rows' losses, the same streams.
+    // The GLM f: r_i = w_i l'(b_i, a_i'x) and the partials of the weighted losses; a weight vector is one more stream.
     int spls_residual(const T* x, T* r_out, int slot) {
         SpEpi<T> E{fb_.p, nullptr, r_out, nullptr, P, nullptr};
+        if (glm_own_kernel()) {
+            E.w = glm_w_.p; E.w_uniform = glm_w_uniform_; E.delta = glm_delta_;
+            const double vecs = (1 + (r_out ? 1 : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T);
+            switch (glm_loss_) {
+            case BZ_LOSS_LEAST_SQUARES: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES>(spF_, x, E, slot, vecs);
+            case BZ_LOSS_LOGISTIC: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_LOGISTIC>(spF_, x, E, slot, vecs);
+            case BZ_LOSS_HUBER: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_HUBER>(spF_, x, E, slot, vecs);
+            case BZ_LOSS_SQUARED_HINGE: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE>(spF_, x, E, slot, vecs);
+            default: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_POISSON>(spF_, x, E, slot, vecs);
+            }
+        }
         if (sparse_logit) return sp_pass<7>(spF_, x, E, slot, (1 + (r_out ? 1 : 0)) * (double)frows * sizeof(T));
         return sp_pass<4>(spF_, x, E, slot, (1 + (r_out ? 1 : 0)) * (double)frows * sizeof(T));
     }
@@ -3498,6 +3566,13 @@ template <class T> class Solver final : public SolverBase {
     // ---- f = SparseLogistic: a sparse_ls problem (both flags set) whose rows of A_f run k_spmv_logit_r
     bool sparse_logit = false;
     std::string splogit_form_;
+    // ---- f = SparseGLM: a sparse_ls problem whose rows of A_f run k_spmv_glm_r<loss> (the plain least-squares and logistic
+    // losses: k_spmv_ls_r / k_spmv_logit_r, sparse_logit set with the latter)
+    bool sparse_glm = false, glm_weighted_ = false;
+    int glm_loss_ = 0;
+    DBuf<T> glm_w_;                        // [m] scale * w, or empty: glm_w_uniform_ = scale for every row
+    T glm_w_uniform_ = T(1), glm_delta_ = T(0);
+    std::string glm_form_;
 };
 
 // one-pass kernel of an oracle family: the instantiations live in bz_families_dk*.hip (one file per D class, so that

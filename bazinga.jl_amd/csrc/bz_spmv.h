@@ -1,7 +1,9 @@
 // bz_spmv.h — the CSR row kernels: the sparse affine constraint c(x) = A x - b (BZ_C_SPARSE_AFFINE), the two passes of its AL
 // gradient, the sparse quadratic f(x) = 0.5 x'Qx + q'x (BZ_F_SPARSE_QUADRATIC), the pass over Q, and the sparse least squares
 // f(x) = 0.5 ||A_f x - b||^2 (BZ_F_SPARSE_LEAST_SQUARES), the passes over A_f and A_f', and the sparse logistic
-// f(x) = sum_i log(1 + exp(-b_i a_i'x)) (BZ_F_SPARSE_LOGISTIC), the same two passes with another epilogue on the rows of A_f.
+// f(x) = sum_i log(1 + exp(-b_i a_i'x)) (BZ_F_SPARSE_LOGISTIC), the same two passes with another epilogue on the rows of A_f,
+// and the sparse GLM f(x) = sum_i w_i l(b_i, a_i'x) (BZ_F_SPARSE_GLM): a row loss l with its derivative as r_i and a weight
+// per row, one more epilogue per loss (weighted least squares and logistic, Huber, squared hinge, Poisson).
 //
 // A and A' are two CSR matrices in HBM (A' is built once, at bz_problem_create, by a stable counting sort).  Both passes
 // are the same row kernel: L lanes (compile time, 1..64, chosen at creation from the mean row length) walk one row, lane
@@ -20,6 +22,8 @@
 //   k_spmv_ls_t         rows of A_f':  A_f' r -> DFX for the forms that finish element-wise or in k_spmv_t_finish
 //   k_spmv_logit_r      rows of A_f, the logistic f:  r_i = -b_i sigma(-b_i a_i'x) -> R (if kept) and the terms
 //                       softplus(-b_i a_i'x); the two kernels over A_f' then run on that r as they do on a residual
+//   k_spmv_glm_r<LOSS>  rows of A_f, the GLM f:  r_i = w_i l'(b_i, a_i'x) -> R (if kept) and the terms w_i l(b_i, a_i'x), the
+//                       loss a template argument (MODE 8 .. 12); the same two kernels over A_f' behind it
 // Rows longer than S entries (S fixed at creation from the matrix alone) are cut into segments that run as rows of
 // their own ("virtual rows": the row pointers refined at the cuts); a segment leaves its sum in a side buffer and
 // k_spmv_fold, one wave per cut row, adds a row's segment sums in a fixed order and runs the row's epilogue.
@@ -27,6 +31,7 @@
 // Kept apart from bz_kernels.h because only bz_solver.hip instantiates these templates: the sixteen family translation
 // units do not see (or rebuild for) them.
 #pragma once
+#include <limits>
 #include "bz_kernels.h"
 
 namespace bz {
@@ -45,7 +50,9 @@ template <class T> struct SpMat {
 // the penalty term; MODE 1 (rows of A'): the gradient and the f term; MODE 2 (rows of Q, c = Identity): the gradient, the
 // f term and the penalty term; MODE 3 (rows of Q): Q x (if kept) and the f term (if x is given); MODE 4 (rows of A_f): the
 // residual (if kept) and its square; MODE 5 (rows of A_f', c = Identity): the gradient and the penalty term; MODE 6 (rows
-// of A_f'): the product alone; MODE 7 (rows of A_f, logistic): the derivative of the row's loss (if kept) and the loss.
+// of A_f'): the product alone; MODE 7 (rows of A_f, logistic): the derivative of the row's loss (if kept) and the loss;
+// MODE 8 .. 12 (rows of A_f, the GLM f): the same for the weighted loss SP_GLM_MODE0 + BZ_LOSS_*.
+constexpr int SP_GLM_MODE0 = 8;      // MODE 8 + loss: 8 least squares, 9 logistic, 10 Huber, 11 squared hinge, 12 Poisson
 template <class T> struct SpEpi {
     const T* b;              // MODE 0: b[ny] ; MODE 4: b[m] of f ; MODE 7: the labels b[m] of f
     T* cx;                   // MODE 0: c(x) for the caller that keeps it, or null
@@ -54,10 +61,13 @@ template <class T> struct SpEpi {
     const T* x;              // MODE 1, 2, 5: x[n] ; MODE 3: x[n], or null for the product alone
     ElemParams<T> P;
     const T* ext;            // MODE 1 with the sparse quadratic f: (Q x)[n], left by k_spmv_q ; with the sparse least
-                             // squares or logistic f: (A_f' r)[n], left by k_spmv_ls_t
+                             // squares, logistic or GLM f: (A_f' r)[n], left by k_spmv_ls_t
+    const T* w;              // MODE 8 .. 12: the row weights w[m] (scale folded in), or null: w_uniform for every row
+    T w_uniform;
+    T delta;                 // MODE 10: Huber's delta
 };
 
-// scalars a mode leaves per row: MODE 2 the f term and the penalty term, the others (MODE 7: the loss) one
+// scalars a mode leaves per row: MODE 2 the f term and the penalty term, the others (MODE 7 .. 12: the loss) one
 template <int MODE> constexpr int sp_nacc() { return MODE == 2 ? 2 : 1; }
 
 // exp and log1p in T: an fp32 problem takes the fp32 functions
@@ -98,8 +108,8 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
             const T xv = E.x[r], e = E.ext[r], qv = P.b[r];
             dfx = e + qv;
             fterm = xv * (T(0.5) * e + qv);
-        } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES || P.f_kind == BZ_F_SPARSE_LOGISTIC) {
-            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r / k_spmv_logit_r)
+        } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES || P.f_kind == BZ_F_SPARSE_LOGISTIC || P.f_kind == BZ_F_SPARSE_GLM) {
+            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r / k_spmv_logit_r / k_spmv_glm_r)
         }
         if (E.out) E.out[r] = dfx + (T)d;
         acc[0] += (double)fterm;
@@ -147,6 +157,46 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
         const T s = u >= T(0) ? e / (T(1) + e) : T(1) / (T(1) + e);
         if (E.out) E.out[r] = -bv * s;
         acc[0] += (double)loss;
+    } else if constexpr (MODE >= SP_GLM_MODE0) {
+        // the GLM f: the row's term w l(b, t) and r = w l'(b, t), t = a_i'x, the loss fixed at compile time.  One pointer test
+        // and one load for the weight, as mu has it; every branch below is a select on values already at hand.  Ordered
+        // compares and arithmetic alone: a NaN in t makes every compare false and reaches both the loss and r.
+        constexpr int LOSS = MODE - SP_GLM_MODE0;
+        const T wv = E.w ? E.w[r] : E.w_uniform;
+        const T bv = E.b[r];
+        const T t = (T)d;
+        T loss, dl;
+        if constexpr (LOSS == BZ_LOSS_LEAST_SQUARES) {
+            const T v = t - bv;                                     // sum w v^2, halved on the host (fscale)
+            loss = v * v;
+            dl = v;
+        } else if constexpr (LOSS == BZ_LOSS_LOGISTIC) {
+            const T u = bv * t;                                     // MODE 7's operations
+            const T e = sp_exp(u < T(0) ? u : -u);
+            loss = (u < T(0) ? -u : T(0)) + sp_log1p(e);
+            const T s = u >= T(0) ? e / (T(1) + e) : T(1) / (T(1) + e);
+            dl = -bv * s;
+        } else if constexpr (LOSS == BZ_LOSS_HUBER) {
+            const T v = t - bv, dlt = E.delta;
+            const T a = v < T(0) ? -v : v;
+            const bool inside = a <= dlt;
+            loss = inside ? T(0.5) * v * v : dlt * (a - T(0.5) * dlt);
+            dl = inside ? v : (v > T(0) ? dlt : (v < T(0) ? -dlt : v));      // (only a NaN takes the last arm)
+        } else if constexpr (LOSS == BZ_LOSS_SQUARED_HINGE) {
+            const T h = T(1) - bv * t;
+            const bool off = h <= T(0);
+            loss = off ? T(0) : T(0.5) * h * h;
+            dl = off ? T(0) : -bv * h;
+        } else {
+            // Poisson, log link: e - b t without the constant log b!.  Where e has overflowed (fp32: t beyond 88.7) the loss is
+            // +inf, not inf - inf; b = 0 drops the product, so that t = -inf gives 0 and not 0 * inf.
+            const T e = sp_exp(t);
+            const T bt = bv == T(0) ? T(0) : bv * t;
+            loss = e < std::numeric_limits<T>::infinity() ? e - bt : e;
+            dl = e - bv;
+        }
+        if (E.out) E.out[r] = wv * dl;
+        acc[0] += (double)(wv * loss);
     } else {
         if (E.out) E.out[r] = (T)d;
     }
@@ -336,6 +386,17 @@ __global__ void __launch_bounds__(BLOCK)
 k_spmv_logit_r(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
     spmv_rows<T, L, NT, 7>(M, x, E, acc);
+    block_reduce_store<1>(acc, 0u, parts, slot0);
+}
+
+// rows of A_f, the GLM f with the loss MODE - SP_GLM_MODE0: r_i = w_i l'(b_i, a_i'x) -> E.out (if kept) ; partials: slot0 the
+// terms w_i l(b_i, a_i'x)
+template <class T, int L, bool NT, int MODE>
+__global__ void __launch_bounds__(BLOCK)
+k_spmv_glm_r(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    static_assert(MODE >= SP_GLM_MODE0 && MODE <= SP_GLM_MODE0 + BZ_LOSS_POISSON, "a GLM mode");
+    double acc[1] = {0.0};
+    spmv_rows<T, L, NT, MODE>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 

@@ -354,6 +354,159 @@ class SparseLogistic(ProximableFunction):
         return x.dtype.type(np.sum(loss))
 
 
+class SparseGLM(ProximableFunction):
+    """A row loss of a sparse design matrix with a weight per row: f(x) = sum_i w^_i l(b_i, t_i), t = A x, w^_i = scale * w_i,
+    A m-by-n in CSR (indptr[m + 1], indices[nnz] 0-based, data[nnz]), never densified; the gradient is A'r with
+    r_i = w^_i dl/dt(b_i, t_i).  The matrix conventions of SparseLeastSquares (unsorted and repeated column indices, empty rows
+    and columns, nnz = 0; an empty row has t = 0).  `loss`, with v = t - b and u = b t:
+      "least_squares"  l = v^2 / 2, l' = v (the 1/2 is taken on the sum)
+      "logistic"       b = +-1: SparseLogistic's l = softplus(-u), l' = -b sigma(-u)
+      "huber"          delta > 0: |v| <= delta: l = v^2 / 2, l' = v ; otherwise l = delta (|v| - delta / 2), l' = +-delta
+      "squared_hinge"  b = +-1, h = 1 - u: h <= 0: l = l' = 0 ; otherwise l = h^2 / 2, l' = -b h
+      "poisson"        counts b >= 0, log link, without the constant log b!: e = exp(t), l = e - b t (b = 0: l = e ; where e has
+                       overflowed l = +inf, never inf - inf), l' = e - b
+    Ordered compares and arithmetic alone: a NaN in t reaches the loss and r.  `weights` (w[m] >= 0, or None) and `scale` (> 0;
+    1 / m gives the mean) are folded into one number per row, the product in float64 rounded once to the dtype; the row's term
+    is w^ * l and r = w^ * l', one multiplication each.  __call__ / gradient below are numpy with these formulas in the dtype
+    of x (the generic-oracle protocol); on the device the kind is BZ_F_SPARSE_GLM."""
+
+    LOSSES = ("least_squares", "logistic", "huber", "squared_hinge", "poisson")
+
+    def __init__(self, indptr, indices, data, b, n, loss, delta=None, weights=None, scale=1.0):
+        ip, ix = np.asarray(indptr), np.asarray(indices)
+        self.data = np.ascontiguousarray(data)
+        bb = np.asarray(b)
+        self.n = int(n)
+        if loss not in self.LOSSES:
+            raise ValueError(f"unknown loss {loss!r}: one of {self.LOSSES}")
+        self.loss = loss
+        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or bb.ndim != 1:
+            raise ValueError("indptr, indices, data and b must be one-dimensional")
+        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr and indices must be integer arrays")
+        if self.data.dtype not in (np.float64, np.float32):
+            raise ValueError("data must be float64 or float32")
+        if not (np.issubdtype(bb.dtype, np.integer) or bb.dtype in (np.float64, np.float32)):
+            raise ValueError("b must be float64, float32 or integers")
+        if loss in ("logistic", "squared_hinge") and not np.all(np.abs(bb) == 1):
+            raise ValueError(f"labels must be -1 or +1 for the {loss} loss")
+        if loss == "poisson" and not np.all(np.isfinite(bb) & (bb >= 0)):
+            raise ValueError("counts must be finite and >= 0 for the poisson loss")
+        if loss == "huber":
+            if delta is None or not (np.isfinite(delta) and delta > 0):
+                raise ValueError("the huber loss needs delta finite and > 0")
+        elif delta is not None:
+            raise ValueError(f"delta is the huber loss's parameter, not the {loss} loss's")
+        self.delta = None if delta is None else float(delta)
+        if not (np.ndim(scale) == 0 and np.isfinite(scale) and scale > 0):
+            raise ValueError("scale must be a finite number > 0")
+        self.scale = float(scale)
+        self.b = np.ascontiguousarray(bb, dtype=self.data.dtype if np.issubdtype(bb.dtype, np.integer) else bb.dtype)
+        self.m = self.b.shape[0]
+        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+            raise ValueError("n and the length of b must be in 1 .. 2^31 - 1")
+        self.weights = None
+        if weights is not None:
+            w = np.asarray(weights)
+            if not (np.issubdtype(w.dtype, np.integer) or w.dtype in (np.float64, np.float32)):
+                raise ValueError("weights must be float64, float32 or integers")
+            if w.shape != (self.m,) or not np.all(np.isfinite(w) & (w >= 0)):
+                raise ValueError(f"weights must be {self.m} finite numbers >= 0")
+            self.weights = np.ascontiguousarray(w, dtype=self.data.dtype if np.issubdtype(w.dtype, np.integer) else w.dtype)
+        if ip.shape[0] != self.m + 1:
+            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
+        if ix.shape[0] != self.data.shape[0]:
+            raise ValueError("indices and data must have the same length")
+        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
+        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
+            raise ValueError(f"column indices must lie in [0, {self.n})")
+        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
+        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
+        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+
+    @property
+    def nnz(self):
+        return int(self.indices.shape[0])
+
+    @classmethod
+    def from_dense(cls, A, b, loss, **kw):
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise ValueError("A must be m-by-n")
+        mask = A != 0
+        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
+        indices = np.nonzero(mask)[1].astype(np.int32)
+        return cls(indptr, indices, np.ascontiguousarray(A[mask]), b, A.shape[1], loss, **kw)
+
+    @classmethod
+    def from_scipy(cls, M, b, loss, **kw):
+        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        return cls(M.indptr, M.indices, M.data, b, M.shape[1], loss, **kw)
+
+    def toarray(self):
+        A = np.zeros((self.m, self.n), self.data.dtype)
+        np.add.at(A, (self._rows, self.indices), self.data)
+        return A
+
+    def row_weights(self, dtype):
+        """w^ in dtype: scale * w with the product in float64, rounded once (without weights the one number scale)"""
+        dt = np.dtype(dtype).type
+        with np.errstate(over="ignore"):                 # (a product beyond the dtype's range rounds to inf: lower() refuses it)
+            if self.weights is None:
+                return dt(self.scale)
+            return (self.scale * self.weights.astype(np.float64)).astype(dt)
+
+    @staticmethod
+    def loss_and_derivative(loss, delta, b, t):
+        """the rows' l(b, t) and dl/dt(b, t) in the dtype of t (least_squares: v^2, the 1/2 being taken on the sum)"""
+        dt = t.dtype.type
+        with np.errstate(over="ignore", invalid="ignore"):
+            if loss == "least_squares":
+                v = t - b
+                return v * v, v
+            if loss == "logistic":
+                u = b * t
+                e = np.exp(-np.abs(u))
+                s = np.where(u >= 0, e / (dt(1) + e), dt(1) / (dt(1) + e))
+                return np.where(u < 0, -u, dt(0)) + np.log1p(e), -b * s
+            if loss == "huber":
+                v, d = t - b, dt(delta)
+                a = np.where(v < 0, -v, v)
+                inside = a <= d
+                return (np.where(inside, dt(0.5) * v * v, d * (a - dt(0.5) * d)),
+                        np.where(inside, v, np.where(v > 0, d, np.where(v < 0, -d, v))))
+            if loss == "squared_hinge":
+                h = dt(1) - b * t
+                off = h <= 0
+                return np.where(off, dt(0), dt(0.5) * h * h), np.where(off, dt(0), -b * h)
+            e = np.exp(t)
+            bt = np.where(b == 0, dt(0), b * t)
+            return np.where(e < np.inf, e - bt, e), e - b
+
+    def _loss_r(self, x):
+        """the rows' terms w^ l (least_squares: w^ v^2) and r = w^ l' in the dtype of x"""
+        t = np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.m).astype(x.dtype, copy=False)
+        l, dl = self.loss_and_derivative(self.loss, self.delta, self.b.astype(x.dtype, copy=False), t)
+        w = self.row_weights(x.dtype)
+        with np.errstate(over="ignore", invalid="ignore"):
+            return w * l, w * dl
+
+    def _value(self, terms, dt):
+        fx = dt(np.sum(terms))
+        return dt(0.5) * fx if self.loss == "least_squares" else fx
+
+    def __call__(self, x):
+        return self._value(self._loss_r(x)[0], x.dtype.type)
+
+    def gradient(self, dfx, x):
+        terms, r = self._loss_r(x)
+        dfx[...] = np.bincount(self.indices, weights=self.data * r[self._rows], minlength=self.n)
+        return self._value(terms, x.dtype.type)
+
+
 class Stencil5ptQuadratic(ProximableFunction):
     """f(x) = 0.5 x'A_h x - b'x on an nx-by-ny grid (row-major), A_h the 5-point Laplacian
     (4,-1,-1,-1,-1) with homogeneous Dirichlet halo — the structured `Quadratic` of BASELINE
@@ -689,7 +842,7 @@ def _vec(a, dtype, n, name):
 
 
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, SparseLeastSquares,
-                                      SparseLogistic, Stencil5ptQuadratic))
+                                      SparseLogistic, SparseGLM, Stencil5ptQuadratic))
 _LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
@@ -853,6 +1006,28 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
         d.f_sp_nnz = f.nnz
         d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "labels")))
+    elif isinstance(f, SparseGLM):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("SparseGLM is not lowered in the slack (ALS) form")
+        if isinstance(c, DenseAffine):
+            raise UnsupportedOracle("SparseGLM is not lowered beside a dense c (DenseAffine)")
+        if f.n != n:
+            raise ValueError(f"A must have {n} columns")
+        d.f_kind = L.BZ_F_SPARSE_GLM
+        d.f_rows = f.m
+        d.f_sp_rowptr = ptr(f.indptr)
+        d.f_sp_col = ptr(f.indices)
+        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
+        d.f_sp_nnz = f.nnz
+        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "b")))
+        d.f_loss = SparseGLM.LOSSES.index(f.loss)
+        d.f_loss_delta = 0.0 if f.delta is None else f.delta
+        d.f_scale = f.scale
+        if not np.all(np.isfinite(f.row_weights(dtype))) or (f.delta is not None and not np.isfinite(dtype.type(f.delta))):
+            raise ValueError(f"scale, scale * weights and delta must be finite in {dtype}")
+        if f.weights is not None:
+            d.f_w = ptr(np.ascontiguousarray(_vec(f.weights, dtype, f.m, "weights")))
     elif isinstance(f, Stencil5ptQuadratic):
         d.f_kind = L.BZ_F_STENCIL5
         d.f_grid_nx, d.f_grid_ny = f.nx, f.ny
@@ -905,7 +1080,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         # what the library refuses with this kind, refused here before any device call
         if slack:
             raise UnsupportedOracle("SparseAffine is not lowered in the slack (ALS) form")
-        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares, SparseLogistic)):
+        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares, SparseLogistic, SparseGLM)):
             raise UnsupportedOracle(f"SparseAffine is lowered with an element-wise f (Zero, DiagQuadratic), not {type(f).__name__}")
         if isinstance(D, PairwiseSet):
             raise UnsupportedOracle("pairwise D sets need c = IdentityFunction")

@@ -195,6 +195,47 @@ def sparse_logistic(m: int, n: int, k: int = 5, dtype=np.float64, seed: int = SE
             "labels": labels.astype(dtype), "m": m, "n": n, "xstar": xstar.astype(dtype)}
 
 
+GLM_LOSSES = ("least_squares", "logistic", "huber", "squared_hinge", "poisson")
+
+
+def sparse_glm(m: int, n: int, k: int = 5, loss: str = "huber", dtype=np.float64, seed: int = SEED):
+    """A sparse GLM: min sum_i w_i l(b_i, a_i'x) + lam ||x||_1 with the matrix and the planted x* of sparse_lasso(m, n, k, dtype,
+    seed) and b by the loss.  least_squares: sparse_lasso's b = A x* + 0.01 (2 u8 - 1).  huber (delta = 1): the same with a
+    gross outlier in every 16th row, b_i += 10 (2 u10 - 1) + (5 or -5 by the sign of that draw) at i = 15, 31, ...  logistic and
+    squared_hinge: sparse_logistic's labels.  poisson: the margins scaled into [-2, 2], t~ = 2 A x* / max|A x*| (the planted
+    vector returned is scaled with them), and the counts by inverse CDF at the rate exp(t~_i): the smallest c with
+    P(Poisson(rate) <= c) >= u9.  `delta` is 1 for huber and None otherwise."""
+    if loss not in GLM_LOSSES:
+        raise ValueError(f"loss must be one of {GLM_LOSSES}")
+    if not 1 <= k <= n or m < 1:
+        raise ValueError("sparse_glm needs m >= 1 and 1 <= k <= n")
+    cols, data, xstar, Axstar = _sparse_rows(m, n, k, dtype, seed)
+    delta = None
+    if loss in ("logistic", "squared_hinge"):
+        b = np.where(Axstar + 0.1 * (2.0 * uniform(9, m, seed=seed) - 1.0) >= 0, 1.0, -1.0)
+    elif loss == "poisson":
+        top = float(np.max(np.abs(Axstar)))
+        s = 2.0 / top if top > 0 else 1.0
+        xstar, rate = s * xstar, np.exp(s * Axstar)
+        u = uniform(9, m, seed=seed)
+        b = np.zeros(m)
+        pmf = np.exp(-rate)
+        cdf = pmf.copy()
+        for c in range(1, 48):                       # (rate <= e^2: the tail beyond 47 is below 2^-53)
+            b[cdf < u] = c
+            pmf = pmf * rate / c
+            cdf += pmf
+    else:
+        b = Axstar + 0.01 * (2.0 * uniform(8, m, seed=seed) - 1.0)
+        if loss == "huber":
+            delta = 1.0
+            out = 2.0 * uniform(10, m, seed=seed) - 1.0
+            rows = np.arange(15, m, 16)
+            b[rows] += 10.0 * out[rows] + np.where(out[rows] >= 0, 5.0, -5.0)
+    return {"indptr": k * np.arange(m + 1, dtype=np.int64), "indices": cols.reshape(-1).astype(np.int32), "data": data,
+            "b": b.astype(dtype), "m": m, "n": n, "xstar": xstar.astype(dtype), "loss": loss, "delta": delta}
+
+
 def portfolio(n: int, dtype=np.float64, rank: int | None = None):
     """A stand-in for the absent demo/portfolio_data (demo/portfolio.jl:70-91: Q, rho, mu, ub), from the uniform stream:
 

@@ -79,6 +79,26 @@ extern "C" {
                                     +inf and r_i = -b_i.  Computed in the problem's type (fp32: the fp32 exp / log1p), summed
                                     in double.  The matrix conventions, the limits, the supported c / D and the refusals of
                                     BZ_F_SPARSE_LEAST_SQUARES (an empty row gives u = 0: loss log 2, r_i = -b_i / 2).      */
+#define BZ_F_SPARSE_GLM      9   /* sum_i w^_i l(b_i, t_i), t = A x, w^_i = f_scale * w_i: a row loss (f_loss, BZ_LOSS_*) of a sparse
+                                    design matrix A[f_rows][n] in CSR (f_sp_*), b[f_rows] in f_b, optional row weights w[f_rows] in
+                                    f_w (NULL: all ones).  The gradient is A'r with r_i = w^_i dl/dt(b_i, t_i).  w^_i is formed at
+                                    bz_problem_create, the product in double and rounded once to the problem's type; the row's
+                                    term is w^_i * l and r_i = w^_i * l', one multiplication each in that type, the sum in double.
+                                    Ordered compares and arithmetic alone: a NaN in t reaches the value and the gradient.  An empty
+                                    row has t = 0.  Checked here (BZ_ERR_ARG): f_loss in range, f_loss_delta finite and > 0 for
+                                    Huber, f_scale finite and > 0 (a zeroed field is an error), every w_i finite and >= 0, each of them
+                                    also as rounded to the problem's type (an fp32 problem: no overflow to +inf); labels
+                                    and counts are the caller's contract.  The matrix conventions, the limits, the supported
+                                    c / D and the refusals of BZ_F_SPARSE_LEAST_SQUARES.  BZ_LOSS_LEAST_SQUARES / BZ_LOSS_LOGISTIC
+                                    without weights and with f_scale = 1 are kinds 7 / 8 bit for bit.                       */
+/* the row losses of BZ_F_SPARSE_GLM (f_loss), with v = t - b and u = b t                                   */
+#define BZ_LOSS_LEAST_SQUARES 0  /* l = v^2 / 2, l' = v                                                      */
+#define BZ_LOSS_LOGISTIC      1  /* b = +-1: BZ_F_SPARSE_LOGISTIC's l = softplus(-u), l' = -b sigma(-u)       */
+#define BZ_LOSS_HUBER         2  /* delta = f_loss_delta > 0: |v| <= delta: l = v^2 / 2, l' = v ; otherwise
+                                    l = delta (|v| - delta / 2), l' = +-delta; v = +-inf: l = +inf, l' = +-delta */
+#define BZ_LOSS_SQUARED_HINGE 3  /* b = +-1, h = 1 - u: h <= 0: l = l' = 0 ; otherwise l = h^2 / 2, l' = -b h   */
+#define BZ_LOSS_POISSON       4  /* counts b >= 0, log link, without the constant log b!: e = exp(t), l = e - b t
+                                    (b = 0: l = e; e overflowed: l = +inf, never inf - inf), l' = e - b             */
 /* g: proximable cost.  prox!(z,g,x,gamma)->g(z)                                     */
 #define BZ_G_ZERO            0   /* zero.jl:22-25, ProximalOperators.Zero / IndFree   */
 #define BZ_G_NORM_L1         1   /* ProximalOperators.NormL1(lambda) (test_verbose.jl:23) */
@@ -231,11 +251,17 @@ typedef struct {
     /* f, SPARSE_QUADRATIC (with q[n] in f_b): Q in CSR, copied (and validated: BZ_ERR_ARG) at bz_problem_create.
        f, SPARSE_LEAST_SQUARES (with f_rows = m and b[m] in f_b): A in CSR with m rows (rowptr[m + 1], rowptr[m] = nnz).
        f, SPARSE_LOGISTIC (with f_rows = m and the labels b[m] in f_b): A in CSR with m rows, as SPARSE_LEAST_SQUARES.
-       (These four sit in front of c_sp_*: the sparse constraint's fields stay the descriptor's last four.) */
+       f, SPARSE_GLM: A, f_rows and f_b as SPARSE_LEAST_SQUARES, and the four fields behind f_sp_nnz.
+       (All of these sit in front of c_sp_*: the sparse constraint's fields stay the descriptor's last four.) */
     const int64_t* f_sp_rowptr;    /* rowptr[n + 1], rowptr[0] = 0, non-decreasing, rowptr[n] = nnz */
     const int32_t* f_sp_col;       /* col[nnz], 0-based, in [0, n)                    */
     const void*    f_sp_val;       /* val[nnz]                                        */
     int64_t        f_sp_nnz;
+    /* f, SPARSE_GLM alone (the other kinds ignore them) */
+    int32_t        f_loss;         /* BZ_LOSS_*                                       */
+    double         f_loss_delta;   /* BZ_LOSS_HUBER: delta, finite and > 0            */
+    const void*    f_w;            /* w[f_rows] >= 0 in the problem's type, or NULL: no weights */
+    double         f_scale;        /* finite and > 0 (1: the plain sum; 1 / f_rows: the mean)  */
     /* c, SPARSE_AFFINE (with c_b[ny]): A in CSR, copied (and validated: BZ_ERR_ARG) at bz_problem_create */
     const int64_t* c_sp_rowptr;    /* rowptr[ny + 1], rowptr[0] = 0, non-decreasing, rowptr[ny] = nnz */
     const int32_t* c_sp_col;       /* col[nnz], 0-based, in [0, n)                    */

@@ -39,6 +39,8 @@ Base.@kwdef mutable struct ProblemDesc
     # f = SparseLeastSquares (BZ_F_SPARSE_LEAST_SQUARES): A (f_rows x n) in CSR, 0-based; b in f_b
     # f = SparseLogistic (BZ_F_SPARSE_LOGISTIC): A (f_rows x n) in CSR, 0-based; the labels in f_b
     f_sp_rowptr::Ptr{Cvoid} = C_NULL; f_sp_col::Ptr{Cvoid} = C_NULL; f_sp_val::Ptr{Cvoid} = C_NULL; f_sp_nnz::Int64 = 0
+    # f = SparseGLM (BZ_F_SPARSE_GLM) alone: the row loss (BZ_LOSS_*), Huber's delta, the row weights w[f_rows] or C_NULL, the scale
+    f_loss::Int32 = 0; f_loss_delta::Float64 = 0; f_w::Ptr{Cvoid} = C_NULL; f_scale::Float64 = 1
     # c = SparseAffine (BZ_C_SPARSE_AFFINE): A in CSR, 0-based
     c_sp_rowptr::Ptr{Cvoid} = C_NULL; c_sp_col::Ptr{Cvoid} = C_NULL; c_sp_val::Ptr{Cvoid} = C_NULL; c_sp_nnz::Int64 = 0
 end
@@ -158,6 +160,51 @@ function Bazinga.gradient!(dfx, f::SparseLeastSquares, x)
     return sum(r .* r) / 2
 end
 
+"""`SparseGLM(A::SparseMatrixCSC, b, loss; delta = 0, weights = nothing, scale = 1)`: f(x) = sum_i scale w_i l(b_i, a_i'x) with
+`loss` one of :least_squares, :logistic, :huber (delta > 0), :squared_hinge, :poisson (BZ_LOSS_* 0 .. 4); the formulas are those of
+include/bazinga_hip.h.  Labels (+-1), counts (>= 0), delta, the weights (>= 0) and the scale (> 0) are checked here."""
+struct SparseGLM{T} <: Bazinga.ProximableFunction
+    A::SparseMatrixCSC{T,Int}; b::Vector{T}; loss::Int32; delta::Float64; w::Union{Nothing,Vector{T}}; scale::Float64
+    rowptr::Vector{Int64}; col::Vector{Int32}; val::Vector{T}
+    function SparseGLM(A::SparseMatrixCSC{T}, b::Vector{T}, loss::Symbol; delta = 0.0, weights = nothing, scale = 1.0) where {T}
+        code = findfirst(==(loss), (:least_squares, :logistic, :huber, :squared_hinge, :poisson))
+        code === nothing && throw(ArgumentError("unknown loss $loss"))
+        length(b) == size(A, 1) || throw(ArgumentError("one b per row of A"))
+        loss in (:logistic, :squared_hinge) && !all(v -> abs(v) == 1, b) && throw(ArgumentError("labels must be -1 or +1"))
+        loss == :poisson && !all(v -> isfinite(v) && v >= 0, b) && throw(ArgumentError("counts must be finite and >= 0"))
+        loss == :huber && !(isfinite(delta) && delta > 0) && throw(ArgumentError("the huber loss needs delta finite and > 0"))
+        (isfinite(scale) && scale > 0) || throw(ArgumentError("scale must be finite and > 0"))
+        weights === nothing || (length(weights) == length(b) && all(v -> isfinite(v) && v >= 0, weights)) ||
+            throw(ArgumentError("weights must be finite and >= 0, one per row"))
+        At = sparse(A')
+        new{T}(A, b, Int32(code - 1), Float64(delta), weights === nothing ? nothing : Vector{T}(weights), Float64(scale),
+               Int64.(At.colptr .- 1), Int32.(At.rowval .- 1), Vector{T}(At.nzval))
+    end
+end
+function Bazinga.gradient!(dfx, f::SparseGLM{T}, x) where {T}
+    t = f.A * x; b = f.b
+    w = f.w === nothing ? T(f.scale) : T.(f.scale .* Float64.(f.w))
+    if f.loss == 0
+        v = t .- b; l = v .* v; dl = v
+    elseif f.loss == 1
+        u = b .* t; e = exp.(.-abs.(u))
+        l = ifelse.(u .< 0, .-u, zero(T)) .+ log1p.(e)
+        dl = .-b .* ifelse.(u .>= 0, e ./ (one(T) .+ e), one(T) ./ (one(T) .+ e))
+    elseif f.loss == 2
+        v = t .- b; d = T(f.delta); a = ifelse.(v .< 0, .-v, v); inside = a .<= d
+        l = ifelse.(inside, T(0.5) .* v .* v, d .* (a .- T(0.5) * d))
+        dl = ifelse.(inside, v, ifelse.(v .> 0, d, ifelse.(v .< 0, -d, v)))
+    elseif f.loss == 3
+        h = one(T) .- b .* t; off = h .<= 0
+        l = ifelse.(off, zero(T), T(0.5) .* h .* h); dl = ifelse.(off, zero(T), .-b .* h)
+    else
+        e = exp.(t); bt = ifelse.(b .== 0, zero(T), b .* t)
+        l = ifelse.(e .< T(Inf), e .- bt, e); dl = e .- b
+    end
+    dfx .= f.A' * (w .* dl)
+    return f.loss == 0 ? sum(w .* l) / 2 : sum(w .* l)
+end
+
 """`SparseLogistic(A::SparseMatrixCSC, labels)`: f(x) = sum_i log(1 + exp(-b_i a_i'x)), the logistic loss of a sparse design
 matrix that is never densified, labels b in {-1, +1} (checked here).  The plain sum: no 1/2 and no 1/m.  The library takes CSR:
 the CSC arrays of `sparse(A')` ARE the CSR arrays of A, made 0-based here."""
@@ -214,6 +261,13 @@ lower_f!(d, f::SparseLeastSquares) = (d.f_kind = 7; d.f_rows = length(f.b); d.f_
 lower_f!(d, f::SparseLogistic) = (d.f_kind = 8; d.f_rows = length(f.b); d.f_sp_rowptr = pointer(f.rowptr);
                                   d.f_sp_col = pointer(f.col); d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val);
                                   d.f_b = pointer(f.b); nothing)
+function lower_f!(d, f::SparseGLM)
+    d.f_kind = 9; d.f_rows = length(f.b); d.f_sp_rowptr = pointer(f.rowptr); d.f_sp_col = pointer(f.col)
+    d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val); d.f_b = pointer(f.b)
+    d.f_loss = f.loss; d.f_loss_delta = f.delta; d.f_scale = f.scale
+    d.f_w = f.w === nothing ? C_NULL : pointer(f.w)
+    return nothing
+end
 lower_f!(d, f) = :generic
 
 lower_g!(d, g::Bazinga.Zero) = (d.g_kind = 0)
