@@ -60,7 +60,7 @@ class ProblemDesc(C.Structure):
         ("f_q", C.c_void_p), ("f_b", C.c_void_p), ("f_grid_nx", C.c_int64), ("f_grid_ny", C.c_int64),
         ("f_A", C.c_void_p), ("f_rows", C.c_int64),
         ("g_lambda", C.c_double), ("g_p", C.c_double), ("g_u", C.c_void_p), ("g_lo", C.c_double), ("g_hi", C.c_double),
-        ("g_lo_vec", C.c_void_p), ("g_hi_vec", C.c_void_p),
+        ("g_lo_vec", C.c_void_p), ("g_hi_vec", C.c_void_p), ("g_lambda_vec", C.c_void_p),
         ("c_A", C.c_void_p), ("c_b", C.c_void_p),
         ("D_lo", C.c_double), ("D_hi", C.c_double), ("D_lo_vec", C.c_void_p), ("D_hi_vec", C.c_void_p),
         ("cb_user", C.c_void_p), ("cb_f_gradient", F_GRADIENT_FN), ("cb_g_prox", G_PROX_FN),
@@ -127,6 +127,7 @@ SIGNATURES = {
     "bz_problem_destroy": (None, [_vp]),
     "bz_panoc_default_opts": (None, [_P(PanocOpts)]),
     "bz_problem_set_multipliers": (C.c_int, [_vp, _vp, _vp]),
+    "bz_problem_set_g_lambda": (C.c_int, [_vp, C.c_double, _vp]),
     "bz_panoc_solve": (C.c_int, [_vp, _P(PanocOpts), _vp, _vp, _P(PanocStats)]),
     "bz_panoc_begin": (C.c_int, [_vp, _P(PanocOpts), _vp]),
     "bz_problem_halo_export": (C.c_int, [_vp, _vp]),

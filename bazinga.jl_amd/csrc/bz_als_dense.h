@@ -108,7 +108,8 @@ k_fbstep_lifted(const T* __restrict__ xs, const T* __restrict__ g, T gamma, Elem
                 T y = px.v[e];
                 if (g) { T t = gamma * pg.v[e]; y = px.v[e] - t; }
                 T gterm;
-                const T a = prox_elem<T, LP>(P.g_kind, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+                const T a = prox_elem<T, LP>(P.g_kind, y, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+                gterm = gterm_elem(P, L, e, gterm);
                 const T r = px.v[e] - a;
                 pz.v[e] = a; pr.v[e] = r;
                 if (e < cnt) {

@@ -13,6 +13,7 @@ struct bz_problem {
     bz::SolverBase* s;
     int dtype;
     int device;       // kept here so destroy never dereferences a context that was freed first
+    bool stepping;    // between bz_panoc_begin and bz_panoc_finish (bz_problem_set_g_lambda is refused there)
 };
 
 namespace {
@@ -157,7 +158,7 @@ int bz_problem_create(bz_ctx* ctx, const bz_problem_desc* d, bz_problem** out) {
     return guard([&] {
         need(ctx, "ctx"); need(d, "desc"); need(out, "out");
         BZ_HIP(hipSetDevice(ctx->c.device));
-        auto* p = new bz_problem{ctx, nullptr, d->dtype, ctx->c.device};
+        auto* p = new bz_problem{ctx, nullptr, d->dtype, ctx->c.device, false};
         try {
             p->s = bz::make_solver(&ctx->c, *d);
         } catch (...) {
@@ -198,16 +199,25 @@ int bz_problem_set_multipliers(bz_problem* p, const void* mu, const void* y) {
     return guard([&] { need(p, "problem"); on_device(p->device); need(mu, "mu"); need(y, "y"); p->s->set_multipliers(mu, y); });
 }
 
+int bz_problem_set_g_lambda(bz_problem* p, double lambda, const void* lambda_vec) {
+    return guard([&] {
+        need(p, "problem"); on_device(p->device);
+        if (p->stepping) throw bz::Error(BZ_ERR_STATE, "bz_problem_set_g_lambda between bz_panoc_begin and bz_panoc_finish");
+        p->s->set_g_lambda(lambda, lambda_vec);
+    });
+}
+
 int bz_panoc_solve(bz_problem* p, const bz_panoc_opts* o, const void* x0, void* x_out,
                    bz_panoc_stats* st) {
     return guard([&] {
         need(p, "problem"); on_device(p->device); need(o, "opts"); need(x0, "x0"); need(x_out, "x_out");
+        p->stepping = false;      // (a whole solve: it begins and finishes by itself)
         p->s->solve(*o, x0, x_out, st);
     });
 }
 
 int bz_panoc_begin(bz_problem* p, const bz_panoc_opts* o, const void* x0) {
-    return guard([&] { need(p, "problem"); on_device(p->device); need(o, "opts"); need(x0, "x0"); p->s->begin(*o, x0); });
+    return guard([&] { need(p, "problem"); on_device(p->device); need(o, "opts"); need(x0, "x0"); p->s->begin(*o, x0); p->stepping = true; });
 }
 int bz_panoc_step(bz_problem* p) {
     return guard([&] { need(p, "problem"); on_device(p->device); p->s->step(); });
@@ -220,7 +230,7 @@ int bz_panoc_steps(bz_problem* p, int64_t k) {
     });
 }
 int bz_panoc_finish(bz_problem* p, void* x_out, bz_panoc_stats* st) {
-    return guard([&] { need(p, "problem"); on_device(p->device); p->s->finish(x_out, st); });
+    return guard([&] { need(p, "problem"); on_device(p->device); p->s->finish(x_out, st); p->stepping = false; });
 }
 int bz_panoc_scalars(bz_problem* p, double* out16) {
     return guard([&] { need(p, "problem"); on_device(p->device); need(out16, "out16"); p->s->scalars(out16); });
@@ -234,6 +244,7 @@ int bz_alps_solve(bz_problem* p, const bz_alps_opts* ao, const bz_panoc_opts* po
     return guard([&] {
         need(p, "problem"); on_device(p->device); need(ao, "alps opts"); need(po, "panoc opts");
         need(x0, "x0"); need(y0, "y0"); need(x, "x"); need(y, "y"); need(s, "s"); need(mu, "mu");
+        p->stepping = false;      // (a whole solve: it begins and finishes by itself)
         p->s->alps(*ao, *po, x0, y0, x, y, s, mu, st);
     });
 }
@@ -243,6 +254,7 @@ int bz_als_solve(bz_problem* p, const bz_alps_opts* ao, const bz_panoc_opts* po,
     return guard([&] {
         need(p, "problem"); on_device(p->device); need(ao, "alps opts"); need(po, "panoc opts");
         need(x0, "x0"); need(y0, "y0"); need(x, "x"); need(y, "y"); need(s, "s"); need(mu, "mu");
+        p->stepping = false;      // (a whole solve: it begins and finishes by itself)
         p->s->als(*ao, *po, x0, y0, x, y, s, mu, st);
     });
 }

@@ -57,7 +57,12 @@ template <class T> struct ElemParams {
     const T* muy;
     T g_lambda;
     T g_p;                 // NormLpPower*: exponent p in (0,1); g_lambda holds alpha
-    const T* g_u;
+    union {                // one per-element stream of g, by kind (the struct, and with it every kernel's argument block, keeps its size)
+        const T* g_u;          // NormL1Box / NormL0Box / NormLpPowerBox: u[n]
+        const T* g_lambda_vec; // NormL1: lambda[n], g = sum lambda_i |x_i| (then g_lambda is unused), or null.  Read through
+                               // lambda_vec() by the run-time-kind kernels only (load_params puts it into ElemLoads::gu); the
+                               // host keeps a problem that has it away from every compile-time form
+    };
     T g_lo, g_hi;
     const T* g_lo_vec;
     const T* g_hi_vec;
@@ -65,6 +70,7 @@ template <class T> struct ElemParams {
     const T* D_lo_vec;
     const T* D_hi_vec;
     T mu_uniform;          // the value of every mu[i] when the penalties are uniform (k_muy's probe), else unused
+    __host__ __device__ const T* lambda_vec() const { return g_kind == BZ_G_NORM_L1 ? g_lambda_vec : nullptr; }
 };
 
 // ---------------------------------------------------------------------------
@@ -560,10 +566,23 @@ __device__ __forceinline__ T prox_elem(int g_kind, T y, T gl, T u, T lo, T hi, T
 }
 
 template <class T> struct ElemLoads {
-    Pack<T> q, b, mu, muy, dlo, dhi, gu, glo, ghi;
+    Pack<T> q, b, mu, muy, dlo, dhi, gu, glo, ghi;      // gu: u of the box kinds, or lambda of NormL1 with a vector lambda
 };
 
-template <class T, bool NT = false>
+// NormL1 with a per-element lambda (ProximalOperators.NormL1 with an array): gamma*lambda and the g term of element e.
+// The test on the pointer is uniform over the launch; without the vector these return the launch-wide gl and the
+// |z| that the host multiplies by lambda, with it gamma*lambda_e formed in T and lambda_e*|z|, which the host sums as is.
+template <class T>
+__device__ __forceinline__ T gl_elem(const ElemParams<T>& P, const ElemLoads<T>& L, int e, T gamma, T gl) {
+    return P.lambda_vec() ? gamma * L.gu.v[e] : gl;
+}
+template <class T>
+__device__ __forceinline__ T gterm_elem(const ElemParams<T>& P, const ElemLoads<T>& L, int e, T gterm) {
+    return P.lambda_vec() ? L.gu.v[e] * gterm : gterm;
+}
+
+// LAMV = false: a caller whose kinds are compile-time facts (it never holds NormL1's vector lambda)
+template <class T, bool NT = false, bool LAMV = true>
 __device__ __forceinline__ void load_params(const ElemParams<T>& P, int64_t i0, int cnt,
                                             ElemLoads<T>& L, bool need_f, bool need_al,
                                             bool need_g) {
@@ -578,6 +597,7 @@ __device__ __forceinline__ void load_params(const ElemParams<T>& P, int64_t i0, 
     if (need_g) {
         L.gu = (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX || P.g_kind == BZ_G_NORM_LP_BOX)
                    ? ldp<T, NT>(P.g_u, i0, cnt) : splat(T(0));
+        if constexpr (LAMV) { if (P.lambda_vec()) L.gu = ldp<T, NT>(P.g_lambda_vec, i0, cnt); }
         L.glo = P.g_lo_vec ? ldp<T, NT>(P.g_lo_vec, i0, cnt) : splat(P.g_lo);
         L.ghi = P.g_hi_vec ? ldp<T, NT>(P.g_hi_vec, i0, cnt) : splat(P.g_hi);
     }
@@ -775,7 +795,8 @@ k_begin_fb(const T* __restrict__ x, const T* __restrict__ gx, T gamma, ElemParam
         for (int e = 0; e < PackN<T>::N; ++e) {
             T t = gamma * pg.v[e];
             T y = px.v[e] - t;
-            T zz = prox_elem<T, false>(P.g_kind, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm[e], P.g_p);
+            T zz = prox_elem<T, false>(P.g_kind, y, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm[e], P.g_p);
+            gterm[e] = gterm_elem(P, L, e, gterm[e]);
             pz.v[e] = zz; pr.v[e] = px.v[e] - zz;
         }
 #pragma unroll
@@ -820,7 +841,7 @@ k_zres_elem(const T* __restrict__ x, ElemParams<T> P, T gamma, T* __restrict__ z
             T t = gamma * o.grad;
             T y = px.v[e] - t;
             T gterm;
-            T zz = prox_elem<T, false>(P.g_kind, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+            T zz = prox_elem<T, false>(P.g_kind, y, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
             pz.v[e] = zz; pr.v[e] = px.v[e] - zz;
         }
         st(z, i0, cnt, pz);
@@ -927,7 +948,8 @@ k_stencil_fb(const T* __restrict__ x, ElemParams<T> P, int64_t nx, int64_t ny, T
             T t = gamma * pg.v[e];
             T y = xc.v[e] - t;
             T gterm;
-            T zz = prox_elem(P.g_kind, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+            T zz = prox_elem(P.g_kind, y, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+            gterm = gterm_elem(P, L, e, gterm);
             T r = xc.v[e] - zz;
             pz.v[e] = zz; pr.v[e] = r;
             if (e < cnt) {
@@ -2157,7 +2179,8 @@ k_fbstep(const T* __restrict__ x, const T* __restrict__ g, T gamma, ElemParams<T
             T y = px.v[e];
             if (g) { T t = gamma * pg.v[e]; y = px.v[e] - t; }
             T gterm;
-            T zz = prox_elem<T, LP>(P.g_kind, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+            T zz = prox_elem<T, LP>(P.g_kind, y, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+            gterm = gterm_elem(P, L, e, gterm);
             T r = px.v[e] - zz;
             pz.v[e] = zz; pr.v[e] = r;
             if (e < cnt) {
@@ -2239,7 +2262,8 @@ k_fbstep_slack(const T* __restrict__ xs, const T* __restrict__ g, T gamma, ElemP
             T yx = px.v[e], ys = ps.v[e];
             if (g) { T t = gamma * pgx.v[e]; yx = px.v[e] - t; T u = gamma * pgs.v[e]; ys = ps.v[e] - u; }
             T gterm;
-            const T a = prox_elem<T, LP>(P.g_kind, yx, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+            const T a = prox_elem<T, LP>(P.g_kind, yx, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+            gterm = gterm_elem(P, L, e, gterm);
             const T b = proj_D(P.D_kind, ys, dlo.v[e], dhi.v[e]);
             const T r1 = px.v[e] - a, r2 = ps.v[e] - b;
             zx.v[e] = a; zs.v[e] = b; rx.v[e] = r1; rs.v[e] = r2;
@@ -2370,7 +2394,8 @@ k_fused_sep(TailArgs<T> a, const T* __restrict__ x, const T* __restrict__ res_pr
                                   L.muy.v[e], L.dlo.v[e], L.dhi.v[e], pxd.v[e ^ 1] + L.muy.v[e ^ 1], e & 1);
             T t = gamma * o1.grad;
             T y = xd - t;
-            T zz = prox_elem(P.g_kind, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], pgt.v[e]);
+            T zz = prox_elem(P.g_kind, y, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], pgt.v[e]);
+            pgt.v[e] = gterm_elem(P, L, e, pgt.v[e]);
             pz.v[e] = zz; pr.v[e] = xd - zz;
             pg1.v[e] = o1.grad; f1[e] = o1.fterm; p1[e] = o1.pterm;
         }
@@ -2715,7 +2740,8 @@ k_dense_head(DenseHeadArgs<T, MM> A, ElemParams<T> P) {
                 T t = A.gamma * g.v[e];
                 T y = xd.v[e] - t;
                 T gterm;
-                T zz = prox_elem<T, false>(P.g_kind, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+                T zz = prox_elem<T, false>(P.g_kind, y, gl_elem(P, L, e, A.gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm, P.g_p);
+                gterm = gterm_elem(P, L, e, gterm);
                 T r = xd.v[e] - zz;
                 zp.v[e] = zz; rp.v[e] = r;
                 if (e < cnt) {
@@ -2939,7 +2965,7 @@ k_pairs_from_iterates(SnapVecs<T, MM> V, int m, ElemParams<T> P, T* __restrict__
             for (int e = 0; e < PackN<T>::N; ++e) {
                 T zz;
                 const T gi = (T)V.gam[i];
-                rh[i].v[e] = resid_elem<T>(P.f_kind, P.D_kind, P.g_kind, xh[i].v[e], L, e, gi, gi * P.g_lambda, zz, false,
+                rh[i].v[e] = resid_elem<T>(P.f_kind, P.D_kind, P.g_kind, xh[i].v[e], L, e, gi, gl_elem(P, L, e, gi, gi * P.g_lambda), zz, false,
                                            T(0), xh[i].v[e ^ 1]);
                 if (i == MM) pz.v[e] = zz;
             }
@@ -3307,7 +3333,7 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
             } else {
                 // run-time kinds (generic stored-pair body; the ragged last chunk of a family kernel, whose kinds
                 // are those of P by construction)
-                load_params<T, NT>(P, i0, cnt, L, true, true, true);
+                load_params<T, NT, !FAMILY && !SPEC>(P, i0, cnt, L, true, true, true);
                 if (FAMILY && uni >= 1) L.mu = splat(P.mu_uniform);
                 if (FAMILY && uni >= 2) L.muy = splat(T(0));
             }
@@ -3364,7 +3390,10 @@ k_fused_compact(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ x
                                   pxd.v[e ^ 1] + L.muy.v[e ^ 1], e & 1, UDIV, rmu.v[e]);
             T t = gamma * o1.grad;
             T y = xd - t;
-            T zz = prox_elem(gk, y, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], pgt.v[e]);
+            T gle = gl;                        // (the generic stored-pair body alone may hold a vector lambda)
+            if constexpr (!FAMILY && !SPEC) gle = gl_elem(P, L, e, gamma, gl);
+            T zz = prox_elem(gk, y, gle, L.gu.v[e], L.glo.v[e], L.ghi.v[e], pgt.v[e]);
+            if constexpr (!FAMILY && !SPEC) pgt.v[e] = gterm_elem(P, L, e, pgt.v[e]);
             pz.v[e] = zz; pr.v[e] = xd - zz;
             pg1.v[e] = o1.grad; f1[e] = o1.fterm; p1[e] = o1.pterm;
         }
@@ -3625,7 +3654,8 @@ k_fused_slack(CompactVecs<T, MM> V, CompactCoef<MM> C, const T* __restrict__ xs,
             T u = gamma * o1.gs;
             const T ys = sd - u;
             T gterm;
-            const T a = prox_elem(P.g_kind, yx, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+            const T a = prox_elem(P.g_kind, yx, gl_elem(P, L, e, gamma, gl), L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+            gterm = gterm_elem(P, L, e, gterm);
             const T b = proj_D(P.D_kind, ys, dlo.v[e], dhi.v[e]);
             const T r1 = xd - a, r2 = sd - b;
             pz[0].v[e] = a; pz[1].v[e] = b; pr[0].v[e] = r1; pr[1].v[e] = r2;
@@ -3707,14 +3737,14 @@ template <class T, int MM> struct SlackIterates {
 };
 template <class T>
 __device__ __forceinline__ void slack_resid(const ElemParams<T>& P, T x, T sv, const ElemLoads<T>& L, int e, T dlo, T dhi, T yv,
-                                            T gam, T& rx, T& rs, T& zx, T& zs, bool udiv = false, T rmu = T(0)) {
+                                            T gam, T lam, T& rx, T& rs, T& zx, T& zs, bool udiv = false, T rmu = T(0)) {
     const SlackOut<T> o = slack_elem(P.f_kind, x, sv, L.q.v[e], L.b.v[e], L.mu.v[e], L.muy.v[e], yv, udiv, rmu);
     T t = gam * o.gx;
     const T yx = x - t;
     T u = gam * o.gs;
     const T ys = sv - u;
     T gterm;
-    zx = prox_elem(P.g_kind, yx, gam * P.g_lambda, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+    zx = prox_elem(P.g_kind, yx, gam * lam, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
     zs = proj_D(P.D_kind, ys, dlo, dhi);
     rx = x - zx;
     rs = sv - zs;
@@ -3811,7 +3841,9 @@ k_fused_slack_xr(SlackIterates<T, MM> V, CompactCoef<MM> C, ElemParams<T> P, con
 #pragma unroll
                 for (int e = 0; e < N; ++e) {
                     T zx, zs;
-                    slack_resid(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, rh[0][i].v[e], rh[1][i].v[e], zx, zs, udiv, rmu);
+                    T lam = P.g_lambda;                    // (the run-time form alone may hold a vector lambda)
+                    if constexpr (UNI < 0) lam = P.lambda_vec() ? L.gu.v[e] : P.g_lambda;
+                    slack_resid(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, lam, rh[0][i].v[e], rh[1][i].v[e], zx, zs, udiv, rmu);
                 }
             }
         Pack<T> px[2], prp[2], ps[2][MM], py[2][MM], d[2];
@@ -3846,7 +3878,10 @@ k_fused_slack_xr(SlackIterates<T, MM> V, CompactCoef<MM> C, ElemParams<T> P, con
             T u = gamma * o1.gs;
             const T ys = sd - u;
             T gterm;
-            const T a = prox_elem(P.g_kind, yx, gl, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+            T gle = gl;                                    // (the run-time form alone may hold a vector lambda)
+            if constexpr (UNI < 0) gle = gl_elem(P, L, e, gamma, gl);
+            const T a = prox_elem(P.g_kind, yx, gle, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+            if constexpr (UNI < 0) gterm = gterm_elem(P, L, e, gterm);
             const T b = proj_D(P.D_kind, ys, dlo.v[e], dhi.v[e]);
             const T r1 = xd - a, r2 = sd - b;
             pz[0].v[e] = a; pz[1].v[e] = b;
@@ -3960,7 +3995,7 @@ k_pairs_from_iterates_slack(SnapVecs<T, MM> V, int m, ElemParams<T> P, const T* 
 #pragma unroll
             for (int e = 0; e < N; ++e) {
                 T zx, zs;
-                slack_resid(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, rh[0][i].v[e], rh[1][i].v[e], zx, zs);
+                slack_resid(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, P.lambda_vec() ? L.gu.v[e] : P.g_lambda, rh[0][i].v[e], rh[1][i].v[e], zx, zs);
                 if (i == MM) { pz[0].v[e] = zx; pz[1].v[e] = zs; }
             }
         }

@@ -334,8 +334,12 @@ template <class T> class Solver final : public SolverBase {
                 throw Error(BZ_ERR_UNSUPPORTED, "pairwise D sets need c = Identity, an element-wise or dense f and no slack");
             if (ny % 2 != 0) throw Error(BZ_ERR_ARG, "pairwise D sets need an even number of constraints");
         }
+        // (a per-element lambda: NormL1 alone — the box kinds use the one spare per-element g stream for u, and the
+        // reference's NormL1Nonneg takes a number; g_lambda is ignored beside it)
+        if (d.g_lambda_vec && d.g_kind != BZ_G_NORM_L1)
+            throw Error(BZ_ERR_ARG, "g_lambda_vec (a per-element lambda) is taken by NormL1 alone");
         if ((d.g_kind == BZ_G_NORM_L1 || d.g_kind == BZ_G_NORM_L1_NONNEG ||
-             d.g_kind == BZ_G_NORM_L1_BOX || d.g_kind == BZ_G_NORM_L0_BOX) && d.g_lambda < 0)
+             d.g_kind == BZ_G_NORM_L1_BOX || d.g_kind == BZ_G_NORM_L0_BOX) && d.g_lambda < 0 && !d.g_lambda_vec)
             throw Error(BZ_ERR_ARG, "parameter lambda must be nonnegative");
         BZ_HIP(hipSetDevice(ctx->device));
         const int64_t nchunks = (n + PackN<T>::N - 1) / PackN<T>::N;
@@ -443,6 +447,12 @@ template <class T> class Solver final : public SolverBase {
             P.b = b_.p;
         }
         P.g_lambda = (T)d.g_lambda;
+        if (d.g_lambda_vec) {
+            // (the x half in the slack form: the s half has no g)
+            std::vector<T> lam;
+            read_lambda_vec(d.g_lambda_vec, lam);
+            upload(glam_, lam.data(), nx); P.g_lambda_vec = glam_.p;      // (shares its slot with g_u: read through P.lambda_vec())
+        }
         P.g_p = (T)d.g_p;
         lp_g = d.g_kind == BZ_G_NORM_LP_NONNEG || d.g_kind == BZ_G_NORM_LP_BOX;
         if (lp_g) {
@@ -511,6 +521,34 @@ template <class T> class Solver final : public SolverBase {
     }
 
     // ------------------------------------------------------------------ API
+    // lambda of a live problem, between solves.  Number <-> vector would change which kernel forms the problem runs: that
+    // stays a creation-time decision.  Every launch takes P as it is when it is made and g_value reads P, so nothing else
+    // holds a copy — but a one-pass launch made early for an iteration that never came, which is recalled here.
+    void set_g_lambda(double lam, const void* lam_vec) override {
+        const int k = desc.g_kind;
+        if (!(k == BZ_G_NORM_L1 || k == BZ_G_NORM_L1_NONNEG || k == BZ_G_NORM_L1_BOX || k == BZ_G_NORM_L0_BOX))
+            throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: g must be NormL1, NormL1Nonneg, NormL1Box or NormL0Box");
+        if (lam_vec && !P.lambda_vec())
+            throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: the problem was created with a number lambda (NormL1 takes a vector at bz_problem_create only)");
+        if (!lam_vec && P.lambda_vec())
+            throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: the problem was created with a vector lambda of NormL1: pass a vector");
+        std::vector<T> h;
+        if (lam_vec) read_lambda_vec(lam_vec, h);
+        else if (lam < 0) throw Error(BZ_ERR_ARG, "parameter lambda must be nonnegative");
+        gate_abort();
+        BZ_HIP(hipStreamSynchronize(ctx->stream));
+        if (lam_vec) copy_in(glam_.p, h.data(), nx);
+        else { P.g_lambda = (T)lam; desc.g_lambda = lam; }
+    }
+    // NormL1's per-element lambda on a host copy: every entry finite and >= 0 (zeros are the unpenalised coefficients)
+    void read_lambda_vec(const void* src, std::vector<T>& h) {
+        h.resize((size_t)nx);
+        BZ_HIP(hipMemcpy(h.data(), src, h.size() * sizeof(T), hipMemcpyDefault));
+        for (int64_t i = 0; i < nx; ++i)
+            if (!(std::isfinite((double)h[i]) && h[i] >= T(0)))
+                throw Error(BZ_ERR_ARG, "NormL1: every entry of the vector lambda must be finite and >= 0 (entry " + std::to_string(i) + ")");
+    }
+
     void set_multipliers(const void* mu, const void* y) override {
         copy_in(mu_.p, mu, ny);
         copy_in(ymul_.p, y, ny);
@@ -877,7 +915,7 @@ template <class T> class Solver final : public SolverBase {
         gs = (int)std::min<int64_t>(PSTRIDE / 2, std::max<int64_t>(1, ((ny_ + N - 1) / N + BLOCK - 1) / BLOCK));
     }
     ElemParams<T> P;
-    DBuf<T> q_, b_, gu_, glo_, ghi_, dlo_, dhi_, mu_, muy_, ymul_, sproj_;
+    DBuf<T> q_, b_, gu_, glam_, glo_, ghi_, dlo_, dhi_, mu_, muy_, ymul_, sproj_;
     // x lives in a ring long enough to keep the last CM+1 iterates alive (history as iterates, see xr_run_): CM+1
     // snapshots + the slot being written (+ one more slot for the tau blend); res in two slots, the current and the next
     static constexpr int NXR = CM + 3, NRR = 2;
@@ -1307,7 +1345,7 @@ template <class T> class Solver final : public SolverBase {
         if (need_f && P.f_kind == BZ_F_DIAG_QUADRATIC) k += 2;
         if (need_al) k += 2 - (P.uni >= 1 ? 1 : 0) - (P.uni >= 2 ? 1 : 0) + (P.D_lo_vec ? 1 : 0) + (P.D_hi_vec ? 1 : 0);
         if (need_g) k += (P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX || P.g_kind == BZ_G_NORM_LP_BOX) ? 1 : 0) +
-                         (P.g_lo_vec ? 1 : 0) + (P.g_hi_vec ? 1 : 0);
+                         (P.lambda_vec() ? 1 : 0) + (P.g_lo_vec ? 1 : 0) + (P.g_hi_vec ? 1 : 0);
         return k;
     }
     void account(int cat, ProfRec* r) {
@@ -1817,6 +1855,7 @@ template <class T> class Solver final : public SolverBase {
         switch (desc.g_kind) {
         case BZ_G_NORM_L1: case BZ_G_NORM_L1_NONNEG: case BZ_G_NORM_L1_BOX: case BZ_G_NORM_L0_BOX:
         case BZ_G_NORM_LP_NONNEG: case BZ_G_NORM_LP_BOX:
+            if (P.lambda_vec()) return T(gsum);      // (the kernels summed lambda_i |z_i|)
             return P.g_lambda * T(gsum);
         case BZ_G_CALLBACK: return T(gsum);      // the callback returned g(z) itself
         default: return T(0);
@@ -2378,6 +2417,7 @@ template <class T> class Solver final : public SolverBase {
     // element-wise f, any element-wise g but the Newton / L0 kinds, any D
     int fused_family() const {
         if (desc.c_kind != BZ_C_IDENTITY || slack || ny != n || lp_g) return -1;
+        if (P.lambda_vec()) return -1;      // (a per-element lambda: no family for it, the stored-pair forms)
         int fk, gk, dk;
         switch (desc.f_kind) {
         case BZ_F_ZERO: fk = FAM_F_ZERO; break;
@@ -3015,7 +3055,7 @@ template <class T> class Solver final : public SolverBase {
         // pipelined like the headline kernel, 256 VGPRs + spill AGPRs: one workgroup per CU there too)
         const bool slack_fast = slack && xr == 2 && env_.slackfast && m_now == CM && desc.f_kind == BZ_F_DIAG_QUADRATIC &&
                                 pstreams(false, true, true) == 2 - std::min(2, (int)P.uni) &&
-                                !(P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX));
+                                !(P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX)) && !P.lambda_vec();
         // ... with the kinds fixed too (g = NormL1, D = Box: the ALS form of cfg 2), one pack of loads ahead
         const bool slack_hk = slack_fast && env_.slackkind && P.g_kind == BZ_G_NORM_L1 && P.D_kind == BZ_D_BOX;
         if (xr == 2 && env_.gfc <= 0 && (!slack || slack_hk)) gfc = std::min(grid, std::max(1, num_cus));

@@ -159,6 +159,16 @@ class Problem:
         mu, y = self._in(mu, self.ny), self._in(y, self.ny)
         self._call(L.load().bz_problem_set_multipliers(self._h, mu.ctypes.data, y.ctypes.data))
 
+    def set_g_lambda(self, lam):
+        """lambda of g = NormL1 / NormL1Nonneg / NormL1Box / NormL0Box between solves, without a new problem (a path of
+        fits on one upload of the matrices): a number for a problem created with a number, a vector of length n for one
+        created with NormL1(array)."""
+        if np.ndim(lam) == 0:
+            self._call(L.load().bz_problem_set_g_lambda(self._h, float(lam), None))
+        else:
+            v = self._in(lam, self.nx)
+            self._call(L.load().bz_problem_set_g_lambda(self._h, 0.0, v.ctypes.data))
+
     def panoc_solve(self, opts: L.PanocOpts, x0):
         x0 = self._in(x0, self.n)
         out = np.empty(self.n, self.dtype)

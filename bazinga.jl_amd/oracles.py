@@ -529,17 +529,35 @@ class IndFree(ProximableFunction):
 
 
 class NormL1(ProximableFunction):
-    """ProximalOperators.NormL1(lambda) (test_verbose.jl:23, demo/basispursuit.jl:63)."""
+    """ProximalOperators.NormL1(lambda) (test_verbose.jl:23, demo/basispursuit.jl:63).  lambda is a number, or a 1-D
+    array of per-element weights, g(x) = sum lambda_i |x_i| (finite, >= 0; a zero leaves its coefficient unpenalised)."""
 
     def __init__(self, lam=1.0):
-        if lam < 0:
-            raise ValueError("parameter λ must be nonnegative")
-        self.lam = float(lam)
+        if np.ndim(lam) == 0:
+            if lam < 0:
+                raise ValueError("parameter λ must be nonnegative")
+            self.lam = float(lam)
+            return
+        lam = np.array(lam, dtype=np.float64)
+        if lam.ndim != 1:
+            raise ValueError("parameter λ must be a number or a 1-D array")
+        if not np.all(np.isfinite(lam) & (lam >= 0)):
+            raise ValueError("parameter λ must have finite, nonnegative entries")
+        self.lam = lam
+
+    def __call__(self, x):
+        return np.sum(np.abs(self.lam * x)) if np.ndim(self.lam) else self.lam * np.sum(np.abs(x))
 
     def prox(self, z, x, gamma):
-        gl = x.dtype.type(gamma * self.lam)
+        T = x.dtype.type
+        if np.ndim(self.lam) == 0:
+            gl = T(gamma * self.lam)
+            z[...] = x + np.where(x <= -gl, gl, np.where(x >= gl, -gl, -x))
+            return T(self.lam) * np.sum(np.abs(z))
+        lam = np.asarray(self.lam, dtype=x.dtype)
+        gl = T(gamma) * lam
         z[...] = x + np.where(x <= -gl, gl, np.where(x >= gl, -gl, -x))
-        return x.dtype.type(self.lam) * np.sum(np.abs(z))
+        return np.sum(lam * np.abs(z))
 
 
 class NormL1Nonneg(ProximableFunction):
@@ -1038,7 +1056,11 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
     if isinstance(g, (Zero, IndFree)):
         d.g_kind = L.BZ_G_ZERO
     elif isinstance(g, NormL1):
-        d.g_kind, d.g_lambda = L.BZ_G_NORM_L1, g.lam
+        d.g_kind = L.BZ_G_NORM_L1
+        if np.ndim(g.lam) == 0:
+            d.g_lambda = g.lam
+        else:
+            d.g_lambda_vec = ptr(_vec(g.lam, dtype, n, "λ"))
     elif isinstance(g, NormL1Nonneg):
         d.g_kind, d.g_lambda = L.BZ_G_NORM_L1_NONNEG, g.lam
     elif isinstance(g, NormL1Box):

@@ -234,6 +234,9 @@ typedef struct {
     double      g_lo, g_hi;        /* IND_BOX scalar bounds                           */
     const void* g_lo_vec;          /* IND_BOX vector bounds (or NULL)                 */
     const void* g_hi_vec;
+    const void* g_lambda_vec;      /* NORM_L1 alone: lambda[n] >= 0 (finite; zeros allowed: an unpenalised coefficient), g(x) =
+                                      sum lambda_i |x_i|, or NULL; g_lambda is ignored beside it.  In the slack form n entries,
+                                      the x half.  Any other g kind with a vector: BZ_ERR_ARG                                */
     /* c */
     const void* c_A;               /* DENSE_AFFINE: A[ny][n] row-major                */
     const void* c_b;               /* DENSE_AFFINE: b[ny]                             */
@@ -392,6 +395,13 @@ typedef struct {
 /* Multipliers/penalties of the current subproblem:  AugLagUpdate!(alFun, mu, y)
  * (src/utilities/auglagfun.jl:91-101).  Returns BZ_ERR_MU if any mu <= 0.           */
 int bz_problem_set_multipliers(bz_problem* p, const void* mu, const void* y);
+
+/* lambda of a live problem, between solves (a path of Lasso fits on one upload of the matrices): g NORM_L1, NORM_L1_NONNEG,
+ * NORM_L1_BOX or NORM_L0_BOX.  A problem created with a number takes lambda (>= 0) and lambda_vec == NULL; one created
+ * with g_lambda_vec takes a non-NULL lambda_vec[n], validated as at creation, which overwrites the device copy (lambda is
+ * ignored).  Number <-> vector would change the kernel forms the problem runs and stays a creation-time decision:
+ * BZ_ERR_ARG, as for any other g kind.  Between bz_panoc_begin and bz_panoc_finish: BZ_ERR_STATE.                         */
+int bz_problem_set_g_lambda(bz_problem* p, double lambda, const void* lambda_vec);
 
 /* One-shot subsolve.  x_out receives state.z.                                      */
 int bz_panoc_solve(bz_problem* p, const bz_panoc_opts* o, const void* x0,

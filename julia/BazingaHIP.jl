@@ -29,7 +29,7 @@ Base.@kwdef mutable struct ProblemDesc
     f_q::Ptr{Cvoid} = C_NULL; f_b::Ptr{Cvoid} = C_NULL; f_grid_nx::Int64 = 0; f_grid_ny::Int64 = 0
     f_A::Ptr{Cvoid} = C_NULL; f_rows::Int64 = 0
     g_lambda::Float64 = 0; g_p::Float64 = 0; g_u::Ptr{Cvoid} = C_NULL; g_lo::Float64 = 0; g_hi::Float64 = 0
-    g_lo_vec::Ptr{Cvoid} = C_NULL; g_hi_vec::Ptr{Cvoid} = C_NULL
+    g_lo_vec::Ptr{Cvoid} = C_NULL; g_hi_vec::Ptr{Cvoid} = C_NULL; g_lambda_vec::Ptr{Cvoid} = C_NULL
     c_A::Ptr{Cvoid} = C_NULL; c_b::Ptr{Cvoid} = C_NULL
     D_lo::Float64 = 0; D_hi::Float64 = 0; D_lo_vec::Ptr{Cvoid} = C_NULL; D_hi_vec::Ptr{Cvoid} = C_NULL
     # generic oracles (all four kinds BZ_*_CALLBACK): host callbacks, see lower_generic!
@@ -274,6 +274,8 @@ lower_g!(d, g::Bazinga.Zero) = (d.g_kind = 0)
 lower_g!(d, g::ProximalOperators.Zero) = (d.g_kind = 0)
 lower_g!(d, g::ProximalOperators.IndFree) = (d.g_kind = 0)
 lower_g!(d, g::ProximalOperators.NormL1{<:Real}) = (d.g_kind = 1; d.g_lambda = g.lambda)
+# (an array lambda: one weight per element, in the problem's type; the array must stay alive until bz_problem_create returns)
+lower_g!(d, g::ProximalOperators.NormL1{<:AbstractVector}) = (d.g_kind = 1; d.g_lambda_vec = pointer(g.lambda))
 lower_g!(d, g::Bazinga.NormL1Nonneg) = (d.g_kind = 2; d.g_lambda = g.lambda)
 lower_g!(d, g::Bazinga.NormL1Box) = (d.g_kind = 3; d.g_lambda = g.lambda; d.g_u = pointer(g.u))
 lower_g!(d, g::ProximalOperators.IndBox{<:Real,<:Real}) = (d.g_kind = 4; d.g_lo = g.lb; d.g_hi = g.ub)
@@ -395,6 +397,13 @@ mutable struct Problem
         finalizer(p -> ccall((:bz_problem_destroy, lib), Cvoid, (Ptr{Cvoid},), p.h), p)
     end
 end
+
+# lambda of g (NormL1, NormL1Nonneg, NormL1Box, NormL0Box) between solves, on the live problem: a number for a problem
+# lowered from a number, a vector (the problem's type, length n) for one lowered from NormL1 with an array
+set_g_lambda!(p::Problem, lambda::Real) = check(ccall((:bz_problem_set_g_lambda, lib), Cint,
+    (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), p.h, lambda, C_NULL))
+set_g_lambda!(p::Problem, lambda::AbstractVector) = GC.@preserve lambda check(ccall((:bz_problem_set_g_lambda, lib), Cint,
+    (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), p.h, 0.0, pointer(lambda)))
 
 # ---- the subsolver seam: drop-in for ProximalAlgorithms.PANOCplus -----------------------------
 struct PANOCplusHIP

@@ -6,6 +6,10 @@
                                                        # vector and the scale 1 / m) beside kinds 7 and 8 on the same matrix, and
                                                        # each k_spmv_glm_r against k_spmv_ls_r and k_spmv_logit_r
     python tools/bench_sparse_glm.py --case callback   # sparse_glm(5e5, 1e6, 5, "huber"): lowered kind against the callback kinds
+    python tools/bench_sparse_glm.py --case intercept  # the Lasso of `losses` (kind 7) with one more column of ones: g = NormL1 with
+                                                       # a vector lambda that is zero at that column, beside the same matrix with
+                                                       # the number lambda; it/s of both, and every kernel's time from a
+                                                       # rocprofv3 run of each (the prox launches: one more stream of n elements)
 
 Each case prints ONE JSON line and writes it to <out>/sparse_glm_<case>.json.  Per run: warm-up steps, then `repeats` timed calls
 of bz_panoc_steps(K): median, minimum and maximum it/s.  The row kernels share the profile's category 9, so the per-kernel times
@@ -34,11 +38,27 @@ from tools.bench_sparse_ls import ls_bytes                              # noqa: 
 from tools.bench_sparse_qp import HostOnly                              # noqa: E402
 
 KINDS = ("ls", "logit", "huber", "squared_hinge", "poisson", "huber_w")
+INTERCEPT = ("icpt", "icpt_vec")      # the Lasso with a column of ones: a number lambda, a vector lambda with a zero at that column
 MODES = {8: "least_squares", 9: "logistic", 10: "huber", 11: "squared_hinge", 12: "poisson"}      # k_spmv_glm_r's last argument
 
 
 def problem(bz, kind, m, n, k, dtype):
     rest = (bz.NormL1(0.1), bz.IdentityFunction(), bz.FreeSet())
+    if kind in INTERCEPT:
+        d = bz.synth.sparse_glm(m, n, k, "least_squares", dtype)
+        # (one more entry per row, behind the row's own: column n, value 1)
+        lens = np.diff(d["indptr"])
+        indptr = (d["indptr"] + np.arange(m + 1)).astype(np.int64)
+        at = indptr[1:] - 1
+        indices, data = np.empty(d["indices"].shape[0] + m, np.int32), np.empty(d["data"].shape[0] + m, dtype)
+        own = np.ones(indices.shape[0], bool)
+        own[at] = False
+        indices[own], data[own], indices[at], data[at] = d["indices"], d["data"], n, 1.0
+        assert np.array_equal(np.diff(indptr), lens + 1)
+        lam = np.full(n + 1, 0.1)
+        lam[n] = 0.0
+        g = bz.NormL1(lam if kind == "icpt_vec" else 0.1)
+        return bz.SparseLeastSquares(indptr, indices, data, d["b"], n + 1), (g,) + rest[1:]
     if kind in ("ls", "logit"):
         d = bz.synth.sparse_glm(m, n, k, "least_squares" if kind == "ls" else "logistic", dtype)
         cls = bz.SparseLeastSquares if kind == "ls" else bz.SparseLogistic
@@ -85,6 +105,19 @@ def kernel_stats(directory):
                 "std_us": max(v["std_ns"]) / 1e3 if v["std_ns"] else None} for k, v in out.items() if v["calls"]}
 
 
+def all_kernel_stats(directory):
+    """per kernel (template arguments dropped): calls and the average duration (us)"""
+    out = {}
+    for path in glob.glob(os.path.join(directory, "**", "*kernel_stats.csv"), recursive=True):
+        for row in csv.DictReader(open(path)):
+            name = re.sub(r"<.*", "", row.get("Name", "").replace("void bz::", "").replace("bz::", "")).strip()
+            if not name.startswith("k_") or not row.get("Calls"):
+                continue
+            a = out.setdefault(name, {"calls": 0, "total_ns": 0.0})
+            a["calls"] += int(row["Calls"]); a["total_ns"] += float(row.get("TotalDurationNs") or 0.0)
+    return {k: {"calls": v["calls"], "avg_us": v["total_ns"] / v["calls"] / 1e3} for k, v in out.items() if v["calls"]}
+
+
 def worker(args):
     import bazinga_jl_amd as bz
     dt = np.float64
@@ -104,8 +137,8 @@ def worker(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--case", choices=["losses", "callback"])
-    ap.add_argument("--worker", default=None, help="comma-separated kinds of " + ", ".join(KINDS))
+    ap.add_argument("--case", choices=["losses", "callback", "intercept"])
+    ap.add_argument("--worker", default=None, help="comma-separated kinds of " + ", ".join(KINDS + INTERCEPT))
     ap.add_argument("--callback", type=int, default=0)
     ap.add_argument("--m", type=int, default=None)
     ap.add_argument("--n", type=int, default=None)
@@ -170,6 +203,29 @@ def main():
                 res["weight_vector_cost_us"] = hw["avg_us"] - hu["avg_us"]
         else:
             res["per_kernel"] = "rocprofv3 not found: category 9 (the row kernels together) only"
+    elif args.case == "intercept":
+        res = child(cmd(",".join(INTERCEPT)), env, "it/s of " + ", ".join(INTERCEPT))
+        res.update(case="intercept", commit=args.commit or commit_of_tree())
+        res["it_per_s_median"] = {k: v["run"]["it_per_s_median"] for k, v in res["runs"].items()}
+        res["it_per_s_vector_over_number"] = res["it_per_s_median"]["icpt_vec"] / res["it_per_s_median"]["icpt"]
+        # the byte model: one more stream of n elements in every launch that evaluates the prox, nothing in the row kernels
+        res["model_extra_bytes_per_prox_launch"] = res["n"] * 8
+        rocprof = shutil.which("rocprofv3")
+        if rocprof:
+            res["per_kernel"] = {}
+            for kind in INTERCEPT:      # (a process each: the kernels have the same names)
+                d = os.path.join(args.out, "rocprof_sparse_glm_" + kind)
+                shutil.rmtree(d, ignore_errors=True)
+                child([rocprof, "--kernel-trace", "--stats", "--output-format", "csv", "-d", d, "--"] + cmd(kind, **{"--steps": 40, "--repeats": 1}),
+                      env, "rocprofv3 " + kind)
+                res["per_kernel"][kind] = all_kernel_stats(d)
+                shutil.rmtree(d, ignore_errors=True)
+            a, b = res["per_kernel"]["icpt"], res["per_kernel"]["icpt_vec"]
+            res["vector_minus_number_us"] = {k: b[k]["avg_us"] - a[k]["avg_us"] for k in sorted(set(a) & set(b))}
+            # (what the extra stream would cost at the HBM peak)
+            res["model_extra_us_at_8TBs"] = res["model_extra_bytes_per_prox_launch"] / HBM_PEAK * 1e6
+        else:
+            res["per_kernel"] = "rocprofv3 not found"
     else:
         res = child(cmd("huber", **{"--callback": 1}), env, "lowered against callbacks")
         res.update(case="callback", commit=args.commit or commit_of_tree(), speedup=res["runs"]["huber"]["speedup"])
