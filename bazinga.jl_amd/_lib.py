@@ -25,6 +25,7 @@ BZ_F_SPARSE_QUADRATIC = 6
 BZ_F_SPARSE_LEAST_SQUARES = 7
 BZ_F_SPARSE_LOGISTIC = 8
 BZ_F_SPARSE_GLM = 9
+BZ_F_SPARSE_MULTINOMIAL = 10
 BZ_LOSS_LEAST_SQUARES, BZ_LOSS_LOGISTIC, BZ_LOSS_HUBER, BZ_LOSS_SQUARED_HINGE, BZ_LOSS_POISSON = 0, 1, 2, 3, 4
 # host-callback oracle protocol (include/bazinga_hip.h)
 F_GRADIENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)
@@ -58,7 +59,7 @@ class ProblemDesc(C.Structure):
         ("D_kind", C.c_int32), ("slack", C.c_int32),
         ("n", C.c_int64), ("ny", C.c_int64),
         ("f_q", C.c_void_p), ("f_b", C.c_void_p), ("f_grid_nx", C.c_int64), ("f_grid_ny", C.c_int64),
-        ("f_A", C.c_void_p), ("f_rows", C.c_int64),
+        ("f_A", C.c_void_p), ("f_rows", C.c_int64), ("f_classes", C.c_int64),
         ("g_lambda", C.c_double), ("g_p", C.c_double), ("g_u", C.c_void_p), ("g_lo", C.c_double), ("g_hi", C.c_double),
         ("g_lo_vec", C.c_void_p), ("g_hi_vec", C.c_void_p), ("g_lambda_vec", C.c_void_p),
         ("c_A", C.c_void_p), ("c_b", C.c_void_p),

@@ -8,6 +8,7 @@
 // provenance of the restatement.
 #include "bz_solver.h"
 #include "bz_spmv.h"
+#include "bz_spmm.h"
 #include "bz_als_dense.h"
 #include "bz_csr_host.h"
 
@@ -253,6 +254,31 @@ template <class T> class Solver final : public SolverBase {
             glm_weighted_ = d.f_w != nullptr || d.f_scale != 1.0;
             sparse_logit = d.f_loss == BZ_LOSS_LOGISTIC && !glm_weighted_;
         }
+        sparse_mn = d.f_kind == BZ_F_SPARSE_MULTINOMIAL;
+        if (sparse_mn) {
+            // (a `sparse_ls` problem whose three row launches are the K-wide kernels of bz_spmm.h; x is n / K rows of K)
+            sparse_ls = true;
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: the slack (ALS) form is not lowered with a sparse multinomial f");
+            if (d.c_kind == BZ_C_DENSE_AFFINE)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: a sparse multinomial f beside a dense c (DenseAffine) is not lowered");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: the sparse multinomial f is not sharded (one rank)");
+            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+                throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: the sparse multinomial f does not mix with host callbacks");
+            if (d.f_classes < 2 || d.f_classes > 64)
+                throw Error(BZ_ERR_ARG, "SparseMultinomial: f_classes = K must be in 2 .. 64");
+            if (n % d.f_classes != 0)
+                throw Error(BZ_ERR_ARG, "SparseMultinomial: n must be a multiple of f_classes (x is n / K rows of K)");
+            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
+                throw Error(BZ_ERR_ARG, "SparseMultinomial needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and the labels b[m]");
+            // (32-bit: the column indices of A_f, below n / K, and of A_f', below m; an index into X or R is formed in 64 bits)
+            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
+                throw Error(BZ_ERR_ARG, "SparseMultinomial: n and m must fit 32-bit indices");
+            if (!(std::isfinite(d.f_scale) && d.f_scale > 0))
+                throw Error(BZ_ERR_ARG, "SparseMultinomial: f_scale must be finite and > 0 (1 for the plain sum)");
+            mn_K_ = (int)d.f_classes;
+            mn_KP_ = 2;
+            while (mn_KP_ < mn_K_) mn_KP_ *= 2;
+        }
         if (d.c_kind == BZ_C_SPARSE_AFFINE) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: the slack (ALS) form is not lowered with a sparse c");
             if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine is not sharded (one rank)");
@@ -405,10 +431,11 @@ template <class T> class Solver final : public SolverBase {
             frows = d.f_rows;
             sparse_ls_create(d);
             upload(fb_, d.f_b, frows);
-            FR_.alloc(frows);
+            FR_.alloc(sparse_mn ? frows * mn_K_ : frows);                   // (the multinomial f: R is m rows of K)
             if (d.c_kind == BZ_C_SPARSE_AFFINE || !spls_fused_on()) DFX_.alloc(nx);
-            fscale = sparse_logit || (sparse_glm && glm_loss_ != BZ_LOSS_LEAST_SQUARES) ? T(1) : T(0.5);
-            if (sparse_glm) glm_weights_create(d);
+            fscale = sparse_logit || sparse_mn || (sparse_glm && glm_loss_ != BZ_LOSS_LEAST_SQUARES) ? T(1) : T(0.5);
+            if (sparse_mn) mn_labels_check(d);
+            if (sparse_glm || sparse_mn) glm_weights_create(d);
         }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             A_.alloc((size_t)ny * nx);
@@ -1872,11 +1899,12 @@ template <class T> class Solver final : public SolverBase {
         DBuf<double> part;
         int64_t rows = 0, cols = 0, nnz = 0, nv = 0, S = 0;
         int L = 1, ncut = 0;
+        int64_t kw = 1;                    // values behind a gathered index (the multinomial f's matrices: K)
         SpMat<T> mat() const { return SpMat<T>{ptr.p, col.p, val.p, ncut ? vrow.p : nullptr, ncut ? vpart.p : nullptr, part.p, nv}; }
         // bytes of one pass without the per-row vectors: both CSR arrays, the row pointers (and the two virtual-row
         // tables of a cut matrix), one read of the gathered vector
         double bytes() const {
-            return (double)nnz * (sizeof(T) + 4) + (double)(nv + 1) * 8 + (ncut ? (double)nv * 8 : 0.0) + (double)cols * sizeof(T);
+            return (double)nnz * (sizeof(T) + 4) + (double)(nv + 1) * 8 + (ncut ? (double)nv * 8 : 0.0) + (double)(cols * kw) * sizeof(T);
         }
     };
     SpCsr spA_, spAt_, spQ_;               // (Q: the sparse quadratic f; symmetric, so no transpose)
@@ -1944,7 +1972,9 @@ template <class T> class Solver final : public SolverBase {
     }
     // a host copy of the caller's CSR (rows x n), validated; `what` is the kind and `rows_name` its row count in the messages
     void sp_read(const std::string& what, const char* rows_name, int64_t rows, const int64_t* rowptr, const int32_t* colp,
-                 const void* valp, int64_t nnz, std::vector<int64_t>& rp, std::vector<int32_t>& col, std::vector<T>& val) {
+                 const void* valp, int64_t nnz, std::vector<int64_t>& rp, std::vector<int32_t>& col, std::vector<T>& val,
+                 int64_t ncols = -1) {
+        // (ncols: the matrix's columns where they are not the problem's n — the multinomial f's A_f has n / K)
         rp.resize((size_t)rows + 1); col.resize((size_t)nnz); val.resize((size_t)nnz);
         BZ_HIP(hipMemcpy(rp.data(), rowptr, rp.size() * sizeof(int64_t), hipMemcpyDefault));
         if (nnz) {
@@ -1959,8 +1989,8 @@ template <class T> class Solver final : public SolverBase {
             throw Error(BZ_ERR_ARG, what + ": rowptr[" + rows_name + "] must equal nnz (row " + std::to_string(rows - 1) + ")");
         for (int64_t r = 0; r < rows; ++r)
             for (int64_t k = rp[r]; k < rp[r + 1]; ++k)
-                if (col[k] < 0 || (int64_t)col[k] >= n)
-                    throw Error(BZ_ERR_ARG, what + ": column index outside [0, n) (row " + std::to_string(r) + ")");
+                if (col[k] < 0 || (int64_t)col[k] >= (ncols >= 0 ? ncols : n))
+                    throw Error(BZ_ERR_ARG, what + (ncols >= 0 ? ": column index outside [0, n / K) (row " : ": column index outside [0, n) (row ") + std::to_string(r) + ")");
     }
     static std::string sp_form(const char* kernel, const SpCsr& m) {
         return std::string(kernel) + "<L=" + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
@@ -1978,6 +2008,24 @@ template <class T> class Solver final : public SolverBase {
     // rules of A and A'
     void sparse_ls_create(const bz_problem_desc& d) {
         std::vector<int64_t> rp, tp; std::vector<int32_t> col, tcol; std::vector<T> val, tval;
+        if (sparse_mn) {
+            // A_f is m x n_f, n_f = n / K: the transpose is built over n_f columns; a segment of a cut row leaves K sums
+            const int64_t nf = nx / mn_K_;
+            sp_read("SparseMultinomial", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val, nf);
+            csr_transpose(frows, nf, rp, col, val, tp, tcol, tval);
+            sp_build(spF_, frows, nf, rp, col, val);
+            sp_build(spFt_, nf, frows, tp, tcol, tval);
+            for (SpCsr* m : {&spF_, &spFt_}) {
+                m->kw = mn_K_;
+                m->L = spmm_lanes(m->nnz, m->nv, mn_KP_);
+                if (cenv_.spmv_l) m->L = std::min(*cenv_.spmv_l, 64 / mn_KP_);
+                if (m->ncut) m->part.alloc(m->part.n * (size_t)mn_K_);
+            }
+            spmm_form_[0] = spmm_form("k_spmm_softmax_r", spF_);
+            spmm_form_[1] = spmm_form("k_spmm_t_algrad", spFt_);
+            spmm_form_[2] = spmm_form("k_spmm_t", spFt_);
+            return;
+        }
         sp_read(sparse_glm ? "SparseGLM" : sparse_logit ? "SparseLogistic" : "SparseLeastSquares", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
         csr_transpose(frows, nx, rp, col, val, tp, tcol, tval);
         sp_build(spF_, frows, nx, rp, col, val);
@@ -1995,24 +2043,98 @@ template <class T> class Solver final : public SolverBase {
     // the GLM f: w^_i = T(scale * w_i), the product in double and rounded once; without a weight vector the one number T(scale).
     // Every w_i finite and >= 0, checked on a host copy.
     void glm_weights_create(const bz_problem_desc& d) {
+        const std::string what = sparse_mn ? "SparseMultinomial" : "SparseGLM";     // (the multinomial f: the same two fields, the same rules)
         glm_w_uniform_ = (T)d.f_scale;
         glm_delta_ = (T)d.f_loss_delta;
         // (what the kernel multiplies by is the ROUNDED number: an fp32 problem can overflow where the double was finite)
         if (!std::isfinite((double)glm_w_uniform_))
-            throw Error(BZ_ERR_ARG, "SparseGLM: f_scale must be finite and > 0 in the problem's type");
-        if (d.f_loss == BZ_LOSS_HUBER && !(std::isfinite((double)glm_delta_) && glm_delta_ > T(0)))
+            throw Error(BZ_ERR_ARG, what + ": f_scale must be finite and > 0 in the problem's type");
+        if (sparse_glm && d.f_loss == BZ_LOSS_HUBER && !(std::isfinite((double)glm_delta_) && glm_delta_ > T(0)))
             throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0 in the problem's type");
         if (!d.f_w) return;
         std::vector<T> w((size_t)frows);
         BZ_HIP(hipMemcpy(w.data(), d.f_w, w.size() * sizeof(T), hipMemcpyDefault));
         for (int64_t r = 0; r < frows; ++r) {
             if (!(std::isfinite((double)w[r]) && w[r] >= T(0)))
-                throw Error(BZ_ERR_ARG, "SparseGLM: the weights must be finite and >= 0 (row " + std::to_string(r) + ")");
+                throw Error(BZ_ERR_ARG, what + ": the weights must be finite and >= 0 (row " + std::to_string(r) + ")");
             w[r] = (T)(d.f_scale * (double)w[r]);
             if (!std::isfinite((double)w[r]))
-                throw Error(BZ_ERR_ARG, "SparseGLM: the weights times f_scale must be finite in the problem's type (row " + std::to_string(r) + ")");
+                throw Error(BZ_ERR_ARG, what + ": the weights times f_scale must be finite in the problem's type (row " + std::to_string(r) + ")");
         }
         sp_upload(glm_w_, w);
+    }
+    // the multinomial f: every label finite, integral and in [0, K), checked on a host copy (a bad label would silently change
+    // the loss: no class lane would own the row)
+    void mn_labels_check(const bz_problem_desc& d) {
+        std::vector<T> b((size_t)frows);
+        BZ_HIP(hipMemcpy(b.data(), d.f_b, b.size() * sizeof(T), hipMemcpyDefault));
+        for (int64_t r = 0; r < frows; ++r) {
+            const double v = (double)b[r];
+            if (!(std::isfinite(v) && v == std::floor(v) && v >= 0 && v < (double)mn_K_))
+                throw Error(BZ_ERR_ARG, "SparseMultinomial: the labels must be integers in [0, K) (row " + std::to_string(r) + ")");
+        }
+    }
+    // lanes per class and row from the mean (virtual) row length, sp_lanes' rule under KP * L <= 64
+    static int spmm_lanes(int64_t nnz, int64_t nv, int KP) {
+        const double mean = nv > 0 ? (double)nnz / (double)nv : 0.0;
+        int L = 1;
+        while (KP * L * 2 <= 64 && mean > 4.0 * L) L *= 2;
+        return L;
+    }
+    std::string spmm_form(const char* kernel, const SpCsr& m) const {
+        return std::string(kernel) + "<K=" + std::to_string(mn_K_) + ",L=" + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
+    }
+    // go(KP, L, NT) with the run-time class width, lane count and stream policy as compile-time constants (KP * L <= 64)
+    template <int KP, class F> static void spmm_with_l(int L, bool nt, F&& go) {
+        with_bool(nt, [&](auto nt_) {
+            constexpr int LMAX = 64 / KP;
+            auto at = [&](auto l_) { go(std::integral_constant<int, KP>{}, l_, nt_); };
+            if (L >= 32 && LMAX >= 32) at(std::integral_constant<int, LMAX >= 32 ? 32 : 1>{});
+            else if (L >= 16 && LMAX >= 16) at(std::integral_constant<int, LMAX >= 16 ? 16 : 1>{});
+            else if (L >= 8 && LMAX >= 8) at(std::integral_constant<int, LMAX >= 8 ? 8 : 1>{});
+            else if (L >= 4 && LMAX >= 4) at(std::integral_constant<int, LMAX >= 4 ? 4 : 1>{});
+            else if (L >= 2 && LMAX >= 2) at(std::integral_constant<int, LMAX >= 2 ? 2 : 1>{});
+            else at(std::integral_constant<int, 1>{});
+        });
+    }
+    template <class F> void spmm_with_lanes(int L, bool nt, F&& go) const {
+        switch (mn_KP_) {
+        case 2: spmm_with_l<2>(L, nt, go); break;
+        case 4: spmm_with_l<4>(L, nt, go); break;
+        case 8: spmm_with_l<8>(L, nt, go); break;
+        case 16: spmm_with_l<16>(L, nt, go); break;
+        case 32: spmm_with_l<32>(L, nt, go); break;
+        default: spmm_with_l<64>(L, nt, go); break;
+        }
+    }
+    // one pass of the K-wide row kernel (WHICH 0: k_spmm_softmax_r over A_f, 1: k_spmm_t_algrad and 2: k_spmm_t over A_f') and,
+    // for a cut matrix, the fold of its cut rows; returns the number of block partials left in `slot`.  The byte model counts
+    // the matrix once per pass (m.bytes(): the entries, the row pointers, one read of the K-wide gathered vector) and the
+    // K-wide per-row vectors in vec_bytes.
+    template <int WHICH> int spmm_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
+        constexpr int MODE = WHICH == 0 ? SPMM_SOFTMAX : WHICH == 1 ? 5 : 6;
+        const double bytes = m.bytes() + vec_bytes;
+        const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
+        const int gfold = m.ncut ? (int)std::min<int64_t>(512, (m.ncut + WAVES - 1) / WAVES) : 0;
+        const int K = mn_K_;
+        int g = 1;
+        spmm_with_lanes(m.L, nt, [&](auto kp_, auto l_, auto nt_) {
+            constexpr int KP = decltype(kp_)::value, L = decltype(l_)::value;
+            constexpr bool NT = decltype(nt_)::value;
+            const int64_t rpb = BLOCK / (KP * L);
+            g = (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - gfold, (m.nv + rpb - 1) / rpb));
+            pending_bytes_ += bytes;
+            nm(spmm_form_[WHICH].c_str());
+            if constexpr (WHICH == 0) launch(C_GEMV, k_spmm_softmax_r<T, KP, L, NT>, g, m.mat(), gathered, K, E, parts_.p, slot);
+            else if constexpr (WHICH == 1) launch(C_GEMV, k_spmm_t_algrad<T, KP, L, NT>, g, m.mat(), gathered, K, E, parts_.p, slot);
+            else launch(C_GEMV, k_spmm_t<T, KP, L, NT>, g, m.mat(), gathered, K, E, parts_.p, slot);
+            if (gfold) {
+                pending_bytes_ += (double)m.part.n * 8 + (double)m.ncut * 8;
+                launch(C_MISC, k_spmm_fold<T, KP, MODE>, gfold, (const double*)m.part.p, (const int32_t*)m.crow.p,
+                       (const int32_t*)m.cptr.p, m.ncut, K, E, parts_.p, slot, g);
+            }
+        });
+        return g + gfold;
     }
     // (the plain least-squares and logistic losses run k_spmv_ls_r / k_spmv_logit_r)
     bool glm_own_kernel() const { return sparse_glm && (glm_weighted_ || glm_loss_ >= BZ_LOSS_HUBER); }
@@ -2121,6 +2243,12 @@ template <class T> class Solver final : public SolverBase {
     // The GLM f: r_i = w_i l'(b_i, a_i'x) and the partials of the weighted losses; a weight vector is one more stream.
     int spls_residual(const T* x, T* r_out, int slot) {
         SpEpi<T> E{fb_.p, nullptr, r_out, nullptr, P, nullptr};
+        if (sparse_mn) {
+            // the multinomial f: R = w (softmax(A_f X) - onehot(b)), m rows of K, and the partials of the rows' losses.  Per row:
+            // the label (and K of R); a weight vector is one more stream.
+            E.w = glm_w_.p; E.w_uniform = glm_w_uniform_;
+            return spmm_pass<0>(spF_, x, E, slot, (1 + (r_out ? mn_K_ : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T));
+        }
         if (glm_own_kernel()) {
             E.w = glm_w_.p; E.w_uniform = glm_w_uniform_; E.delta = glm_delta_;
             const double vecs = (1 + (r_out ? 1 : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T);
@@ -2139,11 +2267,13 @@ template <class T> class Solver final : public SolverBase {
     // (and D's vector bounds), the gradient.
     int spls_t_algrad(const T* x, T* grad, int slot) {
         SpEpi<T> E{nullptr, nullptr, grad, x, P, nullptr};
+        if (sparse_mn) return spmm_pass<1>(spFt_, FR_.p, E, slot, (1 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T));
         return sp_pass<5>(spFt_, FR_.p, E, slot, (1 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T));
     }
     // rows of A_f': A_f' r -> DFX_ (r in FR_)
     void spls_product() {
         SpEpi<T> E{nullptr, nullptr, DFX_.p, nullptr, P, nullptr};
+        if (sparse_mn) { spmm_pass<2>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T)); return; }
         sp_pass<6>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
     }
     // (pairwise D: the projection of element j needs its partner, which a row's first lane does not have)
@@ -3613,6 +3743,11 @@ template <class T> class Solver final : public SolverBase {
     DBuf<T> glm_w_;                        // [m] scale * w, or empty: glm_w_uniform_ = scale for every row
     T glm_w_uniform_ = T(1), glm_delta_ = T(0);
     std::string glm_form_;
+    // ---- f = SparseMultinomial: a sparse_ls problem whose three row launches are bz_spmm.h's (K values behind every index);
+    // the weights are glm_w_ / glm_w_uniform_
+    bool sparse_mn = false;
+    int mn_K_ = 0, mn_KP_ = 0;             // the classes, and the power of two >= K
+    std::string spmm_form_[3];             // k_spmm_softmax_r, k_spmm_t_algrad, k_spmm_t
 };
 
 // one-pass kernel of an oracle family: the instantiations live in bz_families_dk*.hip (one file per D class, so that

@@ -108,8 +108,9 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
             const T xv = E.x[r], e = E.ext[r], qv = P.b[r];
             dfx = e + qv;
             fterm = xv * (T(0.5) * e + qv);
-        } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES || P.f_kind == BZ_F_SPARSE_LOGISTIC || P.f_kind == BZ_F_SPARSE_GLM) {
-            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r / k_spmv_logit_r / k_spmv_glm_r)
+        } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES || P.f_kind == BZ_F_SPARSE_LOGISTIC || P.f_kind == BZ_F_SPARSE_GLM ||
+                   P.f_kind == BZ_F_SPARSE_MULTINOMIAL) {
+            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r / k_spmv_logit_r / k_spmv_glm_r / k_spmm_softmax_r)
         }
         if (E.out) E.out[r] = dfx + (T)d;
         acc[0] += (double)fterm;

@@ -507,6 +507,132 @@ class SparseGLM(ProximableFunction):
         return self._value(terms, x.dtype.type)
 
 
+class SparseMultinomial(ProximableFunction):
+    """Multinomial (softmax) regression on a sparse design matrix: f(X) = sum_i w^_i (logsumexp_k(t_ik) - t_{i,b_i}), T = A X,
+    w^_i = scale * w_i; A m-by-n_features in CSR (indptr[m + 1], indices[nnz] 0-based, data[nnz]), never densified; labels b in
+    {0 .. K - 1}^m, K = n_classes in 2 .. 64.  X is n_features x K ROW-MAJOR (class fastest): the variable is the flat vector x of
+    length n = n_features * K with x[j * K + k] = X[j, k] (`coef(x)` is that view).  The symmetric, over-parameterised softmax, as
+    glmnet has it: no reference class.  The gradient is A'R, laid out as X is, with r_ik = w^_i (p_ik - [k = b_i]).  Per row, with
+    ordered compares and arithmetic alone: mx = max_k t_ik, e_k = exp(t_ik - mx), S = sum_k e_k, p_k = e_k / S, and the row's loss
+    is w^_i ((mx - t_{i,b_i}) + log S).  A NaN in any t_ik reaches the row's loss and all K of its r; t_ik = +inf gives NaN
+    (inf - inf); an empty row has t = 0: loss w^_i log K, p = 1 / K.  The matrix conventions of SparseLeastSquares; `weights` and
+    `scale` as SparseGLM has them (the product in float64, rounded once to the dtype).  __call__ / gradient below are numpy with
+    these formulas in the dtype of x (the generic-oracle protocol); on the device the kind is BZ_F_SPARSE_MULTINOMIAL.
+    The first step size: PANOCplus estimates it from grad L(x0 + 1) - grad L(x0), and adding one number to all K classes of a
+    feature leaves f unchanged; where the penalty is flat there too (D = FreeSet, a box holding x0 and x0 + 1) the estimate is 0
+    and gamma = alpha / 0, as in the reference's algorithm.  Give the step size: PANOCplus(gamma=1.0, adaptive=True), or Lf."""
+
+    def __init__(self, indptr, indices, data, labels, n_features, n_classes, weights=None, scale=1.0):
+        ip, ix = np.asarray(indptr), np.asarray(indices)
+        self.data = np.ascontiguousarray(data)
+        lab = np.asarray(labels)
+        self.n_features, self.n_classes = int(n_features), int(n_classes)
+        if not 2 <= self.n_classes <= 64:
+            raise ValueError("n_classes must be in 2 .. 64")
+        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or lab.ndim != 1:
+            raise ValueError("indptr, indices, data and labels must be one-dimensional")
+        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr and indices must be integer arrays")
+        if self.data.dtype not in (np.float64, np.float32):
+            raise ValueError("data must be float64 or float32")
+        if not (np.issubdtype(lab.dtype, np.integer) or lab.dtype in (np.float64, np.float32)):
+            raise ValueError("labels must be float64, float32 or integers")
+        with np.errstate(invalid="ignore"):
+            if not np.all(np.isfinite(lab) & (lab == np.floor(lab)) & (lab >= 0) & (lab < self.n_classes)):
+                raise ValueError(f"labels must be integers in [0, {self.n_classes})")
+        if not (np.ndim(scale) == 0 and np.isfinite(scale) and scale > 0):
+            raise ValueError("scale must be a finite number > 0")
+        self.scale = float(scale)
+        self.b = np.ascontiguousarray(lab, dtype=self.data.dtype if np.issubdtype(lab.dtype, np.integer) else lab.dtype)
+        self.m = self.b.shape[0]
+        self.n = self.n_features * self.n_classes
+        if self.n_features <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+            raise ValueError("n_features * n_classes and the number of labels must be in 1 .. 2^31 - 1")
+        self.weights = None
+        if weights is not None:
+            w = np.asarray(weights)
+            if not (np.issubdtype(w.dtype, np.integer) or w.dtype in (np.float64, np.float32)):
+                raise ValueError("weights must be float64, float32 or integers")
+            if w.shape != (self.m,) or not np.all(np.isfinite(w) & (w >= 0)):
+                raise ValueError(f"weights must be {self.m} finite numbers >= 0")
+            self.weights = np.ascontiguousarray(w, dtype=self.data.dtype if np.issubdtype(w.dtype, np.integer) else w.dtype)
+        if ip.shape[0] != self.m + 1:
+            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
+        if ix.shape[0] != self.data.shape[0]:
+            raise ValueError("indices and data must have the same length")
+        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
+        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n_features):
+            raise ValueError(f"column indices must lie in [0, {self.n_features})")
+        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
+        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
+        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+
+    @property
+    def nnz(self):
+        return int(self.indices.shape[0])
+
+    @classmethod
+    def from_dense(cls, A, labels, n_classes, **kw):
+        A = np.asarray(A)
+        if A.ndim != 2:
+            raise ValueError("A must be m-by-n_features")
+        mask = A != 0
+        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
+        indices = np.nonzero(mask)[1].astype(np.int32)
+        return cls(indptr, indices, np.ascontiguousarray(A[mask]), labels, A.shape[1], n_classes, **kw)
+
+    @classmethod
+    def from_scipy(cls, M, labels, n_classes, **kw):
+        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        return cls(M.indptr, M.indices, M.data, labels, M.shape[1], n_classes, **kw)
+
+    def toarray(self):
+        A = np.zeros((self.m, self.n_features), self.data.dtype)
+        np.add.at(A, (self._rows, self.indices), self.data)
+        return A
+
+    def coef(self, x):
+        """the (n_features, n_classes) view of the flat variable"""
+        return np.asarray(x).reshape(self.n_features, self.n_classes)
+
+    row_weights = SparseGLM.row_weights
+
+    @staticmethod
+    def softmax_terms(t, labels, w):
+        """the rows' losses w ((mx - t_b) + log S) and R = w (p - onehot(b)) from T (m x K) in its dtype"""
+        dt = t.dtype.type
+        rows = np.arange(t.shape[0])
+        with np.errstate(over="ignore", invalid="ignore", divide="ignore"):
+            mx = np.max(t, axis=1)
+            e = np.exp(t - mx[:, None])
+            S = np.sum(e, axis=1, dtype=t.dtype)
+            r = e / S[:, None]
+            r[rows, labels] -= dt(1)
+            w = np.asarray(w, t.dtype)
+            loss = w * ((mx - t[rows, labels]) + np.log(S))
+            return loss, (w[:, None] if w.ndim else w) * r
+
+    def _loss_r(self, x):
+        K = self.n_classes
+        X = self.coef(x)
+        t = np.zeros((self.m, K), x.dtype)
+        np.add.at(t, self._rows, self.data.astype(x.dtype, copy=False)[:, None] * X[self.indices])
+        return self.softmax_terms(t, self.b.astype(np.int64), self.row_weights(x.dtype))
+
+    def __call__(self, x):
+        return x.dtype.type(np.sum(self._loss_r(x)[0]))
+
+    def gradient(self, dfx, x):
+        loss, r = self._loss_r(x)
+        G = np.zeros((self.n_features, self.n_classes), x.dtype)
+        np.add.at(G, self.indices, self.data.astype(x.dtype, copy=False)[:, None] * r[self._rows])
+        dfx[...] = G.reshape(-1)
+        return x.dtype.type(np.sum(loss))
+
+
 class Stencil5ptQuadratic(ProximableFunction):
     """f(x) = 0.5 x'A_h x - b'x on an nx-by-ny grid (row-major), A_h the 5-point Laplacian
     (4,-1,-1,-1,-1) with homogeneous Dirichlet halo — the structured `Quadratic` of BASELINE
@@ -860,7 +986,7 @@ def _vec(a, dtype, n, name):
 
 
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, SparseLeastSquares,
-                                      SparseLogistic, SparseGLM, Stencil5ptQuadratic))
+                                      SparseLogistic, SparseGLM, SparseMultinomial, Stencil5ptQuadratic))
 _LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
@@ -1046,6 +1172,27 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
             raise ValueError(f"scale, scale * weights and delta must be finite in {dtype}")
         if f.weights is not None:
             d.f_w = ptr(np.ascontiguousarray(_vec(f.weights, dtype, f.m, "weights")))
+    elif isinstance(f, SparseMultinomial):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("SparseMultinomial is not lowered in the slack (ALS) form")
+        if isinstance(c, DenseAffine):
+            raise UnsupportedOracle("SparseMultinomial is not lowered beside a dense c (DenseAffine)")
+        if f.n != n:
+            raise ValueError(f"x must have n_features * n_classes = {f.n} elements, not {n}")
+        d.f_kind = L.BZ_F_SPARSE_MULTINOMIAL
+        d.f_rows = f.m
+        d.f_classes = f.n_classes
+        d.f_sp_rowptr = ptr(f.indptr)
+        d.f_sp_col = ptr(f.indices)
+        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
+        d.f_sp_nnz = f.nnz
+        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "labels")))
+        d.f_scale = f.scale
+        if not np.all(np.isfinite(f.row_weights(dtype))):
+            raise ValueError(f"scale and scale * weights must be finite in {dtype}")
+        if f.weights is not None:
+            d.f_w = ptr(np.ascontiguousarray(_vec(f.weights, dtype, f.m, "weights")))
     elif isinstance(f, Stencil5ptQuadratic):
         d.f_kind = L.BZ_F_STENCIL5
         d.f_grid_nx, d.f_grid_ny = f.nx, f.ny
@@ -1102,7 +1249,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         # what the library refuses with this kind, refused here before any device call
         if slack:
             raise UnsupportedOracle("SparseAffine is not lowered in the slack (ALS) form")
-        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares, SparseLogistic, SparseGLM)):
+        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares, SparseLogistic, SparseGLM, SparseMultinomial)):
             raise UnsupportedOracle(f"SparseAffine is lowered with an element-wise f (Zero, DiagQuadratic), not {type(f).__name__}")
         if isinstance(D, PairwiseSet):
             raise UnsupportedOracle("pairwise D sets need c = IdentityFunction")

@@ -236,6 +236,29 @@ def sparse_glm(m: int, n: int, k: int = 5, loss: str = "huber", dtype=np.float64
             "b": b.astype(dtype), "m": m, "n": n, "xstar": xstar.astype(dtype), "loss": loss, "delta": delta}
 
 
+def sparse_multinomial(m: int, n_f: int, K: int, k: int = 5, dtype=np.float64, seed: int = SEED):
+    """Sparse multinomial (softmax) regression: min sum_i (logsumexp_c(t_ic) - t_{i,b_i}) + lam ||X||_1, T = A X, with the
+    matrix of sparse_lasso(m, n_f, k, dtype, seed) and a planted X* (n_f x K, row-major): its rows at the max(1, n_f div 20)
+    columns of the smallest keys u5, every entry there 2 (1 + u6) of random sign (u7), drawn for the K classes of a row in a
+    run.  The labels are drawn from the softmax of A X* by inverse CDF: b_i is the first class c whose cumulated probability
+    reaches u9 (K - 1 if rounding leaves none).  `xstar` is the flat vector X*.reshape(-1)."""
+    if not 2 <= K <= 64:
+        raise ValueError("sparse_multinomial needs 2 <= K <= 64")
+    if not 1 <= k <= n_f or m < 1:
+        raise ValueError("sparse_multinomial needs m >= 1 and 1 <= k <= n_f")
+    cols, data, _, _ = _sparse_rows(m, n_f, k, dtype, seed)
+    nz = max(1, n_f // 20)
+    support = np.argsort(uniform(5, n_f, seed=seed), kind="stable")[:nz]
+    X = np.zeros((n_f, K))
+    X[support] = (2.0 * (1.0 + uniform(6, nz * K, seed=seed)) * np.where(uniform(7, nz * K, seed=seed) < 0.5, -1.0, 1.0)).reshape(nz, K)
+    t = (data.astype(np.float64).reshape(m, k, 1) * X[cols]).sum(axis=1)
+    p = np.exp(t - t.max(axis=1, keepdims=True))
+    cdf = np.cumsum(p / p.sum(axis=1, keepdims=True), axis=1)
+    labels = np.minimum((cdf < uniform(9, m, seed=seed)[:, None]).sum(axis=1), K - 1)
+    return {"indptr": k * np.arange(m + 1, dtype=np.int64), "indices": cols.reshape(-1).astype(np.int32), "data": data,
+            "labels": labels.astype(dtype), "m": m, "n_f": n_f, "K": K, "n": n_f * K, "xstar": X.reshape(-1).astype(dtype)}
+
+
 def portfolio(n: int, dtype=np.float64, rank: int | None = None):
     """A stand-in for the absent demo/portfolio_data (demo/portfolio.jl:70-91: Q, rho, mu, ub), from the uniform stream:
 

@@ -91,6 +91,29 @@ extern "C" {
                                     and counts are the caller's contract.  The matrix conventions, the limits, the supported
                                     c / D and the refusals of BZ_F_SPARSE_LEAST_SQUARES.  BZ_LOSS_LEAST_SQUARES / BZ_LOSS_LOGISTIC
                                     without weights and with f_scale = 1 are kinds 7 / 8 bit for bit.                       */
+#define BZ_F_SPARSE_MULTINOMIAL 10 /* sum_i w^_i (logsumexp_k(t_ik) - t_{i,b_i}), T = A X, w^_i = f_scale * w_i: multinomial
+                                    (softmax) regression on a sparse design matrix A[f_rows][n_f] in CSR (f_sp_*), never
+                                    densified.  K = f_classes classes, 2 <= K <= 64; X is n_f x K ROW-MAJOR (class fastest:
+                                    x[j * K + k]), so the problem's n is n_f * K and the column indices lie in [0, n / K); the
+                                    symmetric, over-parameterised softmax (no reference class).  The labels b_i in {0 .. K - 1}
+                                    are stored in the problem's type in f_b[f_rows]; f_w / f_scale are BZ_F_SPARSE_GLM's fields
+                                    with its rules (w^_i the product in double rounded once; weights finite and >= 0, f_scale
+                                    finite and > 0, each also as rounded to the problem's type).  The gradient is A'R, laid out
+                                    as X is, with r_ik = w^_i (p_ik - [k = b_i]).  Per row, in the problem's type, with ordered
+                                    compares and arithmetic alone: mx = max_k t_ik ; e_k = exp(t_ik - mx) ; S = sum_k e_k (a
+                                    fixed tree) ; p_k = e_k / S ; the row's loss is w^_i ((mx - t_{i,b_i}) + log S).  An fp32
+                                    problem takes the fp32 exp / log; the rows' losses are summed in double.  A NaN in any
+                                    t_ik reaches the row's loss and all K of its r (S carries it even where the max drops it);
+                                    t_ik = +inf gives NaN (inf - inf), and so does a row whose t are all -inf; an empty row has
+                                    t = 0: loss w^_i log K, p = 1 / K.  The matrix conventions of BZ_F_SPARSE_LEAST_SQUARES
+                                    (unsorted and repeated column indices, empty rows and columns, nnz = 0).  Limits: n = n_f K
+                                    and f_rows <= 2^31 - 1 (32-bit column indices of A and A'), nnz and every index into X and
+                                    R (f_rows * K elements) 64-bit.  Checked at bz_problem_create (BZ_ERR_ARG): K in range,
+                                    n % K == 0, the column indices, f_rows > 0 and the pointers, every label finite, integral
+                                    and in [0, K) (on a host copy; the message names the row), f_scale and the weights.  c
+                                    Identity or SparseAffine, slack = 0, one rank, D Zero / Free / Box (and, with c = Identity,
+                                    the pairwise sets); refused (BZ_ERR_UNSUPPORTED): slack = 1, c = DenseAffine, more than one
+                                    rank, callbacks mixed in.                                                            */
 /* the row losses of BZ_F_SPARSE_GLM (f_loss), with v = t - b and u = b t                                   */
 #define BZ_LOSS_LEAST_SQUARES 0  /* l = v^2 / 2, l' = v                                                      */
 #define BZ_LOSS_LOGISTIC      1  /* b = +-1: BZ_F_SPARSE_LOGISTIC's l = softplus(-u), l' = -b sigma(-u)       */
@@ -227,6 +250,7 @@ typedef struct {
     const void* f_A;               /* LEAST_SQUARES: A[f_rows][n]; QUADRATIC: Q[n][n]; row-major;
                                       f_b then holds b[f_rows] resp. q[n]                */
     int64_t     f_rows;
+    int64_t     f_classes;         /* SPARSE_MULTINOMIAL alone: K, 2 <= K <= 64 (x is n / K rows of K); the other kinds ignore it */
     /* g */
     double      g_lambda;          /* NORM_L1*, NORM_L0_BOX: lambda >= 0; NORM_LP_*: alpha */
     double      g_p;               /* NORM_LP_*: exponent p in (0,1)                  */
@@ -255,6 +279,7 @@ typedef struct {
        f, SPARSE_LEAST_SQUARES (with f_rows = m and b[m] in f_b): A in CSR with m rows (rowptr[m + 1], rowptr[m] = nnz).
        f, SPARSE_LOGISTIC (with f_rows = m and the labels b[m] in f_b): A in CSR with m rows, as SPARSE_LEAST_SQUARES.
        f, SPARSE_GLM: A, f_rows and f_b as SPARSE_LEAST_SQUARES, and the four fields behind f_sp_nnz.
+       f, SPARSE_MULTINOMIAL: A[f_rows][n / f_classes], the labels b[f_rows] in f_b, and f_w / f_scale of the GLM's four.
        (All of these sit in front of c_sp_*: the sparse constraint's fields stay the descriptor's last four.) */
     const int64_t* f_sp_rowptr;    /* rowptr[n + 1], rowptr[0] = 0, non-decreasing, rowptr[n] = nnz */
     const int32_t* f_sp_col;       /* col[nnz], 0-based, in [0, n)                    */

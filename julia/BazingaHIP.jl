@@ -28,6 +28,7 @@ Base.@kwdef mutable struct ProblemDesc
     n::Int64 = 0; ny::Int64 = 0
     f_q::Ptr{Cvoid} = C_NULL; f_b::Ptr{Cvoid} = C_NULL; f_grid_nx::Int64 = 0; f_grid_ny::Int64 = 0
     f_A::Ptr{Cvoid} = C_NULL; f_rows::Int64 = 0
+    f_classes::Int64 = 0                  # f = SparseMultinomial (BZ_F_SPARSE_MULTINOMIAL) alone: K, x is n / K rows of K
     g_lambda::Float64 = 0; g_p::Float64 = 0; g_u::Ptr{Cvoid} = C_NULL; g_lo::Float64 = 0; g_hi::Float64 = 0
     g_lo_vec::Ptr{Cvoid} = C_NULL; g_hi_vec::Ptr{Cvoid} = C_NULL; g_lambda_vec::Ptr{Cvoid} = C_NULL
     c_A::Ptr{Cvoid} = C_NULL; c_b::Ptr{Cvoid} = C_NULL
@@ -205,6 +206,46 @@ function Bazinga.gradient!(dfx, f::SparseGLM{T}, x) where {T}
     return f.loss == 0 ? sum(w .* l) / 2 : sum(w .* l)
 end
 
+"""`SparseMultinomial(A::SparseMatrixCSC, labels, K; weights = nothing, scale = 1)`: multinomial (softmax) regression,
+f(X) = sum_i scale w_i (logsumexp_k(t_ik) - t_{i,b_i}), T = A X, with a sparse A (m x n_f) that is never densified and labels
+b in {0 .. K - 1} (0-based, as the library stores them), 2 <= K <= 64.  The variable is the flat vector x of length n_f K holding
+X ROW-MAJOR (class fastest): x[(j - 1) K + k] = X[j, k], i.e. `vec(permutedims(X))`; `coef(f, x)` gives X back.  The formulas are
+those of include/bazinga_hip.h.  Labels, the weights (>= 0) and the scale (> 0) are checked here."""
+struct SparseMultinomial{T} <: Bazinga.ProximableFunction
+    A::SparseMatrixCSC{T,Int}; b::Vector{T}; K::Int; w::Union{Nothing,Vector{T}}; scale::Float64
+    rowptr::Vector{Int64}; col::Vector{Int32}; val::Vector{T}
+    function SparseMultinomial(A::SparseMatrixCSC{T}, labels::Vector{T}, K::Integer; weights = nothing, scale = 1.0) where {T}
+        2 <= K <= 64 || throw(ArgumentError("K must be in 2 .. 64"))
+        length(labels) == size(A, 1) || throw(ArgumentError("one label per row of A"))
+        all(v -> isfinite(v) && v == floor(v) && 0 <= v < K, labels) || throw(ArgumentError("labels must be integers in [0, K)"))
+        (isfinite(scale) && scale > 0) || throw(ArgumentError("scale must be finite and > 0"))
+        weights === nothing || (length(weights) == length(labels) && all(v -> isfinite(v) && v >= 0, weights)) ||
+            throw(ArgumentError("weights must be finite and >= 0, one per row"))
+        At = sparse(A')
+        new{T}(A, labels, Int(K), weights === nothing ? nothing : Vector{T}(weights), Float64(scale),
+               Int64.(At.colptr .- 1), Int32.(At.rowval .- 1), Vector{T}(At.nzval))
+    end
+end
+coef(f::SparseMultinomial, x) = permutedims(reshape(x, f.K, size(f.A, 2)))
+# per row: mx = max_k t_k ; e = exp(t - mx) ; S = sum e ; p = e / S ; loss = w ((mx - t_b) + log S) ; r = w (p - onehot(b))
+function Bazinga.gradient!(dfx, f::SparseMultinomial{T}, x) where {T}
+    X = coef(f, x)
+    t = f.A * X
+    w = f.w === nothing ? fill(T(f.scale), length(f.b)) : T.(f.scale .* Float64.(f.w))
+    mx = maximum(t, dims = 2)
+    e = exp.(t .- mx)
+    S = sum(e, dims = 2)
+    R = e ./ S
+    loss = zero(T)
+    for i in eachindex(f.b)
+        k = Int(f.b[i]) + 1
+        R[i, k] -= one(T)
+        loss += w[i] * ((mx[i] - t[i, k]) + log(S[i]))
+    end
+    dfx .= vec(permutedims(f.A' * (w .* R)))
+    return loss
+end
+
 """`SparseLogistic(A::SparseMatrixCSC, labels)`: f(x) = sum_i log(1 + exp(-b_i a_i'x)), the logistic loss of a sparse design
 matrix that is never densified, labels b in {-1, +1} (checked here).  The plain sum: no 1/2 and no 1/m.  The library takes CSR:
 the CSC arrays of `sparse(A')` ARE the CSR arrays of A, made 0-based here."""
@@ -265,6 +306,13 @@ function lower_f!(d, f::SparseGLM)
     d.f_kind = 9; d.f_rows = length(f.b); d.f_sp_rowptr = pointer(f.rowptr); d.f_sp_col = pointer(f.col)
     d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val); d.f_b = pointer(f.b)
     d.f_loss = f.loss; d.f_loss_delta = f.delta; d.f_scale = f.scale
+    d.f_w = f.w === nothing ? C_NULL : pointer(f.w)
+    return nothing
+end
+function lower_f!(d, f::SparseMultinomial)
+    d.f_kind = 10; d.f_rows = length(f.b); d.f_classes = f.K; d.f_sp_rowptr = pointer(f.rowptr); d.f_sp_col = pointer(f.col)
+    d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val); d.f_b = pointer(f.b)
+    d.f_scale = f.scale
     d.f_w = f.w === nothing ? C_NULL : pointer(f.w)
     return nothing
 end
