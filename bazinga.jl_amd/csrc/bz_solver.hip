@@ -9,6 +9,7 @@
 #include "bz_solver.h"
 #include "bz_spmv.h"
 #include "bz_spmm.h"
+#include "bz_group.h"
 #include "bz_als_dense.h"
 #include "bz_csr_host.h"
 
@@ -188,6 +189,23 @@ template <class T> class Solver final : public SolverBase {
         if (n <= 0 || ny < 0) throw Error(BZ_ERR_ARG, "n must be positive");
         if (d.c_kind == BZ_C_IDENTITY && ny != n)
             throw Error(BZ_ERR_ARG, "c = Identity requires ny == n");
+        group_g = d.g_kind == BZ_G_NORM_L21;
+        if (group_g) {
+            // (a run-time kind outside the one-pass family table, as the Lp kinds are: the kernel chain, fbstep() its one prox site)
+            if (d.g_group < 1 || d.g_group > 64)
+                throw Error(BZ_ERR_ARG, "NormL21: g_group = K must be in 1 .. 64");
+            if (n % d.g_group != 0)
+                throw Error(BZ_ERR_ARG, "NormL21: n must be a multiple of g_group (x is n / K groups of K)");
+            if (!d.g_lambda_vec && !(std::isfinite(d.g_lambda) && d.g_lambda >= 0))
+                throw Error(BZ_ERR_ARG, "NormL21: g_lambda must be finite and >= 0");
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "NormL21: the slack (ALS) form is not lowered with a group penalty");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "NormL21: the group penalty is not sharded (one rank: a shard would have to hold whole groups)");
+            if (d.f_kind == BZ_F_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+                throw Error(BZ_ERR_UNSUPPORTED, "NormL21: the group penalty does not mix with host callbacks");
+            grp_K_ = (int)d.g_group;
+            grp_KP_ = 1;
+            while (grp_KP_ < grp_K_) grp_KP_ *= 2;
+        }
         sparse_f = d.f_kind == BZ_F_SPARSE_QUADRATIC;
         if (sparse_f) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseQuadratic: the slack (ALS) form is not lowered with a sparse quadratic f");
@@ -351,7 +369,7 @@ template <class T> class Solver final : public SolverBase {
             if (ctx->nranks > 1 && !ctx->p2p_on)
                 throw Error(BZ_ERR_UNSUPPORTED, "a sharded Stencil5pt needs the p2p mailboxes (bz_ctx_p2p_connect)");
         }
-        if ((d.g_kind < BZ_G_ZERO || d.g_kind > BZ_G_NORM_LP_BOX) && !generic_)
+        if ((d.g_kind < BZ_G_ZERO || d.g_kind > BZ_G_NORM_LP_BOX) && !group_g && !generic_)
             throw Error(BZ_ERR_ARG, "unknown g kind");
         if ((d.D_kind < BZ_D_ZERO || d.D_kind > BZ_D_XOR_PAIRS) && !generic_) throw Error(BZ_ERR_ARG, "unknown D kind");
         if (d.D_kind >= BZ_D_VC_PAIRS && d.D_kind <= BZ_D_XOR_PAIRS) {
@@ -362,7 +380,7 @@ template <class T> class Solver final : public SolverBase {
         }
         // (a per-element lambda: NormL1 alone — the box kinds use the one spare per-element g stream for u, and the
         // reference's NormL1Nonneg takes a number; g_lambda is ignored beside it)
-        if (d.g_lambda_vec && d.g_kind != BZ_G_NORM_L1)
+        if (d.g_lambda_vec && d.g_kind != BZ_G_NORM_L1 && !group_g)
             throw Error(BZ_ERR_ARG, "g_lambda_vec (a per-element lambda) is taken by NormL1 alone");
         if ((d.g_kind == BZ_G_NORM_L1 || d.g_kind == BZ_G_NORM_L1_NONNEG ||
              d.g_kind == BZ_G_NORM_L1_BOX || d.g_kind == BZ_G_NORM_L0_BOX) && d.g_lambda < 0 && !d.g_lambda_vec)
@@ -474,7 +492,12 @@ template <class T> class Solver final : public SolverBase {
             P.b = b_.p;
         }
         P.g_lambda = (T)d.g_lambda;
-        if (d.g_lambda_vec) {
+        if (d.g_lambda_vec && group_g) {
+            // (one entry per group, in the union slot g_u and NormL1's vector share: read through P.group_lambda_vec())
+            std::vector<T> lam;
+            read_group_lambda_vec(d.g_lambda_vec, lam);
+            upload(glam_, lam.data(), nx / grp_K_); P.g_group_lambda = glam_.p;
+        } else if (d.g_lambda_vec) {
             // (the x half in the slack form: the s half has no g)
             std::vector<T> lam;
             read_lambda_vec(d.g_lambda_vec, lam);
@@ -553,6 +576,7 @@ template <class T> class Solver final : public SolverBase {
     // holds a copy — but a one-pass launch made early for an iteration that never came, which is recalled here.
     void set_g_lambda(double lam, const void* lam_vec) override {
         const int k = desc.g_kind;
+        if (group_g) { set_group_lambda(lam, lam_vec); return; }
         if (!(k == BZ_G_NORM_L1 || k == BZ_G_NORM_L1_NONNEG || k == BZ_G_NORM_L1_BOX || k == BZ_G_NORM_L0_BOX))
             throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: g must be NormL1, NormL1Nonneg, NormL1Box or NormL0Box");
         if (lam_vec && !P.lambda_vec())
@@ -566,6 +590,28 @@ template <class T> class Solver final : public SolverBase {
         BZ_HIP(hipStreamSynchronize(ctx->stream));
         if (lam_vec) copy_in(glam_.p, h.data(), nx);
         else { P.g_lambda = (T)lam; desc.g_lambda = lam; }
+    }
+    // ... of NormL21: a number for a number, a vector (one entry per group) for a vector; a refused call changes nothing
+    void set_group_lambda(double lam, const void* lam_vec) {
+        if (lam_vec && !P.group_lambda_vec())
+            throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: the problem was created with a number lambda (NormL21 takes a vector at bz_problem_create only)");
+        if (!lam_vec && P.group_lambda_vec())
+            throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: the problem was created with a vector lambda of NormL21: pass a vector");
+        std::vector<T> h;
+        if (lam_vec) read_group_lambda_vec(lam_vec, h);
+        else if (!(std::isfinite(lam) && lam >= 0)) throw Error(BZ_ERR_ARG, "NormL21: lambda must be finite and >= 0");
+        gate_abort();
+        BZ_HIP(hipStreamSynchronize(ctx->stream));
+        if (lam_vec) copy_in(glam_.p, h.data(), nx / grp_K_);
+        else { P.g_lambda = (T)lam; desc.g_lambda = lam; }
+    }
+    // NormL21's per-group lambda on a host copy: n / K entries, finite and >= 0 (a zero: an unpenalised group)
+    void read_group_lambda_vec(const void* src, std::vector<T>& h) {
+        h.resize((size_t)(nx / grp_K_));
+        BZ_HIP(hipMemcpy(h.data(), src, h.size() * sizeof(T), hipMemcpyDefault));
+        for (size_t i = 0; i < h.size(); ++i)
+            if (!(std::isfinite((double)h[i]) && h[i] >= T(0)))
+                throw Error(BZ_ERR_ARG, "NormL21: every entry of the vector lambda must be finite and >= 0 (entry " + std::to_string(i) + ")");
     }
     // NormL1's per-element lambda on a host copy: every entry finite and >= 0 (zeros are the unpenalised coefficients)
     void read_lambda_vec(const void* src, std::vector<T>& h) {
@@ -951,6 +997,8 @@ template <class T> class Solver final : public SolverBase {
     int rows_per_chunk = 1, nrowchunks = 1;
     DBuf<T> FA_, fb_, FR_, DFX_, FGT_;       // dense f: matrix, vector, residual / Qx, gradient of f, A_f'r row-chunk partials
     bool dense_f = false, sparse_f = false, lp_g = false;      // (sparse_f: the sparse quadratic; sparse_ls: at the end)
+    bool group_g = false;                    // g = NormL21: kept on the kernel chain wherever lp_g is, k_fbstep_group its one kernel
+    int grp_K_ = 0, grp_KP_ = 0;             // ... its group size K and the power of two >= K
     // generic oracles (host callbacks): host mirrors of the vectors the callbacks read and write
     bool generic_ = false;
     std::vector<T> hx_, hg_, hy_, hz_, hres_, hdfx_, hjtv_, hcx_, ht_, hs_, hmu_, hmuy_, hyv_;
@@ -1849,6 +1897,7 @@ template <class T> class Solver final : public SolverBase {
     // common kinds keep their register budget
     void fbstep(const T* x, const T* g, T gam, T* z, T* res, int slot0) {
         if (generic_) { fbstep_generic(x, g, gam, z, res, slot0); return; }
+        if (group_g) { fbstep_group(x, g, gam, z, res, slot0); return; }      // (no slack form with that kind)
         if (slack_dense) {
             // one launch over the lifted vector, a section per half (k_fbstep_lifted)
             for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = lgx_ + lgs_;
@@ -1871,6 +1920,33 @@ template <class T> class Solver final : public SolverBase {
         if (lp_g) launch(C_FB, k_fbstep<T, true>, grid, x, g, gam, P, z, res, n, parts_.p, slot0);
         else launch(C_FB, k_fbstep<T, false>, grid, x, g, gam, P, z, res, n, parts_.p, slot0);
     }
+    // g = NormL21: k_fbstep_group<KP, NT>, KP the power of two >= K.  The streams k_fbstep counts, and one entry per group of
+    // a vector lambda; non-temporal loads when those streams are beyond the Infinity Cache
+    void fbstep_group(const T* x, const T* g, T gam, T* z, T* res, int slot0) {
+        const int64_t ngroups = n / grp_K_;
+        const int gg = group_grid(ngroups, grp_KP_);
+        const T* lamv = P.group_lambda_vec();
+        for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = gg;
+        const int vs = 1 + (g ? 1 : 0) + 1 + (res ? 1 : 0);
+        mv(vs); if (lamv) mv(1, ngroups);
+        const bool nt = env_.nt >= 0 ? env_.nt != 0 : (double)n * sizeof(T) * vs > 340e6;
+        with_bool(nt, [&](auto nt_) {
+            constexpr bool NT = decltype(nt_)::value;
+            auto go = [&](auto kp_) {
+                constexpr int KP = decltype(kp_)::value;
+                launch(C_FB, k_fbstep_group<T, KP, NT>, gg, x, g, gam, P.g_lambda, lamv, grp_K_, z, res, ngroups, parts_.p, slot0);
+            };
+            switch (grp_KP_) {
+            case 1: nm(NT ? "k_fbstep_group<KP=1,NT=1>" : "k_fbstep_group<KP=1,NT=0>"); go(std::integral_constant<int, 1>{}); break;
+            case 2: nm(NT ? "k_fbstep_group<KP=2,NT=1>" : "k_fbstep_group<KP=2,NT=0>"); go(std::integral_constant<int, 2>{}); break;
+            case 4: nm(NT ? "k_fbstep_group<KP=4,NT=1>" : "k_fbstep_group<KP=4,NT=0>"); go(std::integral_constant<int, 4>{}); break;
+            case 8: nm(NT ? "k_fbstep_group<KP=8,NT=1>" : "k_fbstep_group<KP=8,NT=0>"); go(std::integral_constant<int, 8>{}); break;
+            case 16: nm(NT ? "k_fbstep_group<KP=16,NT=1>" : "k_fbstep_group<KP=16,NT=0>"); go(std::integral_constant<int, 16>{}); break;
+            case 32: nm(NT ? "k_fbstep_group<KP=32,NT=1>" : "k_fbstep_group<KP=32,NT=0>"); go(std::integral_constant<int, 32>{}); break;
+            default: nm(NT ? "k_fbstep_group<KP=64,NT=1>" : "k_fbstep_group<KP=64,NT=0>"); go(std::integral_constant<int, 64>{}); break;
+            }
+        });
+    }
     T al_value(double fsum, double pensum) const {   // auglagfun.jl:78,81-82
         T lx = T(0.5) * T(pensum);
         lx += f_value(fsum);
@@ -1883,6 +1959,9 @@ template <class T> class Solver final : public SolverBase {
         case BZ_G_NORM_L1: case BZ_G_NORM_L1_NONNEG: case BZ_G_NORM_L1_BOX: case BZ_G_NORM_L0_BOX:
         case BZ_G_NORM_LP_NONNEG: case BZ_G_NORM_LP_BOX:
             if (P.lambda_vec()) return T(gsum);      // (the kernels summed lambda_i |z_i|)
+            return P.g_lambda * T(gsum);
+        case BZ_G_NORM_L21:
+            if (P.group_lambda_vec()) return T(gsum);      // (the kernel summed lambda_j (scal nrm))
             return P.g_lambda * T(gsum);
         case BZ_G_CALLBACK: return T(gsum);      // the callback returned g(z) itself
         default: return T(0);
@@ -2512,7 +2591,7 @@ template <class T> class Solver final : public SolverBase {
         uni_ = 0;
         const int uni_env = read_uni_knob();
         const bool probe = uni_env && (fused_family() >= 0 || (slack && !lp_g) ||
-                                       (desc.f_kind == BZ_F_STENCIL5 && desc.c_kind == BZ_C_IDENTITY && !slack && !lp_g));
+                                       (desc.f_kind == BZ_F_STENCIL5 && desc.c_kind == BZ_C_IDENTITY && !slack && !lp_g && !group_g));
         for (int k = 0; k < 3; ++k) slot_n[SL_GP + k] = grid_y;
         slot_n[SL_OUTER] = slot_n[SL_OUTER + 1] = grid_y;
         mv(3 + (safeguard ? 1 : 0), ny);
@@ -2546,7 +2625,7 @@ template <class T> class Solver final : public SolverBase {
     // the oracle family of the iterate-history one-pass kernel (fam_code, bz_kernels.h), or -1: c = Identity, an
     // element-wise f, any element-wise g but the Newton / L0 kinds, any D
     int fused_family() const {
-        if (desc.c_kind != BZ_C_IDENTITY || slack || ny != n || lp_g) return -1;
+        if (desc.c_kind != BZ_C_IDENTITY || slack || ny != n || lp_g || group_g) return -1;
         if (P.lambda_vec()) return -1;      // (a per-element lambda: no family for it, the stored-pair forms)
         int fk, gk, dk;
         switch (desc.f_kind) {
@@ -2767,13 +2846,13 @@ template <class T> class Solver final : public SolverBase {
     // representation, the persistent two-loop kernel
     void select_paths(const bz_panoc_opts& o) {
         // (the slack form of ALS too: x_i couples with s_i only — k_fused_slack; no pairwise D there, it needs the partner)
-        fused_ok = o.fuse && desc.c_kind == BZ_C_IDENTITY && !lp_g && (!slack || desc.D_kind < BZ_D_VC_PAIRS) &&
+        fused_ok = o.fuse && desc.c_kind == BZ_C_IDENTITY && !lp_g && !group_g && (!slack || desc.D_kind < BZ_D_VC_PAIRS) &&
                    (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
         // auto: the compact representation where it makes the whole iteration one pass (the fused separable
         // path, memory within its capacity), the two-loop recursion everywhere else
         // (... and the stencil path: x_d, k_stencil_fb, k_stencil_update_c with ONE reduction phase per iteration
         // instead of the persistent two-loop kernel's 2m - 1 grid barriers, or 2m + 1 exchanges when sharded)
-        stencil_fast_ = desc.f_kind == BZ_F_STENCIL5 && o.fuse && !lp_g && !slack;
+        stencil_fast_ = desc.f_kind == BZ_F_STENCIL5 && o.fuse && !lp_g && !group_g && !slack;
         if (o.affine_refresh < 0) throw Error(BZ_ERR_ARG, "affine_refresh must be >= 0");
         aff_refresh_ = o.affine_refresh;
         aff_track_ = affine_ok_ && aff_refresh_ > 0 && o.lbfgs_compact != 0 && state_.lbfgs.M >= 1 && state_.lbfgs.M <= CM && dir_kind_ == BZ_DIR_LBFGS;
@@ -2809,7 +2888,7 @@ template <class T> class Solver final : public SolverBase {
         return env_.fused_begin && desc.c_kind == BZ_C_IDENTITY && !slack && !dense_f &&
                (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
     }
-    bool begin_fb_ok() const { return begin_lip_ok() && !lp_g; }
+    bool begin_fb_ok() const { return begin_lip_ok() && !lp_g && !group_g; }
     void begin_impl(const bz_panoc_opts& o, const T* x0_dev) {
         env_ = BeginKnobs(ctx->nranks);
         opt = o;
@@ -3311,7 +3390,7 @@ template <class T> class Solver final : public SolverBase {
         if (!state_.res_valid) ensure_z();
         // cfg 4 with images: x_d, its images under grad L and c, L(x_d) and the forward-backward step in ONE launch
         // (k_dense_head; single rank, element-wise f, the common prox kinds)
-        it.head_on = env_.densesmall && it.use_compact && aff_track_ && !it.stencil_fast_now && !generic_ && !ctx->multi() && !lp_g &&
+        it.head_on = env_.densesmall && it.use_compact && aff_track_ && !it.stencil_fast_now && !generic_ && !ctx->multi() && !lp_g && !group_g &&
                      !dense_f && state_.gx_valid && state_.gz_valid && state_.aff_count + 1 < aff_refresh_ &&
                      (desc.f_kind == BZ_F_ZERO || desc.f_kind == BZ_F_DIAG_QUADRATIC);
         // x_d = x + d ; gradient at x_d ; state.x = x_d

@@ -686,6 +686,79 @@ class NormL1(ProximableFunction):
         return np.sum(lam * np.abs(z))
 
 
+class NormL21(ProximableFunction):
+    """The group Lasso: g(x) = sum_j lambda_j ||x[jK : (j+1)K]||_2 over the n / K contiguous groups of K = `group`
+    elements, 1 <= K <= 64 (no reference class; with SparseMultinomial's layout and K = n_classes a group is a feature's
+    row of coefficients).  lambda is a number, or a 1-D array with one entry per GROUP (finite, >= 0; a zero leaves its
+    group unpenalised: an intercept row).  `prox` is the specification of the device kernel, operation for operation in
+    x's type: the squares of a group are summed by the fixed fold of the power of two KP >= K (zeros behind K, then
+    q[:o] + q[o:] for o = KP/2 .. 1), so the result is the device's bit for bit."""
+
+    def __init__(self, lam=1.0, group=1):
+        if isinstance(group, bool) or not isinstance(group, (int, np.integer)):
+            raise ValueError("the group size must be an integer")
+        if not 1 <= group <= 64:
+            raise ValueError("the group size must be in 1 .. 64")
+        self.group = int(group)
+        if np.ndim(lam) == 0:
+            if not (np.isfinite(lam) and lam >= 0):
+                raise ValueError("parameter λ must be finite and nonnegative")
+            self.lam = float(lam)
+            return
+        lam = np.array(lam, dtype=np.float64)
+        if lam.ndim != 1:
+            raise ValueError("parameter λ must be a number or a 1-D array (one entry per group)")
+        if not np.all(np.isfinite(lam) & (lam >= 0)):
+            raise ValueError("parameter λ must have finite, nonnegative entries")
+        self.lam = lam
+
+    def _groups(self, x):
+        K = self.group
+        if x.ndim != 1 or x.shape[0] % K:
+            raise ValueError(f"the length of x ({x.shape}) must be a multiple of the group size {K}")
+        ng = x.shape[0] // K
+        if np.ndim(self.lam) and self.lam.shape[0] != ng:
+            raise ValueError(f"λ must have one entry per group ({ng}), not {self.lam.shape[0]}")
+        return ng, K
+
+    @staticmethod
+    def fold(q):
+        """the fixed sum over the last axis (a power of two long): q[:o] + q[o:] for o = KP/2 .. 1"""
+        o = q.shape[-1] // 2
+        while o >= 1:
+            q = q[..., :o] + q[..., o:2 * o]
+            o //= 2
+        return q[..., 0]
+
+    def __call__(self, x):
+        x = np.asarray(x)
+        ng, K = self._groups(x)
+        return np.sum(self.lam * np.sqrt(np.sum(x.reshape(ng, K) ** 2, axis=1)))
+
+    def prox(self, z, x, gamma):
+        T = x.dtype.type
+        ng, K = self._groups(x)
+        KP = 1
+        while KP < K:
+            KP *= 2
+        vec = np.ndim(self.lam) != 0
+        lam = np.asarray(self.lam, dtype=x.dtype) if vec else T(self.lam)
+        y = x.reshape(ng, K)
+        with np.errstate(all="ignore"):
+            q = np.zeros((ng, KP), x.dtype)
+            q[:, :K] = y * y
+            nrm = np.sqrt(self.fold(q))
+            gl = T(gamma) * lam
+            zero = nrm <= gl
+            big = nrm > gl
+            scal = np.where(zero, T(0), np.where(big, T(1) - gl / nrm, nrm - gl)).astype(x.dtype)
+            z[...] = np.where(zero[:, None], T(0), scal[:, None] * y).reshape(-1)
+            terms = scal * nrm
+            if vec:
+                return np.sum(lam * terms)
+            return lam * np.sum(terms)
+
+
 class NormL1Nonneg(ProximableFunction):
     """src/proxoperators/normL1Nonneg.jl:9-42"""
 
@@ -987,7 +1060,7 @@ def _vec(a, dtype, n, name):
 
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, SparseLeastSquares,
                                       SparseLogistic, SparseGLM, SparseMultinomial, Stencil5ptQuadratic))
-_LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
+_LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL21, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
 _LOWERED_D = lambda D: isinstance(D, (ZeroSet, FreeSet, PairwiseSet)) or \
@@ -1208,6 +1281,19 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
             d.g_lambda = g.lam
         else:
             d.g_lambda_vec = ptr(_vec(g.lam, dtype, n, "λ"))
+    elif isinstance(g, NormL21):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("NormL21 is not lowered in the slack (ALS) form")
+        if perm is not None:
+            raise UnsupportedOracle("NormL21 is not lowered beside a split-layout pairwise set (the groups would be permuted)")
+        if n % g.group:
+            raise ValueError(f"n = {n} must be a multiple of the group size {g.group}")
+        d.g_kind, d.g_group = L.BZ_G_NORM_L21, g.group
+        if np.ndim(g.lam) == 0:
+            d.g_lambda = g.lam
+        else:
+            d.g_lambda_vec = ptr(_vec(g.lam, dtype, n // g.group, "λ"))
     elif isinstance(g, NormL1Nonneg):
         d.g_kind, d.g_lambda = L.BZ_G_NORM_L1_NONNEG, g.lam
     elif isinstance(g, NormL1Box):

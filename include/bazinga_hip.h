@@ -131,6 +131,18 @@ extern "C" {
 #define BZ_G_NORM_L0_BOX     5   /* src/proxoperators/normL0Box.jl:33-58              */
 #define BZ_G_NORM_LP_NONNEG  6   /* alpha*sum x^p, x >= 0: normLpNonneg.jl:14-90      */
 #define BZ_G_NORM_LP_BOX     7   /* alpha*sum x^p, 0 <= x <= u: normLpBox.jl:11-97    */
+#define BZ_G_NORM_L21        9   /* (8 is BZ_G_CALLBACK.)  The group Lasso: g(x) = sum_j lambda_j ||x[jK : (j+1)K]||_2 over the n / K
+                                    contiguous groups of K = g_group elements, 1 <= K <= 64, n % K == 0 — with x laid out as
+                                    BZ_F_SPARSE_MULTINOMIAL has it and K = f_classes, a group is a feature's row of coefficients.
+                                    lambda is g_lambda, or g_lambda_vec with one entry per GROUP (finite, >= 0; a zero leaves its
+                                    group unpenalised: an intercept row).  No reference class.  The prox of one group, y the argument,
+                                    gl = gamma * lambda_j, all in the problem's type: q_k = y_k * y_k ; s = the sum of q over k by
+                                    the fixed fold of the power of two KP >= K (q_k = 0 for K <= k < KP ; for o = KP/2 .. 1:
+                                    q[:o] + q[o:]) ; nrm = sqrt(s) ; nrm <= gl: z = 0, scal = 0 ; nrm > gl: scal = 1 - gl / nrm,
+                                    z_k = scal * y_k ; otherwise (a NaN) scal = nrm - gl, z_k = scal * y_k.  The group's term of
+                                    g(z) is lambda_j * (scal * nrm).  A NaN makes its own group NaN and nothing else; an infinite
+                                    element gives z = y.  Every f, c and D of the kernel chain, slack = 0, one rank; refused
+                                    (BZ_ERR_UNSUPPORTED): slack = 1, more than one rank, callbacks mixed in.                   */
 /* c: constraint map.  eval!(cx,c,x), jtprod!(jtv,c,x,v)                             */
 #define BZ_C_IDENTITY        0   /* test/definitions/identityFunction.jl:3-13         */
 #define BZ_C_DENSE_AFFINE    1   /* A x - b, demo/basispursuit.jl:38-49               */
@@ -252,15 +264,17 @@ typedef struct {
     int64_t     f_rows;
     int64_t     f_classes;         /* SPARSE_MULTINOMIAL alone: K, 2 <= K <= 64 (x is n / K rows of K); the other kinds ignore it */
     /* g */
-    double      g_lambda;          /* NORM_L1*, NORM_L0_BOX: lambda >= 0; NORM_LP_*: alpha */
+    double      g_lambda;          /* NORM_L1*, NORM_L0_BOX, NORM_L21: lambda >= 0; NORM_LP_*: alpha */
     double      g_p;               /* NORM_LP_*: exponent p in (0,1)                  */
+    int64_t     g_group;           /* NORM_L21 alone: K, 1 <= K <= 64, n % K == 0 (x is n / K groups of K); the other kinds ignore it */
     const void* g_u;               /* NORM_L1_BOX / NORM_L0_BOX / NORM_LP_BOX: u[n] >= 0 */
     double      g_lo, g_hi;        /* IND_BOX scalar bounds                           */
     const void* g_lo_vec;          /* IND_BOX vector bounds (or NULL)                 */
     const void* g_hi_vec;
     const void* g_lambda_vec;      /* NORM_L1 alone: lambda[n] >= 0 (finite; zeros allowed: an unpenalised coefficient), g(x) =
                                       sum lambda_i |x_i|, or NULL; g_lambda is ignored beside it.  In the slack form n entries,
-                                      the x half.  Any other g kind with a vector: BZ_ERR_ARG                                */
+                                      the x half.  NORM_L21: lambda[n / g_group] >= 0, one entry per group, under the same rules.
+                                      Any other g kind with a vector: BZ_ERR_ARG                                               */
     /* c */
     const void* c_A;               /* DENSE_AFFINE: A[ny][n] row-major                */
     const void* c_b;               /* DENSE_AFFINE: b[ny]                             */
@@ -422,9 +436,9 @@ typedef struct {
 int bz_problem_set_multipliers(bz_problem* p, const void* mu, const void* y);
 
 /* lambda of a live problem, between solves (a path of Lasso fits on one upload of the matrices): g NORM_L1, NORM_L1_NONNEG,
- * NORM_L1_BOX or NORM_L0_BOX.  A problem created with a number takes lambda (>= 0) and lambda_vec == NULL; one created
- * with g_lambda_vec takes a non-NULL lambda_vec[n], validated as at creation, which overwrites the device copy (lambda is
- * ignored).  Number <-> vector would change the kernel forms the problem runs and stays a creation-time decision:
+ * NORM_L1_BOX, NORM_L0_BOX or NORM_L21.  A problem created with a number takes lambda (>= 0) and lambda_vec == NULL; one created
+ * with g_lambda_vec takes a non-NULL lambda_vec[n] (NORM_L21: [n / g_group]), validated as at creation, which overwrites the
+ * device copy (lambda is ignored).  Number <-> vector would change the kernel forms the problem runs and stays a creation-time decision:
  * BZ_ERR_ARG, as for any other g kind.  Between bz_panoc_begin and bz_panoc_finish: BZ_ERR_STATE.                         */
 int bz_problem_set_g_lambda(bz_problem* p, double lambda, const void* lambda_vec);
 

@@ -29,7 +29,7 @@ Base.@kwdef mutable struct ProblemDesc
     f_q::Ptr{Cvoid} = C_NULL; f_b::Ptr{Cvoid} = C_NULL; f_grid_nx::Int64 = 0; f_grid_ny::Int64 = 0
     f_A::Ptr{Cvoid} = C_NULL; f_rows::Int64 = 0
     f_classes::Int64 = 0                  # f = SparseMultinomial (BZ_F_SPARSE_MULTINOMIAL) alone: K, x is n / K rows of K
-    g_lambda::Float64 = 0; g_p::Float64 = 0; g_u::Ptr{Cvoid} = C_NULL; g_lo::Float64 = 0; g_hi::Float64 = 0
+    g_lambda::Float64 = 0; g_p::Float64 = 0; g_group::Int64 = 0; g_u::Ptr{Cvoid} = C_NULL; g_lo::Float64 = 0; g_hi::Float64 = 0
     g_lo_vec::Ptr{Cvoid} = C_NULL; g_hi_vec::Ptr{Cvoid} = C_NULL; g_lambda_vec::Ptr{Cvoid} = C_NULL
     c_A::Ptr{Cvoid} = C_NULL; c_b::Ptr{Cvoid} = C_NULL
     D_lo::Float64 = 0; D_hi::Float64 = 0; D_lo_vec::Ptr{Cvoid} = C_NULL; D_hi_vec::Ptr{Cvoid} = C_NULL
@@ -270,6 +270,39 @@ function Bazinga.gradient!(dfx, f::SparseLogistic{T}, x) where {T}
     return sum(loss)
 end
 
+"""`NormL21(λ, group)`: the group Lasso g(x) = Σ_j λ_j ‖x[(j-1)K+1 : jK]‖₂ over the length(x) ÷ K contiguous groups of K = `group`
+elements, 1 ≤ K ≤ 64 (BZ_G_NORM_L21) — with SparseMultinomial's class-fastest layout and K = n_classes, a feature's row of
+coefficients.  λ is a number, or a vector with one entry per group in the problem's type (finite, ≥ 0; a zero leaves its group
+unpenalised: an intercept row); the vector must stay alive until bz_problem_create returns."""
+struct NormL21{L} <: Bazinga.ProximableFunction
+    lambda::L; group::Int
+    function NormL21(lambda::L, group::Integer) where {L<:Union{Real,AbstractVector{<:Real}}}
+        1 <= group <= 64 || throw(ArgumentError("the group size must be in 1 .. 64"))
+        all(v -> isfinite(v) && v >= 0, lambda) || throw(ArgumentError("λ must be finite and nonnegative"))
+        new{L}(lambda, Int(group))
+    end
+end
+# the definition of include/bazinga_hip.h, group by group (the host twin of k_fbstep_group, to rounding: the sum of squares here
+# is Julia's, not the kernel's fixed fold)
+function ProximalOperators.prox!(z, g::NormL21, x, gamma)
+    K = g.group
+    length(x) % K == 0 || throw(ArgumentError("length(x) must be a multiple of the group size"))
+    T = eltype(x); gz = zero(T)
+    for j in 1:(length(x) ÷ K)
+        r = ((j - 1) * K + 1):(j * K)
+        lam = T(g.lambda isa Real ? g.lambda : g.lambda[j])
+        nrm = sqrt(sum(abs2, view(x, r))); gl = T(gamma) * lam
+        if nrm <= gl
+            z[r] .= zero(T)
+        else
+            scal = nrm > gl ? one(T) - gl / nrm : nrm - gl
+            z[r] .= scal .* view(x, r)
+            gz += lam * (scal * nrm)
+        end
+    end
+    return gz
+end
+
 "`LBFGS(M; compact = nothing)`: how the operator is evaluated (bz_panoc_opts.lbfgs_compact) — `false` the two-loop recursion in the reference's order, `true` the compact representation, `nothing` (default) compact where the one-pass kernel applies"
 struct LBFGS
     memory::Int; compact::Union{Nothing,Bool}
@@ -325,6 +358,9 @@ lower_g!(d, g::ProximalOperators.NormL1{<:Real}) = (d.g_kind = 1; d.g_lambda = g
 # (an array lambda: one weight per element, in the problem's type; the array must stay alive until bz_problem_create returns)
 lower_g!(d, g::ProximalOperators.NormL1{<:AbstractVector}) = (d.g_kind = 1; d.g_lambda_vec = pointer(g.lambda))
 lower_g!(d, g::Bazinga.NormL1Nonneg) = (d.g_kind = 2; d.g_lambda = g.lambda)
+# (the group Lasso: one weight per GROUP with a vector; n % group and the slack form are checked by bz_problem_create)
+lower_g!(d, g::NormL21{<:Real}) = (d.g_kind = 9; d.g_group = g.group; d.g_lambda = g.lambda)
+lower_g!(d, g::NormL21{<:AbstractVector}) = (d.g_kind = 9; d.g_group = g.group; d.g_lambda_vec = pointer(g.lambda))
 lower_g!(d, g::Bazinga.NormL1Box) = (d.g_kind = 3; d.g_lambda = g.lambda; d.g_u = pointer(g.u))
 lower_g!(d, g::ProximalOperators.IndBox{<:Real,<:Real}) = (d.g_kind = 4; d.g_lo = g.lb; d.g_hi = g.ub)
 lower_g!(d, g::Bazinga.NormL0Box) = (d.g_kind = 5; d.g_lambda = g.lambda; d.g_u = pointer(g.u))
@@ -446,8 +482,8 @@ mutable struct Problem
     end
 end
 
-# lambda of g (NormL1, NormL1Nonneg, NormL1Box, NormL0Box) between solves, on the live problem: a number for a problem
-# lowered from a number, a vector (the problem's type, length n) for one lowered from NormL1 with an array
+# lambda of g (NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormL21) between solves, on the live problem: a number for a problem
+# lowered from a number, a vector (the problem's type, length n; NormL21: one entry per group) for one lowered from an array
 set_g_lambda!(p::Problem, lambda::Real) = check(ccall((:bz_problem_set_g_lambda, lib), Cint,
     (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), p.h, lambda, C_NULL))
 set_g_lambda!(p::Problem, lambda::AbstractVector) = GC.@preserve lambda check(ccall((:bz_problem_set_g_lambda, lib), Cint,
