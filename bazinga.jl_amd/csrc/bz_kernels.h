@@ -4097,8 +4097,8 @@ k_muy(const T* __restrict__ mu, T* __restrict__ y, T* __restrict__ muy, int64_t 
         for (int e = 0; e < PackN<T>::N; ++e) {
             if (do_clamp) {
                 double w = (double)py.v[e];
-                w = w < 1e20 ? w : 1e20;      // min(y, 1e20)
-                w = w > -1e20 ? w : -1e20;    // max(-1e20, .)
+                w = (w < 1e20 || w != w) ? w : 1e20;      // min(y, 1e20): Julia's min / max return a NaN argument
+                w = (w > -1e20 || w != w) ? w : -1e20;    // max(-1e20, .)
                 py.v[e] = (T)w;
             }
             T m = pm.v[e] * py.v[e];
@@ -4163,11 +4163,11 @@ k_penalty_init(const T* __restrict__ cx, ElemParams<T> P, double denom, T* __res
             T d = pc.v[e] - sv;
             double d2 = (double)(d * d);
             double h = 0.5 * d2;
-            T m = (T)((h > 1.0 ? h : 1.0) / denom);
+            T m = (T)(((h > 1.0 || h != h) ? h : 1.0) / denom);      // max.(1.0, .): a NaN distance stays NaN
             m = (T)((double)m * 0.1);
             double mm = (double)m;
-            mm = mm < 1e8 ? mm : 1e8;
-            mm = mm > 1e-8 ? mm : 1e-8;
+            mm = (mm < 1e8 || mm != mm) ? mm : 1e8;
+            mm = (mm > 1e-8 || mm != mm) ? mm : 1e-8;
             ps.v[e] = sv; pm.v[e] = (T)mm;
         }
         st(s, i0, cnt, ps);
@@ -4187,8 +4187,8 @@ k_clamp_scale(T* __restrict__ v, double lo, double hi, T scale, int do_clamp, in
             T t = a.v[e];
             if (do_clamp) {
                 double w = (double)t;
-                w = w < hi ? w : hi;      // min(y, 1e20)
-                w = w > lo ? w : lo;      // max(-1e20, .)
+                w = (w < hi || w != w) ? w : hi;      // min(y, 1e20): a NaN argument is returned
+                w = (w > lo || w != w) ? w : lo;      // max(-1e20, .)
                 t = (T)w;
             } else {
                 t = t * scale;

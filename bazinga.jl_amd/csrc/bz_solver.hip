@@ -783,11 +783,11 @@ template <class T> class Solver final : public SolverBase {
             for (int64_t i = 0; i < ny; ++i) {
                 const T dd = hcx_[i] - hs_[i];
                 const double h = 0.5 * (double)(dd * dd);
-                T mm = (T)((h > 1.0 ? h : 1.0) / denom);
+                T mm = (T)(((h > 1.0 || h != h) ? h : 1.0) / denom);      // (a NaN distance stays NaN, as in k_penalty_init)
                 mm = (T)((double)mm * 0.1);
                 double w = (double)mm;
-                w = w < 1e8 ? w : 1e8;
-                w = w > 1e-8 ? w : 1e-8;
+                w = (w < 1e8 || w != w) ? w : 1e8;
+                w = (w > 1e-8 || w != w) ? w : 1e-8;
                 hmu_[i] = (T)w;
             }
             copy_in(sproj_.p, hs_.data(), ny);

@@ -351,9 +351,9 @@ def alps(f, g, c, D, x0, y0, *, tol=None, tol_prim=None, tol_dual=None, inner_to
         if not can_stop:
             if norm_res_prim_old is None:
                 pass
-            elif norm_res_prim > max(theta_penalty * norm_res_prim_old, tol_prim):
+            elif float(norm_res_prim) > max(theta_penalty * float(norm_res_prim_old), float(tol_prim)):
                 mu *= T(kappa_penalty)                          # :97
-            inner_tol = max(kappa_tol * inner_tol, tol_dual)    # :100
+            inner_tol = max(kappa_tol * inner_tol, float(tol_dual))    # :100
     elapsed_time = time.time() - start_time
     status = "first_order" if solved else ("max_iter" if tired else ("exception" if broken else "unknown"))
     return x, y, tot_it, tot_inner_it, elapsed_time, status, inner_tol, norm_res_prim, s, mu
@@ -402,9 +402,9 @@ def _als_host_loop(f, g, c, D, x, y, cx, s, mu, gFun, objx, tol_prim, tol_dual, 
         if not can_stop:
             if norm_res_prim_old is None:
                 pass
-            elif norm_res_prim > max(theta_penalty * norm_res_prim_old, tol_prim):
+            elif float(norm_res_prim) > max(theta_penalty * float(norm_res_prim_old), float(tol_prim)):
                 mu *= T(kappa_penalty)                          # :100
-            inner_tol = max(kappa_tol * inner_tol, tol_dual)    # :103
+            inner_tol = max(kappa_tol * inner_tol, float(tol_dual))    # :103
     elapsed_time = time.time() - start_time
     status = "first_order" if solved else ("max_iter" if tired else ("exception" if broken else "unknown"))
     return x, y, tot_it, tot_inner_it, elapsed_time, status, inner_tol, norm_res_prim, s, mu

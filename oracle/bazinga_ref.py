@@ -185,7 +185,9 @@ def project_onto_CC_set(z, x):
         else:
             z[1] = 0
     else:
-        z[...] = np.maximum(0, x)
+        # (Julia's max(0, -0.0) is 0.0; np.maximum(0, -0.0) returns its second argument: + 0 turns that zero positive and
+        # leaves every other value, NaN included, as it is)
+        z[...] = np.maximum(0, x) + 0
     return None
 
 
@@ -1302,9 +1304,9 @@ def alps(f, g, c, D, x0, y0, *, tol=None, tol_prim=None, tol_dual=None, inner_to
         if not can_stop:
             if norm_res_prim_old is None:
                 pass
-            elif norm_res_prim > max(theta_penalty * norm_res_prim_old, tol_prim):
+            elif float(norm_res_prim) > max(theta_penalty * float(norm_res_prim_old), float(tol_prim)):
                 mu *= T(kappa_penalty)                        # :97
-            inner_tol = max(kappa_tol * inner_tol, tol_dual)  # :100
+            inner_tol = max(kappa_tol * inner_tol, float(tol_dual))  # :100
     elapsed_time = time.time() - start_time
 
     if solved:
@@ -1474,9 +1476,9 @@ def als(f, g, c, D, x0, y0, *, tol=None, tol_prim=None, tol_dual=None, inner_tol
         if not can_stop:
             if norm_res_prim_old is None:
                 pass
-            elif norm_res_prim > max(theta_penalty * norm_res_prim_old, tol_prim):
+            elif float(norm_res_prim) > max(theta_penalty * float(norm_res_prim_old), float(tol_prim)):
                 mu *= T(kappa_penalty)
-            inner_tol = max(kappa_tol * inner_tol, tol_dual)
+            inner_tol = max(kappa_tol * inner_tol, float(tol_dual))
     elapsed_time = time.time() - start_time
     status = "first_order" if solved else ("max_iter" if tired else ("exception" if broken else "unknown"))
     return x, y, tot_it, tot_inner_it, elapsed_time, status, inner_tol, norm_res_prim, s, mu
