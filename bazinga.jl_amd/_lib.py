@@ -18,6 +18,7 @@ BZ_F_ZERO, BZ_F_DIAG_QUADRATIC, BZ_F_STENCIL5, BZ_F_LEAST_SQUARES, BZ_F_QUADRATI
 BZ_G_ZERO, BZ_G_NORM_L1, BZ_G_NORM_L1_NONNEG, BZ_G_NORM_L1_BOX, BZ_G_IND_BOX, BZ_G_NORM_L0_BOX = 0, 1, 2, 3, 4, 5
 BZ_G_NORM_LP_NONNEG, BZ_G_NORM_LP_BOX = 6, 7
 BZ_G_NORM_L21 = 9
+BZ_G_GROUP_LASSO = 10
 BZ_C_IDENTITY, BZ_C_DENSE_AFFINE, BZ_C_SPARSE_AFFINE = 0, 1, 3
 BZ_D_ZERO, BZ_D_FREE, BZ_D_BOX = 0, 1, 2
 BZ_D_VC_PAIRS, BZ_D_CC_PAIRS, BZ_D_EITHEROR_PAIRS, BZ_D_XOR_PAIRS = 3, 4, 5, 6
@@ -61,7 +62,8 @@ class ProblemDesc(C.Structure):
         ("n", C.c_int64), ("ny", C.c_int64),
         ("f_q", C.c_void_p), ("f_b", C.c_void_p), ("f_grid_nx", C.c_int64), ("f_grid_ny", C.c_int64),
         ("f_A", C.c_void_p), ("f_rows", C.c_int64), ("f_classes", C.c_int64),
-        ("g_lambda", C.c_double), ("g_p", C.c_double), ("g_group", C.c_int64), ("g_u", C.c_void_p), ("g_lo", C.c_double), ("g_hi", C.c_double),
+        ("g_lambda", C.c_double), ("g_p", C.c_double), ("g_group", C.c_int64), ("g_u", C.c_void_p),
+        ("g_group_ptr", C.c_void_p), ("g_ngroups", C.c_int64), ("g_l1", C.c_double), ("g_lo", C.c_double), ("g_hi", C.c_double),
         ("g_lo_vec", C.c_void_p), ("g_hi_vec", C.c_void_p), ("g_lambda_vec", C.c_void_p),
         ("c_A", C.c_void_p), ("c_b", C.c_void_p),
         ("D_lo", C.c_double), ("D_hi", C.c_double), ("D_lo_vec", C.c_void_p), ("D_hi_vec", C.c_void_p),

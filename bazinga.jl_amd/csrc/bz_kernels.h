@@ -62,8 +62,8 @@ template <class T> struct ElemParams {
         const T* g_lambda_vec; // NormL1: lambda[n], g = sum lambda_i |x_i| (then g_lambda is unused), or null.  Read through
                                // lambda_vec() by the run-time-kind kernels only (load_params puts it into ElemLoads::gu); the
                                // host keeps a problem that has it away from every compile-time form
-        const T* g_group_lambda; // NormL21: lambda[n / K], one entry per group, or null.  Read through group_lambda_vec() by
-                               // k_fbstep_group (bz_group.h) alone: no element-wise kernel runs with that kind
+        const T* g_group_lambda; // NormL21, GroupLasso: lambda[ngroups], one entry per group, or null.  Read through group_lambda_vec() by
+                               // k_fbstep_group / k_fbstep_ragged (bz_group.h, bz_group_ragged.h) alone: no element-wise kernel runs with these kinds
     };
     T g_lo, g_hi;
     const T* g_lo_vec;
@@ -73,7 +73,7 @@ template <class T> struct ElemParams {
     const T* D_hi_vec;
     T mu_uniform;          // the value of every mu[i] when the penalties are uniform (k_muy's probe), else unused
     __host__ __device__ const T* lambda_vec() const { return g_kind == BZ_G_NORM_L1 ? g_lambda_vec : nullptr; }
-    __host__ __device__ const T* group_lambda_vec() const { return g_kind == BZ_G_NORM_L21 ? g_group_lambda : nullptr; }
+    __host__ __device__ const T* group_lambda_vec() const { return g_kind == BZ_G_NORM_L21 || g_kind == BZ_G_GROUP_LASSO ? g_group_lambda : nullptr; }
 };
 
 // ---------------------------------------------------------------------------

@@ -10,6 +10,7 @@
 #include "bz_spmv.h"
 #include "bz_spmm.h"
 #include "bz_group.h"
+#include "bz_group_ragged.h"
 #include "bz_als_dense.h"
 #include "bz_csr_host.h"
 
@@ -189,8 +190,51 @@ template <class T> class Solver final : public SolverBase {
         if (n <= 0 || ny < 0) throw Error(BZ_ERR_ARG, "n must be positive");
         if (d.c_kind == BZ_C_IDENTITY && ny != n)
             throw Error(BZ_ERR_ARG, "c = Identity requires ny == n");
-        group_g = d.g_kind == BZ_G_NORM_L21;
-        if (group_g) {
+        ragged_g = d.g_kind == BZ_G_GROUP_LASSO;
+        group_g = d.g_kind == BZ_G_NORM_L21 || ragged_g;
+        if (ragged_g) {
+            // (the group Lasso over a group pointer: a run-time kind beside NormL21, k_fbstep_ragged its one kernel)
+            if (d.g_ngroups < 1 || d.g_ngroups > n)
+                throw Error(BZ_ERR_ARG, "GroupLasso: g_ngroups must be in 1 .. n");
+            if (!d.g_group_ptr) throw Error(BZ_ERR_ARG, "GroupLasso: g_group_ptr (ptr[g_ngroups + 1]) is null");
+            if (!d.g_lambda_vec && !(std::isfinite(d.g_lambda) && d.g_lambda >= 0))
+                throw Error(BZ_ERR_ARG, "GroupLasso: g_lambda must be finite and >= 0");
+            if (!(std::isfinite(d.g_l1) && d.g_l1 >= 0))
+                throw Error(BZ_ERR_ARG, "GroupLasso: g_l1 must be finite and >= 0");
+            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "GroupLasso: the slack (ALS) form is not lowered with a group penalty");
+            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "GroupLasso: the group penalty is not sharded (one rank: a shard would have to hold whole groups)");
+            if (d.f_kind == BZ_F_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+                throw Error(BZ_ERR_UNSUPPORTED, "GroupLasso: the group penalty does not mix with host callbacks");
+            grp_ng_ = d.g_ngroups;
+            grp_ptr_h_.resize((size_t)grp_ng_ + 1);
+            BZ_HIP(hipMemcpy(grp_ptr_h_.data(), d.g_group_ptr, grp_ptr_h_.size() * sizeof(int64_t), hipMemcpyDefault));
+            if (grp_ptr_h_[0] != 0) throw Error(BZ_ERR_ARG, "GroupLasso: g_group_ptr[0] must be 0");
+            grp_max_ = 0;
+            for (int64_t j = 0; j < grp_ng_; ++j) {
+                const int64_t sz = grp_ptr_h_[j + 1] - grp_ptr_h_[j];
+                if (sz < 1)
+                    throw Error(BZ_ERR_ARG, "GroupLasso: g_group_ptr must be strictly increasing (group " + std::to_string(j) + " is empty or negative)");
+                if (sz > RAGGED_MAX_GROUP)
+                    throw Error(BZ_ERR_ARG, "GroupLasso: a group holds 2^30 elements at the most (group " + std::to_string(j) + ")");
+                grp_max_ = std::max(grp_max_, sz);
+            }
+            if (grp_ptr_h_[grp_ng_] != n) throw Error(BZ_ERR_ARG, "GroupLasso: g_group_ptr[g_ngroups] must be n");
+            grp_L_ = ragged_lanes(n, grp_ng_);
+            // (elements in waves that sweep twice: every group of a wave whose longest group exceeds RAGGED_HOLD trips;
+            // with one workgroup trip per group this is the launch's, a function of the pointer alone)
+            grp_swept_ = 0;
+            const int64_t gpw = 64 / grp_L_;
+            for (int64_t w0 = 0; w0 < grp_ng_; w0 += gpw) {
+                const int64_t w1 = std::min(grp_ng_, w0 + gpw);
+                int64_t mx = 0;
+                for (int64_t j = w0; j < w1; ++j) mx = std::max(mx, grp_ptr_h_[j + 1] - grp_ptr_h_[j]);
+                if (mx > (int64_t)RAGGED_HOLD * grp_L_) grp_swept_ += grp_ptr_h_[w1] - grp_ptr_h_[w0];
+            }
+        } else if (d.g_group_ptr) {
+            // (g_ngroups and g_l1 are ignored beside every other kind; a pointer is a mistake worth naming)
+            throw Error(BZ_ERR_ARG, "g_group_ptr (a group pointer) is taken by GroupLasso alone");
+        }
+        if (group_g && !ragged_g) {
             // (a run-time kind outside the one-pass family table, as the Lp kinds are: the kernel chain, fbstep() its one prox site)
             if (d.g_group < 1 || d.g_group > 64)
                 throw Error(BZ_ERR_ARG, "NormL21: g_group = K must be in 1 .. 64");
@@ -205,6 +249,7 @@ template <class T> class Solver final : public SolverBase {
             grp_K_ = (int)d.g_group;
             grp_KP_ = 1;
             while (grp_KP_ < grp_K_) grp_KP_ *= 2;
+            grp_ng_ = n / grp_K_;
         }
         sparse_f = d.f_kind == BZ_F_SPARSE_QUADRATIC;
         if (sparse_f) {
@@ -496,12 +541,17 @@ template <class T> class Solver final : public SolverBase {
             // (one entry per group, in the union slot g_u and NormL1's vector share: read through P.group_lambda_vec())
             std::vector<T> lam;
             read_group_lambda_vec(d.g_lambda_vec, lam);
-            upload(glam_, lam.data(), nx / grp_K_); P.g_group_lambda = glam_.p;
+            upload(glam_, lam.data(), grp_ng_); P.g_group_lambda = glam_.p;
         } else if (d.g_lambda_vec) {
             // (the x half in the slack form: the s half has no g)
             std::vector<T> lam;
             read_lambda_vec(d.g_lambda_vec, lam);
             upload(glam_, lam.data(), nx); P.g_lambda_vec = glam_.p;      // (shares its slot with g_u: read through P.lambda_vec())
+        }
+        if (ragged_g) {
+            gptr_.alloc((size_t)grp_ng_ + 1);
+            BZ_HIP(hipMemcpyAsync(gptr_.p, grp_ptr_h_.data(), grp_ptr_h_.size() * sizeof(int64_t), hipMemcpyDefault, ctx->stream));
+            BZ_HIP(hipStreamSynchronize(ctx->stream));
         }
         P.g_p = (T)d.g_p;
         lp_g = d.g_kind == BZ_G_NORM_LP_NONNEG || d.g_kind == BZ_G_NORM_LP_BOX;
@@ -591,27 +641,28 @@ template <class T> class Solver final : public SolverBase {
         if (lam_vec) copy_in(glam_.p, h.data(), nx);
         else { P.g_lambda = (T)lam; desc.g_lambda = lam; }
     }
-    // ... of NormL21: a number for a number, a vector (one entry per group) for a vector; a refused call changes nothing
+    const char* gname() const { return ragged_g ? "GroupLasso" : "NormL21"; }
+    // ... of NormL21 and GroupLasso: a number for a number, a vector (one entry per group) for a vector; a refused call changes nothing
     void set_group_lambda(double lam, const void* lam_vec) {
         if (lam_vec && !P.group_lambda_vec())
-            throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: the problem was created with a number lambda (NormL21 takes a vector at bz_problem_create only)");
+            throw Error(BZ_ERR_ARG, std::string("bz_problem_set_g_lambda: the problem was created with a number lambda (") + gname() + " takes a vector at bz_problem_create only)");
         if (!lam_vec && P.group_lambda_vec())
-            throw Error(BZ_ERR_ARG, "bz_problem_set_g_lambda: the problem was created with a vector lambda of NormL21: pass a vector");
+            throw Error(BZ_ERR_ARG, std::string("bz_problem_set_g_lambda: the problem was created with a vector lambda of ") + gname() + ": pass a vector");
         std::vector<T> h;
         if (lam_vec) read_group_lambda_vec(lam_vec, h);
-        else if (!(std::isfinite(lam) && lam >= 0)) throw Error(BZ_ERR_ARG, "NormL21: lambda must be finite and >= 0");
+        else if (!(std::isfinite(lam) && lam >= 0)) throw Error(BZ_ERR_ARG, std::string(gname()) + ": lambda must be finite and >= 0");
         gate_abort();
         BZ_HIP(hipStreamSynchronize(ctx->stream));
-        if (lam_vec) copy_in(glam_.p, h.data(), nx / grp_K_);
+        if (lam_vec) copy_in(glam_.p, h.data(), grp_ng_);
         else { P.g_lambda = (T)lam; desc.g_lambda = lam; }
     }
-    // NormL21's per-group lambda on a host copy: n / K entries, finite and >= 0 (a zero: an unpenalised group)
+    // NormL21's and GroupLasso's per-group lambda on a host copy: one entry per group, finite and >= 0 (a zero: an unpenalised group)
     void read_group_lambda_vec(const void* src, std::vector<T>& h) {
-        h.resize((size_t)(nx / grp_K_));
+        h.resize((size_t)(grp_ng_));
         BZ_HIP(hipMemcpy(h.data(), src, h.size() * sizeof(T), hipMemcpyDefault));
         for (size_t i = 0; i < h.size(); ++i)
             if (!(std::isfinite((double)h[i]) && h[i] >= T(0)))
-                throw Error(BZ_ERR_ARG, "NormL21: every entry of the vector lambda must be finite and >= 0 (entry " + std::to_string(i) + ")");
+                throw Error(BZ_ERR_ARG, std::string(gname()) + ": every entry of the vector lambda must be finite and >= 0 (entry " + std::to_string(i) + ")");
     }
     // NormL1's per-element lambda on a host copy: every entry finite and >= 0 (zeros are the unpenalised coefficients)
     void read_lambda_vec(const void* src, std::vector<T>& h) {
@@ -997,8 +1048,14 @@ template <class T> class Solver final : public SolverBase {
     int rows_per_chunk = 1, nrowchunks = 1;
     DBuf<T> FA_, fb_, FR_, DFX_, FGT_;       // dense f: matrix, vector, residual / Qx, gradient of f, A_f'r row-chunk partials
     bool dense_f = false, sparse_f = false, lp_g = false;      // (sparse_f: the sparse quadratic; sparse_ls: at the end)
-    bool group_g = false;                    // g = NormL21: kept on the kernel chain wherever lp_g is, k_fbstep_group its one kernel
+    bool group_g = false;                    // g = NormL21 or GroupLasso: kept on the kernel chain wherever lp_g is; k_fbstep_group / k_fbstep_ragged its one kernel
     int grp_K_ = 0, grp_KP_ = 0;             // ... its group size K and the power of two >= K
+    int64_t grp_ng_ = 0;                     // ... the number of groups (of both group kinds)
+    bool ragged_g = false;                   // g = GroupLasso (a group pointer; group_g holds too): k_fbstep_ragged its one kernel
+    std::vector<int64_t> grp_ptr_h_;         // ... ptr[ng + 1] on the host, validated
+    DBuf<int64_t> gptr_;                     // ... and on the device
+    int grp_L_ = 1;                          // ... lanes per group (ragged_lanes: from the mean size)
+    int64_t grp_max_ = 0, grp_swept_ = 0;    // ... the longest group; the elements in waves that sweep twice
     // generic oracles (host callbacks): host mirrors of the vectors the callbacks read and write
     bool generic_ = false;
     std::vector<T> hx_, hg_, hy_, hz_, hres_, hdfx_, hjtv_, hcx_, ht_, hs_, hmu_, hmuy_, hyv_;
@@ -1897,7 +1954,8 @@ template <class T> class Solver final : public SolverBase {
     // common kinds keep their register budget
     void fbstep(const T* x, const T* g, T gam, T* z, T* res, int slot0) {
         if (generic_) { fbstep_generic(x, g, gam, z, res, slot0); return; }
-        if (group_g) { fbstep_group(x, g, gam, z, res, slot0); return; }      // (no slack form with that kind)
+        if (ragged_g) { fbstep_ragged(x, g, gam, z, res, slot0); return; }
+        if (group_g) { fbstep_group(x, g, gam, z, res, slot0); return; }      // (no slack form with these kinds)
         if (slack_dense) {
             // one launch over the lifted vector, a section per half (k_fbstep_lifted)
             for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = lgx_ + lgs_;
@@ -1947,6 +2005,46 @@ template <class T> class Solver final : public SolverBase {
             }
         });
     }
+    // g = GroupLasso: k_fbstep_ragged<L, NT, L1, LONG>, L lanes per group from the mean size, LONG where a group exceeds the
+    // RAGGED_HOLD trips held in registers.  The streams k_fbstep counts, the pointer (and a vector lambda) once per group, and
+    // x and g a second time for the waves that sweep twice (grp_swept_)
+    void fbstep_ragged(const T* x, const T* g, T gam, T* z, T* res, int slot0) {
+        const int gg = group_grid(grp_ng_, grp_L_);
+        const T* lamv = P.group_lambda_vec();
+        const T l1 = (T)desc.g_l1;
+        for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = gg;
+        const int vs = 1 + (g ? 1 : 0) + 1 + (res ? 1 : 0);
+        mv(vs); if (lamv) mv(1, grp_ng_);
+        mv((double)sizeof(int64_t) / sizeof(T), grp_ng_ + 1);
+        mv(1 + (g ? 1 : 0), grp_swept_);
+        const bool nt = env_.nt >= 0 ? env_.nt != 0 : (double)n * sizeof(T) * vs > 340e6;
+        const bool lng = grp_max_ > (int64_t)RAGGED_HOLD * grp_L_;
+        const bool l1p = desc.g_l1 > 0;
+        with_bool(nt, [&](auto nt_) {
+            with_bool(l1p, [&](auto l1_) {
+                with_bool(lng, [&](auto lng_) {
+                    // (L = 1: every group has one element, lng is false; its LONG forms are not instantiated)
+                    auto go = [&](auto l_) {
+                        constexpr int L = decltype(l_)::value;
+                        launch(C_FB, k_fbstep_ragged<T, L, decltype(nt_)::value, decltype(l1_)::value, (decltype(lng_)::value && L > 1)>,
+                               gg, x, g, gam, P.g_lambda, lamv, l1, (const int64_t*)gptr_.p, z, res, grp_ng_, parts_.p, slot0);
+                    };
+#define BZ_RAGGED_NM(A) (nt ? (l1p ? (lng ? A "NT=1,L1=1,LONG=1>" : A "NT=1,L1=1,LONG=0>") : (lng ? A "NT=1,L1=0,LONG=1>" : A "NT=1,L1=0,LONG=0>")) \
+                               : (l1p ? (lng ? A "NT=0,L1=1,LONG=1>" : A "NT=0,L1=1,LONG=0>") : (lng ? A "NT=0,L1=0,LONG=1>" : A "NT=0,L1=0,LONG=0>")))
+                    switch (grp_L_) {
+                    case 1: nm(BZ_RAGGED_NM("k_fbstep_ragged<L=1,")); go(std::integral_constant<int, 1>{}); break;
+                    case 2: nm(BZ_RAGGED_NM("k_fbstep_ragged<L=2,")); go(std::integral_constant<int, 2>{}); break;
+                    case 4: nm(BZ_RAGGED_NM("k_fbstep_ragged<L=4,")); go(std::integral_constant<int, 4>{}); break;
+                    case 8: nm(BZ_RAGGED_NM("k_fbstep_ragged<L=8,")); go(std::integral_constant<int, 8>{}); break;
+                    case 16: nm(BZ_RAGGED_NM("k_fbstep_ragged<L=16,")); go(std::integral_constant<int, 16>{}); break;
+                    case 32: nm(BZ_RAGGED_NM("k_fbstep_ragged<L=32,")); go(std::integral_constant<int, 32>{}); break;
+                    default: nm(BZ_RAGGED_NM("k_fbstep_ragged<L=64,")); go(std::integral_constant<int, 64>{}); break;
+                    }
+#undef BZ_RAGGED_NM
+                });
+            });
+        });
+    }
     T al_value(double fsum, double pensum) const {   // auglagfun.jl:78,81-82
         T lx = T(0.5) * T(pensum);
         lx += f_value(fsum);
@@ -1962,6 +2060,10 @@ template <class T> class Solver final : public SolverBase {
             return P.g_lambda * T(gsum);
         case BZ_G_NORM_L21:
             if (P.group_lambda_vec()) return T(gsum);      // (the kernel summed lambda_j (scal nrm))
+            return P.g_lambda * T(gsum);
+        case BZ_G_GROUP_LASSO:
+            // (a vector lambda, or l1 > 0: the kernel summed the finished terms)
+            if (P.group_lambda_vec() || desc.g_l1 > 0) return T(gsum);
             return P.g_lambda * T(gsum);
         case BZ_G_CALLBACK: return T(gsum);      // the callback returned g(z) itself
         default: return T(0);

@@ -130,7 +130,8 @@ class Problem:
             self._iperm = np.argsort(self._perm)
         self.generic = desc.f_kind == L.BZ_F_CALLBACK
         # entries of a vector lambda: one per element, NormL21: one per group
-        self._nlam = self.nx // desc.g_group if desc.g_kind == L.BZ_G_NORM_L21 else self.nx
+        self._nlam = self.nx // desc.g_group if desc.g_kind == L.BZ_G_NORM_L21 else \
+            desc.g_ngroups if desc.g_kind == L.BZ_G_GROUP_LASSO else self.nx
         self._keep = keep if self.generic else None
         del keep
         self._h = h
@@ -162,9 +163,10 @@ class Problem:
         self._call(L.load().bz_problem_set_multipliers(self._h, mu.ctypes.data, y.ctypes.data))
 
     def set_g_lambda(self, lam):
-        """lambda of g = NormL1 / NormL1Nonneg / NormL1Box / NormL0Box / NormL21 between solves, without a new problem (a
+        """lambda of g = NormL1 / NormL1Nonneg / NormL1Box / NormL0Box / NormL21 / GroupLasso between solves, without a new problem (a
         path of fits on one upload of the matrices): a number for a problem created with a number, a vector of length n for
-        one created with NormL1(array), of one entry per group for one created with NormL21(array, group)."""
+        one created with NormL1(array), of one entry per group for one created with NormL21(array, group) or GroupLasso(array, indptr)
+        (whose l1 stays as created)."""
         if np.ndim(lam) == 0:
             self._call(L.load().bz_problem_set_g_lambda(self._h, float(lam), None))
         else:

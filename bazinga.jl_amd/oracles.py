@@ -759,6 +759,121 @@ class NormL21(ProximableFunction):
             return lam * np.sum(terms)
 
 
+class GroupLasso(ProximableFunction):
+    """The group Lasso over groups of unequal size, with an optional l1 mix (the sparse-group Lasso):
+    g(x) = l1 ||x||_1 + sum_j lambda_j ||x[indptr[j] : indptr[j+1]]||_2 over the contiguous groups a pointer cuts x into
+    (indptr[0] = 0, strictly increasing, indptr[-1] = len(x); any size >= 1).  lambda is a number, or a 1-D array with one
+    entry per GROUP (finite, >= 0; a zero leaves its group unpenalised: an intercept); l1 is a number, finite and >= 0.  No
+    reference class.  `prox` is the specification of the device kernel (k_fbstep_ragged), operation for operation in x's type:
+      l1 > 0:  t = gamma * l1 ; u_k = y_k - t where y_k > t, y_k + t where y_k < -t, y_k where it is a NaN, otherwise +0 (the
+               ties |y_k| = t included: a zero result is +0 whatever the sign of y_k).  l1 == 0: u = y, not evaluated (-0 stays -0)
+      q_k = u_k * u_k ; 64 accumulators a[p] = q[p] + q[p + 64] + q[p + 128] + ... in that order (positions past the group's end
+               absent), then NormL21.fold over the 64: a function of the group's size alone.  For a size <= 64 that is NormL21's
+               fold over the power of two >= the size (adding +0 to a square is exact), which is how it is evaluated here.
+      nrm = sqrt(s) ; gl = gamma * lambda_j ; nrm <= gl: z = 0, scal = 0 ; nrm > gl: scal = 1 - gl / nrm ; otherwise (a NaN)
+               scal = nrm - gl ; z_k = scal * u_k
+      the value: l1 == 0: NormL21's (sum_j lambda_j (scal nrm), a number lambda times the sum) ; l1 > 0: the sum of
+               lambda_j * (scal * nrm) + (l1 * scal) * sabs, sabs the sum of |u_k| in the same accumulator order."""
+
+    def __init__(self, lam=1.0, indptr=(0, 1), l1=0.0):
+        p = np.asarray(indptr)
+        if p.ndim != 1 or p.shape[0] < 2:
+            raise ValueError("indptr must be a 1-D array of at least two entries (one group)")
+        if p.dtype == np.bool_ or not np.issubdtype(p.dtype, np.integer):
+            raise ValueError("indptr must hold integers")
+        p = np.ascontiguousarray(p, dtype=np.int64)
+        if p[0] != 0:
+            raise ValueError("indptr must start at 0")
+        if np.any(np.diff(p) < 1):
+            raise ValueError("indptr must be strictly increasing (no empty group)")
+        self.indptr = p
+        self.ngroups = p.shape[0] - 1
+        if isinstance(l1, bool) or np.ndim(l1) != 0 or not (np.isfinite(l1) and l1 >= 0):
+            raise ValueError("parameter l1 must be a finite, nonnegative number")
+        self.l1 = float(l1)
+        if np.ndim(lam) == 0:
+            if not (np.isfinite(lam) and lam >= 0):
+                raise ValueError("parameter λ must be finite and nonnegative")
+            self.lam = float(lam)
+            return
+        lam = np.array(lam, dtype=np.float64)
+        if lam.ndim != 1:
+            raise ValueError("parameter λ must be a number or a 1-D array (one entry per group)")
+        if not np.all(np.isfinite(lam) & (lam >= 0)):
+            raise ValueError("parameter λ must have finite, nonnegative entries")
+        if lam.shape[0] != self.ngroups:
+            raise ValueError(f"λ must have one entry per group ({self.ngroups}), not {lam.shape[0]}")
+        self.lam = lam
+
+    @classmethod
+    def from_sizes(cls, lam, sizes, l1=0.0):
+        s = np.asarray(sizes)
+        if s.ndim != 1 or s.shape[0] < 1 or s.dtype == np.bool_ or not np.issubdtype(s.dtype, np.integer):
+            raise ValueError("sizes must be a 1-D array of integers, one per group")
+        return cls(lam, np.concatenate(([0], np.cumsum(s, dtype=np.int64))), l1)
+
+    @property
+    def sizes(self):
+        return np.diff(self.indptr)
+
+    def _check(self, x):
+        if x.ndim != 1 or x.shape[0] != self.indptr[-1]:
+            raise ValueError(f"the length of x ({x.shape}) must be indptr[-1] = {self.indptr[-1]}")
+
+    def __call__(self, x):
+        x = np.asarray(x)
+        self._check(x)
+        v = np.sum(self.lam * np.sqrt(np.add.reduceat(x * x, self.indptr[:-1])))
+        if self.l1 > 0:
+            v = v + self.l1 * np.sum(np.abs(x))
+        return v
+
+    def group_sums(self, q):
+        """the 64-accumulator sum of every group of q (nonnegative entries or NaNs), bucket by bucket: groups of up to 64 by the
+        fold of their power of two, longer ones by their number of 64-element batches"""
+        p, size = self.indptr, self.sizes
+        s = np.empty(self.ngroups, q.dtype)
+        nb = (size + 63) // 64
+        kp = np.where(nb == 1, 2 ** np.ceil(np.log2(size)).astype(np.int64), 64)
+        for b, w in sorted({(int(b_), int(w_)) for b_, w_ in zip(nb.tolist(), kp.tolist())}):
+            G = np.flatnonzero((nb == b) & (kp == w))
+            off = np.arange(b * w)
+            on = off[None, :] < size[G, None]
+            idx = p[G, None] + np.minimum(off[None, :], size[G, None] - 1)
+            qq = np.where(on, q[idx], q.dtype.type(0)).reshape(G.shape[0], b, w)
+            a = qq[:, 0, :]
+            for c in range(1, b):
+                a = a + qq[:, c, :]
+            s[G] = NormL21.fold(a)
+        return s
+
+    def prox(self, z, x, gamma):
+        T = x.dtype.type
+        self._check(x)
+        vec = np.ndim(self.lam) != 0
+        lam = np.asarray(self.lam, dtype=x.dtype) if vec else T(self.lam)
+        size = self.sizes
+        with np.errstate(all="ignore"):
+            if self.l1 > 0:
+                t = T(gamma) * T(self.l1)
+                u = np.where(x > t, x - t, np.where(x < -t, x + t, np.where(np.isnan(x), x, T(0)))).astype(x.dtype)
+            else:
+                u = x
+            nrm = np.sqrt(self.group_sums(u * u))
+            gl = T(gamma) * lam
+            zero = nrm <= gl
+            big = nrm > gl
+            scal = np.where(zero, T(0), np.where(big, T(1) - gl / nrm, nrm - gl)).astype(x.dtype)
+            z[...] = np.where(np.repeat(zero, size), T(0), np.repeat(scal, size) * u)
+            terms = scal * nrm
+            if self.l1 > 0:
+                sabs = self.group_sums(np.abs(u))
+                return np.sum(lam * terms + (T(self.l1) * scal) * sabs)
+            if vec:
+                return np.sum(lam * terms)
+            return lam * np.sum(terms)
+
+
 class NormL1Nonneg(ProximableFunction):
     """src/proxoperators/normL1Nonneg.jl:9-42"""
 
@@ -1060,7 +1175,7 @@ def _vec(a, dtype, n, name):
 
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, SparseLeastSquares,
                                       SparseLogistic, SparseGLM, SparseMultinomial, Stencil5ptQuadratic))
-_LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL21, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
+_LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL21, GroupLasso, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
 _LOWERED_D = lambda D: isinstance(D, (ZeroSet, FreeSet, PairwiseSet)) or \
@@ -1294,6 +1409,20 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
             d.g_lambda = g.lam
         else:
             d.g_lambda_vec = ptr(_vec(g.lam, dtype, n // g.group, "λ"))
+    elif isinstance(g, GroupLasso):
+        # what the library refuses with this kind, refused here before any device call
+        if slack:
+            raise UnsupportedOracle("GroupLasso is not lowered in the slack (ALS) form")
+        if perm is not None:
+            raise UnsupportedOracle("GroupLasso is not lowered beside a split-layout pairwise set (the groups would be permuted)")
+        if g.indptr[-1] != n:
+            raise ValueError(f"indptr[-1] = {g.indptr[-1]} must be n = {n}")
+        d.g_kind, d.g_ngroups, d.g_l1 = L.BZ_G_GROUP_LASSO, g.ngroups, g.l1
+        d.g_group_ptr = ptr(g.indptr)
+        if np.ndim(g.lam) == 0:
+            d.g_lambda = g.lam
+        else:
+            d.g_lambda_vec = ptr(_vec(g.lam, dtype, g.ngroups, "λ"))
     elif isinstance(g, NormL1Nonneg):
         d.g_kind, d.g_lambda = L.BZ_G_NORM_L1_NONNEG, g.lam
     elif isinstance(g, NormL1Box):

@@ -143,6 +143,21 @@ extern "C" {
                                     g(z) is lambda_j * (scal * nrm).  A NaN makes its own group NaN and nothing else; an infinite
                                     element gives z = y.  Every f, c and D of the kernel chain, slack = 0, one rank; refused
                                     (BZ_ERR_UNSUPPORTED): slack = 1, more than one rank, callbacks mixed in.                   */
+#define BZ_G_GROUP_LASSO     10  /* The group Lasso over a group pointer, with an optional l1 mix:
+                                    g(x) = l1 ||x||_1 + sum_j lambda_j ||x[ptr[j] : ptr[j+1]]||_2, ptr = g_group_ptr[0 .. g_ngroups],
+                                    ptr[0] = 0, strictly increasing, ptr[g_ngroups] = n: contiguous groups of any size >= 1 (2^30
+                                    at the most).  lambda is g_lambda, or g_lambda_vec with one entry per GROUP (finite, >= 0; a
+                                    zero leaves its group unpenalised); l1 = g_l1 (finite, >= 0), fixed at creation.  No reference
+                                    class.  The prox of one group, y the argument, all in the problem's type: with l1 > 0,
+                                    t = gamma * l1 and u_k = y_k - t (y_k > t), y_k + t (y_k < -t), y_k (a NaN), otherwise +0;
+                                    with l1 == 0, u = y and the threshold is not evaluated (-0 stays -0).  q_k = u_k * u_k ;
+                                    64 accumulators a[p] = q[p] + q[p + 64] + q[p + 128] + ... in that order (positions past the
+                                    group's end absent), then the fixed fold a[:o] + a[o:2o] for o = 32 .. 1 gives s — for a size
+                                    <= 64 the sum of BZ_G_NORM_L21 ; nrm = sqrt(s) ; gl = gamma * lambda_j ; nrm <= gl: z = 0,
+                                    scal = 0 ; nrm > gl: scal = 1 - gl / nrm ; otherwise (a NaN) scal = nrm - gl ; z_k = scal * u_k.
+                                    The group's term of g(z) is lambda_j * (scal * nrm), and with l1 > 0 also (l1 * scal) * the
+                                    sum of |u_k| in the same accumulator order.  Every f, c and D of the kernel chain, slack = 0,
+                                    one rank; refused (BZ_ERR_UNSUPPORTED): slack = 1, more than one rank, callbacks mixed in.  */
 /* c: constraint map.  eval!(cx,c,x), jtprod!(jtv,c,x,v)                             */
 #define BZ_C_IDENTITY        0   /* test/definitions/identityFunction.jl:3-13         */
 #define BZ_C_DENSE_AFFINE    1   /* A x - b, demo/basispursuit.jl:38-49               */
@@ -264,16 +279,20 @@ typedef struct {
     int64_t     f_rows;
     int64_t     f_classes;         /* SPARSE_MULTINOMIAL alone: K, 2 <= K <= 64 (x is n / K rows of K); the other kinds ignore it */
     /* g */
-    double      g_lambda;          /* NORM_L1*, NORM_L0_BOX, NORM_L21: lambda >= 0; NORM_LP_*: alpha */
+    double      g_lambda;          /* NORM_L1*, NORM_L0_BOX, NORM_L21, GROUP_LASSO: lambda >= 0; NORM_LP_*: alpha */
     double      g_p;               /* NORM_LP_*: exponent p in (0,1)                  */
     int64_t     g_group;           /* NORM_L21 alone: K, 1 <= K <= 64, n % K == 0 (x is n / K groups of K); the other kinds ignore it */
     const void* g_u;               /* NORM_L1_BOX / NORM_L0_BOX / NORM_LP_BOX: u[n] >= 0 */
+    const int64_t* g_group_ptr;    /* GROUP_LASSO alone: ptr[g_ngroups + 1], ptr[0] = 0 < ptr[1] < ... < ptr[g_ngroups] = n (copied at
+                                      creation).  Non-NULL beside any other g kind: BZ_ERR_ARG                                 */
+    int64_t     g_ngroups;         /* GROUP_LASSO alone: the number of groups, 1 .. n; the other kinds ignore it              */
+    double      g_l1;              /* GROUP_LASSO alone: l1 >= 0, the weight of ||x||_1 (0: the pure group penalty); the other kinds ignore it */
     double      g_lo, g_hi;        /* IND_BOX scalar bounds                           */
     const void* g_lo_vec;          /* IND_BOX vector bounds (or NULL)                 */
     const void* g_hi_vec;
     const void* g_lambda_vec;      /* NORM_L1 alone: lambda[n] >= 0 (finite; zeros allowed: an unpenalised coefficient), g(x) =
                                       sum lambda_i |x_i|, or NULL; g_lambda is ignored beside it.  In the slack form n entries,
-                                      the x half.  NORM_L21: lambda[n / g_group] >= 0, one entry per group, under the same rules.
+                                      the x half.  NORM_L21: lambda[n / g_group] >= 0, GROUP_LASSO: lambda[g_ngroups] >= 0, one entry per group, under the same rules.
                                       Any other g kind with a vector: BZ_ERR_ARG                                               */
     /* c */
     const void* c_A;               /* DENSE_AFFINE: A[ny][n] row-major                */
@@ -436,8 +455,8 @@ typedef struct {
 int bz_problem_set_multipliers(bz_problem* p, const void* mu, const void* y);
 
 /* lambda of a live problem, between solves (a path of Lasso fits on one upload of the matrices): g NORM_L1, NORM_L1_NONNEG,
- * NORM_L1_BOX, NORM_L0_BOX or NORM_L21.  A problem created with a number takes lambda (>= 0) and lambda_vec == NULL; one created
- * with g_lambda_vec takes a non-NULL lambda_vec[n] (NORM_L21: [n / g_group]), validated as at creation, which overwrites the
+ * NORM_L1_BOX, NORM_L0_BOX, NORM_L21 or GROUP_LASSO (whose l1 stays as created).  A problem created with a number takes lambda (>= 0) and lambda_vec == NULL; one created
+ * with g_lambda_vec takes a non-NULL lambda_vec[n] (NORM_L21: [n / g_group], GROUP_LASSO: [g_ngroups]), validated as at creation, which overwrites the
  * device copy (lambda is ignored).  Number <-> vector would change the kernel forms the problem runs and stays a creation-time decision:
  * BZ_ERR_ARG, as for any other g kind.  Between bz_panoc_begin and bz_panoc_finish: BZ_ERR_STATE.                         */
 int bz_problem_set_g_lambda(bz_problem* p, double lambda, const void* lambda_vec);

@@ -29,7 +29,9 @@ Base.@kwdef mutable struct ProblemDesc
     f_q::Ptr{Cvoid} = C_NULL; f_b::Ptr{Cvoid} = C_NULL; f_grid_nx::Int64 = 0; f_grid_ny::Int64 = 0
     f_A::Ptr{Cvoid} = C_NULL; f_rows::Int64 = 0
     f_classes::Int64 = 0                  # f = SparseMultinomial (BZ_F_SPARSE_MULTINOMIAL) alone: K, x is n / K rows of K
-    g_lambda::Float64 = 0; g_p::Float64 = 0; g_group::Int64 = 0; g_u::Ptr{Cvoid} = C_NULL; g_lo::Float64 = 0; g_hi::Float64 = 0
+    g_lambda::Float64 = 0; g_p::Float64 = 0; g_group::Int64 = 0; g_u::Ptr{Cvoid} = C_NULL
+    g_group_ptr::Ptr{Cvoid} = C_NULL; g_ngroups::Int64 = 0; g_l1::Float64 = 0   # g = GroupLasso (BZ_G_GROUP_LASSO) alone
+    g_lo::Float64 = 0; g_hi::Float64 = 0
     g_lo_vec::Ptr{Cvoid} = C_NULL; g_hi_vec::Ptr{Cvoid} = C_NULL; g_lambda_vec::Ptr{Cvoid} = C_NULL
     c_A::Ptr{Cvoid} = C_NULL; c_b::Ptr{Cvoid} = C_NULL
     D_lo::Float64 = 0; D_hi::Float64 = 0; D_lo_vec::Ptr{Cvoid} = C_NULL; D_hi_vec::Ptr{Cvoid} = C_NULL
@@ -303,6 +305,43 @@ function ProximalOperators.prox!(z, g::NormL21, x, gamma)
     return gz
 end
 
+"""`GroupLasso(λ, sizes; l1 = 0)`: the group Lasso over groups of unequal size with an optional ℓ1 mix,
+g(x) = l1 ‖x‖₁ + Σ_j λ_j ‖x[group j]‖₂, the groups contiguous and `sizes[j]` ≥ 1 long, Σ sizes = length(x) (BZ_G_GROUP_LASSO).  λ is a
+number, or a vector with one entry per group in the problem's type (finite, ≥ 0; a zero leaves its group unpenalised: an
+intercept); l1 is a number ≥ 0, fixed once the problem is created.  The object holds the 0-based Int64 group pointer the
+library reads; it and a vector λ must stay alive until bz_problem_create returns."""
+struct GroupLasso{L} <: Bazinga.ProximableFunction
+    lambda::L; ptr::Vector{Int64}; l1::Float64
+    function GroupLasso(lambda::L, sizes::AbstractVector{<:Integer}; l1::Real = 0) where {L<:Union{Real,AbstractVector{<:Real}}}
+        !isempty(sizes) && all(>=(1), sizes) || throw(ArgumentError("every group must hold at least one element"))
+        all(v -> isfinite(v) && v >= 0, lambda) || throw(ArgumentError("λ must be finite and nonnegative"))
+        lambda isa Real || length(lambda) == length(sizes) || throw(ArgumentError("λ must have one entry per group"))
+        isfinite(l1) && l1 >= 0 || throw(ArgumentError("l1 must be finite and nonnegative"))
+        new{L}(lambda, Int64[0; cumsum(Int64.(sizes))], Float64(l1))
+    end
+end
+# the definition of include/bazinga_hip.h, group by group (the host twin of k_fbstep_ragged, to rounding: the sums here are
+# Julia's, not the kernel's 64 accumulators)
+function ProximalOperators.prox!(z, g::GroupLasso, x, gamma)
+    length(x) == g.ptr[end] || throw(ArgumentError("length(x) must be the sum of the group sizes"))
+    T = eltype(x); gz = zero(T); t = T(gamma) * T(g.l1)
+    soft(y) = g.l1 > 0 ? (y > t ? y - t : (y < -t ? y + t : (isnan(y) ? y : zero(T)))) : y
+    for j in 1:(length(g.ptr) - 1)
+        r = (g.ptr[j] + 1):g.ptr[j + 1]
+        lam = T(g.lambda isa Real ? g.lambda : g.lambda[j])
+        u = soft.(view(x, r))
+        nrm = sqrt(sum(abs2, u)); gl = T(gamma) * lam
+        if nrm <= gl
+            z[r] .= zero(T)
+        else
+            scal = nrm > gl ? one(T) - gl / nrm : nrm - gl
+            z[r] .= scal .* u
+            gz += lam * (scal * nrm) + T(g.l1) * scal * sum(abs, u)
+        end
+    end
+    return gz
+end
+
 "`LBFGS(M; compact = nothing)`: how the operator is evaluated (bz_panoc_opts.lbfgs_compact) — `false` the two-loop recursion in the reference's order, `true` the compact representation, `nothing` (default) compact where the one-pass kernel applies"
 struct LBFGS
     memory::Int; compact::Union{Nothing,Bool}
@@ -361,6 +400,9 @@ lower_g!(d, g::Bazinga.NormL1Nonneg) = (d.g_kind = 2; d.g_lambda = g.lambda)
 # (the group Lasso: one weight per GROUP with a vector; n % group and the slack form are checked by bz_problem_create)
 lower_g!(d, g::NormL21{<:Real}) = (d.g_kind = 9; d.g_group = g.group; d.g_lambda = g.lambda)
 lower_g!(d, g::NormL21{<:AbstractVector}) = (d.g_kind = 9; d.g_group = g.group; d.g_lambda_vec = pointer(g.lambda))
+# (the group Lasso over a group pointer: the pointer is the object's own; ptr[end] == n and the slack form are checked by bz_problem_create)
+lower_g!(d, g::GroupLasso{<:Real}) = (d.g_kind = 10; d.g_group_ptr = pointer(g.ptr); d.g_ngroups = length(g.ptr) - 1; d.g_l1 = g.l1; d.g_lambda = g.lambda)
+lower_g!(d, g::GroupLasso{<:AbstractVector}) = (d.g_kind = 10; d.g_group_ptr = pointer(g.ptr); d.g_ngroups = length(g.ptr) - 1; d.g_l1 = g.l1; d.g_lambda_vec = pointer(g.lambda))
 lower_g!(d, g::Bazinga.NormL1Box) = (d.g_kind = 3; d.g_lambda = g.lambda; d.g_u = pointer(g.u))
 lower_g!(d, g::ProximalOperators.IndBox{<:Real,<:Real}) = (d.g_kind = 4; d.g_lo = g.lb; d.g_hi = g.ub)
 lower_g!(d, g::Bazinga.NormL0Box) = (d.g_kind = 5; d.g_lambda = g.lambda; d.g_u = pointer(g.u))
@@ -482,7 +524,7 @@ mutable struct Problem
     end
 end
 
-# lambda of g (NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormL21) between solves, on the live problem: a number for a problem
+# lambda of g (NormL1, NormL1Nonneg, NormL1Box, NormL0Box, NormL21, GroupLasso) between solves, on the live problem: a number for a problem
 # lowered from a number, a vector (the problem's type, length n; NormL21: one entry per group) for one lowered from an array
 set_g_lambda!(p::Problem, lambda::Real) = check(ccall((:bz_problem_set_g_lambda, lib), Cint,
     (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), p.h, lambda, C_NULL))

@@ -11,6 +11,11 @@
 2. The solve: synth.sparse_multinomial(m, n_f, K = 8, k = 5) with g = NormL21(0.1, 8) beside g = NormL1(0.1) — the run of
    tools/bench_sparse_multinomial.py — iterations per second (warm-up, then `repeats` timed calls of bz_panoc_steps).
 
+3. With --ragged, instead: the group Lasso over a group pointer (BZ_G_GROUP_LASSO, k_fbstep_ragged) at n = 10^7, fp64, in one
+   session — all groups of 8 beside k_fbstep_group<KP=8> on the same vectors, sizes drawn uniformly from 1 .. 16, groups of 200,
+   and each of the three with l1 > 0 beside l1 = 0; `repeats` runs of `steps` launches each, the median and the range.  Written to
+   <out>/group_lasso_ragged.json.
+
 Prints ONE JSON line and writes it to <out>/group_lasso.json.  Every GPU step is a child process under a time limit of its own;
 the first one that fails ends the run."""
 import argparse
@@ -50,6 +55,37 @@ def fb_kernel(bz, g, d, n, dtype, steps):
             "n_fused_iters": int(st.n_fused_iters)}
 
 
+def ragged_case(bz, g, d, n, steps, repeats):
+    """`repeats` runs of fb_kernel: the median, the range, the byte-model fraction at the median"""
+    runs = [fb_kernel(bz, g, d, n, np.float64, steps) for _ in range(repeats)]
+    us = sorted(r["avg_us"] for r in runs)
+    med = us[len(us) // 2]
+    return {"form_of_last_launch": runs[0]["form_of_last_launch"], "avg_us_median": med, "avg_us_range": [us[0], us[-1]],
+            "bytes_per_launch": runs[0]["bytes_per_launch"], "fraction_of_8TBs_at_median": runs[0]["bytes_per_launch"] / (med * 1e-6) / HBM_PEAK,
+            "n_fused_iters": runs[0]["n_fused_iters"]}
+
+
+def ragged_worker(bz, args):
+    n = args.n // 200 * 200                                 # (a multiple of 8 and of 200)
+    d = bz.synth.l1_quadratic(args.n, dtype=np.float64)
+    lam = float(d["lam"])
+    rng = np.random.default_rng(0)
+    drawn = rng.integers(1, 17, n // 8)
+    drawn = drawn[:np.searchsorted(np.cumsum(drawn), n)]
+    drawn = np.append(drawn, n - drawn.sum()) if drawn.sum() < n else drawn
+    shapes = {"uniform8": np.full(n // 8, 8), "drawn_1_16": drawn, "uniform200": np.full(n // 200, 200)}
+    res = {"n": n, "dtype": "float64", "steps": args.steps, "repeats": args.repeats, "l1": 0.25 * lam, "lambda": lam,
+           "norm_l21_K8": ragged_case(bz, bz.NormL21(lam, 8), d, n, args.steps, args.repeats)}
+    for name, sizes in shapes.items():
+        assert sizes.sum() == n and sizes.min() >= 1
+        res[name] = {"groups": int(sizes.shape[0]), "largest": int(sizes.max()),
+                     "l1=0": ragged_case(bz, bz.GroupLasso.from_sizes(lam, sizes), d, n, args.steps, args.repeats),
+                     "l1>0": ragged_case(bz, bz.GroupLasso.from_sizes(lam, sizes, 0.25 * lam), d, n, args.steps, args.repeats)}
+        res[name]["l1_over_pure"] = res[name]["l1>0"]["avg_us_median"] / res[name]["l1=0"]["avg_us_median"]
+    res["uniform8_over_norm_l21"] = res["uniform8"]["l1=0"]["avg_us_median"] / res["norm_l21_K8"]["avg_us_median"]
+    return res
+
+
 def run_solve(bz, f, g, dtype, steps, warmup, repeats):
     n = f.n
     prob = bz.Problem(f, g, bz.IdentityFunction(), bz.FreeSet(), n, n, dtype)
@@ -74,7 +110,9 @@ def run_solve(bz, f, g, dtype, steps, warmup, repeats):
 def worker(args):
     import bazinga_jl_amd as bz
     res = {}
-    if args.worker.startswith("k"):
+    if args.worker == "ragged":
+        res = ragged_worker(bz, args)
+    elif args.worker.startswith("k"):
         K = int(args.worker[1:])
         n = args.n // K * K
         res = {"K": K, "n": n}
@@ -98,7 +136,7 @@ def worker(args):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--worker", default=None, help="k<K>: the kernel comparison at group size K ; solve: the multinomial solves")
+    ap.add_argument("--worker", default=None, help="k<K>: the kernel comparison at group size K ; solve: the multinomial solves ; ragged: the group-pointer kind")
     ap.add_argument("--n", type=int, default=10_000_000)
     ap.add_argument("--groups", default=",".join(str(k) for k in GROUPS))
     ap.add_argument("--m", type=int, default=5_000_000)
@@ -108,6 +146,7 @@ def main():
     ap.add_argument("--warmup", type=int, default=20)
     ap.add_argument("--repeats", type=int, default=5)
     ap.add_argument("--no-solve", action="store_true", help="the kernel comparison alone")
+    ap.add_argument("--ragged", action="store_true", help="the group Lasso over a group pointer instead (group_lasso_ragged.json)")
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles"))
     ap.add_argument("--commit", default=None, help="the commit of the measured tree, recorded with the result")
     ap.add_argument("--limit", type=int, default=600, help="seconds per child process")
@@ -121,6 +160,13 @@ def main():
         opts = {"--n": args.n, "--m": args.m, "--nf": args.nf, "--k": args.k, "--steps": args.steps, "--warmup": args.warmup, "--repeats": args.repeats}
         return [sys.executable, os.path.abspath(__file__), "--worker", kind] + [str(v) for kv in opts.items() for v in kv]
     env = dict(os.environ)
+    if args.ragged:
+        res = {"commit": args.commit or commit_of_tree(), "ragged": run_child(cmd("ragged"), env, args.limit)}
+        line = json.dumps(res)
+        print(line)
+        with open(os.path.join(args.out, "group_lasso_ragged.json"), "w") as fh:
+            fh.write(line + "\n")
+        return
     res = {"commit": args.commit or commit_of_tree(), "kernel": {}}
     for K in args.groups.split(","):
         res["kernel"]["K" + K] = run_child(cmd("k" + K), env, args.limit)
