@@ -3,7 +3,13 @@
 Both are EXTERNAL, UN-PINNED algorithms (ProximalAlgorithms.jl is not vendored and has no pinned version) that no shipped
 script selects (rosenbrock.jl:275 picks LBFGS); the oracle restates them from the published methods (oracle/
 bazinga_ref.py: AndersonAcceleration, Broyden) — PARITY UNPINNED.  What is checked: the device follows that restatement,
-and the solves end where L-BFGS solves end."""
+and the solves end where L-BFGS solves end.
+
+These three tests are the first look; tests/test_gpu_directions_table.py is the table: both directions over every path they
+ride (one-pass families in both history forms, kernel chain, stencil, dense and sparse c, group and Lp g, slack form),
+memories 1 to 5, fp64 and fp32, gamma halvings, tau backtracks, kept pairs with <s, y> <= 0, every theta branch, Broyden's
+chunk plans up to n = 4096 — Anderson against a twin of the restatement that solves the device's normal equations, so
+without the 1e-6 used here."""
 import warnings
 
 import numpy as np
