@@ -182,6 +182,19 @@ template <class F> static void with_uni(int u, F&& f) {
     else if (u == 1) f(std::integral_constant<int, 1>{});
     else f(std::integral_constant<int, 0>{});
 }
+// ... or the mode of a row-wise sparse f's pass over A_f (SparseRowF::mode)
+template <class F> static void with_sparse_f_mode(int mode, F&& f) {
+    switch (mode) {
+    case SP_LS_R: f(std::integral_constant<int, SP_LS_R>{}); break;
+    case SP_LOGIT_R: f(std::integral_constant<int, SP_LOGIT_R>{}); break;
+    case SP_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES>{}); break;
+    case SP_GLM_MODE0 + BZ_LOSS_LOGISTIC: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_LOGISTIC>{}); break;
+    case SP_GLM_MODE0 + BZ_LOSS_HUBER: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_HUBER>{}); break;
+    case SP_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE>{}); break;
+    case SP_GLM_MODE0 + BZ_LOSS_POISSON: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_POISSON>{}); break;
+    default: f(std::integral_constant<int, SPMM_SOFTMAX>{}); break;
+    }
+}
 
 template <class T> class Solver final : public SolverBase {
    public:
@@ -264,83 +277,32 @@ template <class T> class Solver final : public SolverBase {
             if (n > (int64_t)std::numeric_limits<int32_t>::max())
                 throw Error(BZ_ERR_ARG, "SparseQuadratic: n must fit 32-bit column indices");
         }
-        sparse_ls = d.f_kind == BZ_F_SPARSE_LEAST_SQUARES;
-        if (sparse_ls) {
-            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: the slack (ALS) form is not lowered with a sparse least-squares f");
-            if (d.c_kind == BZ_C_DENSE_AFFINE)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: a sparse least-squares f beside a dense c (DenseAffine) is not lowered");
-            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: the sparse least-squares f is not sharded (one rank)");
-            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseLeastSquares: the sparse least-squares f does not mix with host callbacks");
-            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
-                throw Error(BZ_ERR_ARG, "SparseLeastSquares needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and b[m]");
-            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
-                throw Error(BZ_ERR_ARG, "SparseLeastSquares: n and m must fit 32-bit indices");
-        }
-        sparse_logit = d.f_kind == BZ_F_SPARSE_LOGISTIC;
-        if (sparse_logit) {
-            // (from here on the logistic f is a `sparse_ls` problem whose first launch has another epilogue)
-            sparse_ls = true;
-            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: the slack (ALS) form is not lowered with a sparse logistic f");
-            if (d.c_kind == BZ_C_DENSE_AFFINE)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: a sparse logistic f beside a dense c (DenseAffine) is not lowered");
-            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: the sparse logistic f is not sharded (one rank)");
-            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseLogistic: the sparse logistic f does not mix with host callbacks");
-            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
-                throw Error(BZ_ERR_ARG, "SparseLogistic needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and the labels b[m]");
-            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
-                throw Error(BZ_ERR_ARG, "SparseLogistic: n and m must fit 32-bit indices");
-        }
-        sparse_glm = d.f_kind == BZ_F_SPARSE_GLM;
-        if (sparse_glm) {
-            // (a `sparse_ls` problem too; the plain least-squares and logistic losses run the epilogues of kinds 7 and 8)
-            sparse_ls = true;
-            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: the slack (ALS) form is not lowered with a sparse GLM f");
-            if (d.c_kind == BZ_C_DENSE_AFFINE)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: a sparse GLM f beside a dense c (DenseAffine) is not lowered");
-            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: the sparse GLM f is not sharded (one rank)");
-            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseGLM: the sparse GLM f does not mix with host callbacks");
-            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
-                throw Error(BZ_ERR_ARG, "SparseGLM needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and b[m]");
-            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
-                throw Error(BZ_ERR_ARG, "SparseGLM: n and m must fit 32-bit indices");
-            if (d.f_loss < BZ_LOSS_LEAST_SQUARES || d.f_loss > BZ_LOSS_POISSON)
-                throw Error(BZ_ERR_ARG, "SparseGLM: f_loss must be one of BZ_LOSS_* (0 .. 4)");
-            if (d.f_loss == BZ_LOSS_HUBER && !(std::isfinite(d.f_loss_delta) && d.f_loss_delta > 0))
-                throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0");
-            if (!(std::isfinite(d.f_scale) && d.f_scale > 0))
-                throw Error(BZ_ERR_ARG, "SparseGLM: f_scale must be finite and > 0 (1 for the plain sum)");
-            glm_loss_ = d.f_loss;
-            // without weights and with scale 1 the least-squares and logistic losses ARE kinds 7 and 8
-            glm_weighted_ = d.f_w != nullptr || d.f_scale != 1.0;
-            sparse_logit = d.f_loss == BZ_LOSS_LOGISTIC && !glm_weighted_;
-        }
+        // a row-wise sparse f (`sparse_ls`): one row of SPARSE_ROW_F, one set of checks
+        for (const SparseRowF& k : SPARSE_ROW_F)
+            if (k.f_kind == d.f_kind) { spf_ = k; sparse_ls = true; }
         sparse_mn = d.f_kind == BZ_F_SPARSE_MULTINOMIAL;
-        if (sparse_mn) {
-            // (a `sparse_ls` problem whose three row launches are the K-wide kernels of bz_spmm.h; x is n / K rows of K)
-            sparse_ls = true;
-            if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: the slack (ALS) form is not lowered with a sparse multinomial f");
-            if (d.c_kind == BZ_C_DENSE_AFFINE)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: a sparse multinomial f beside a dense c (DenseAffine) is not lowered");
-            if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: the sparse multinomial f is not sharded (one rank)");
-            if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
-                throw Error(BZ_ERR_UNSUPPORTED, "SparseMultinomial: the sparse multinomial f does not mix with host callbacks");
-            if (d.f_classes < 2 || d.f_classes > 64)
-                throw Error(BZ_ERR_ARG, "SparseMultinomial: f_classes = K must be in 2 .. 64");
-            if (n % d.f_classes != 0)
-                throw Error(BZ_ERR_ARG, "SparseMultinomial: n must be a multiple of f_classes (x is n / K rows of K)");
-            if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
-                throw Error(BZ_ERR_ARG, "SparseMultinomial needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and the labels b[m]");
-            // (32-bit: the column indices of A_f, below n / K, and of A_f', below m; an index into X or R is formed in 64 bits)
-            if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
-                throw Error(BZ_ERR_ARG, "SparseMultinomial: n and m must fit 32-bit indices");
-            if (!(std::isfinite(d.f_scale) && d.f_scale > 0))
-                throw Error(BZ_ERR_ARG, "SparseMultinomial: f_scale must be finite and > 0 (1 for the plain sum)");
-            mn_K_ = (int)d.f_classes;
-            mn_KP_ = 2;
-            while (mn_KP_ < mn_K_) mn_KP_ *= 2;
+        if (sparse_ls) {
+            sparse_rowwise_check(d);
+            if (d.f_kind == BZ_F_SPARSE_GLM) {
+                if (d.f_loss < BZ_LOSS_LEAST_SQUARES || d.f_loss > BZ_LOSS_POISSON)
+                    throw Error(BZ_ERR_ARG, "SparseGLM: f_loss must be one of BZ_LOSS_* (0 .. 4)");
+                if (d.f_loss == BZ_LOSS_HUBER && !(std::isfinite(d.f_loss_delta) && d.f_loss_delta > 0))
+                    throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0");
+            }
+            if (spf_.weighted && !(std::isfinite(d.f_scale) && d.f_scale > 0))
+                throw Error(BZ_ERR_ARG, std::string(spf_.name) + ": f_scale must be finite and > 0 (1 for the plain sum)");
+            if (d.f_kind == BZ_F_SPARSE_GLM) {
+                // the mode follows the loss; without weights and with scale 1 the least-squares and logistic losses ARE the plain
+                // kinds and take their epilogues
+                spf_.weighted = d.f_w != nullptr || d.f_scale != 1.0 || d.f_loss >= BZ_LOSS_HUBER;
+                spf_.mode = spf_.weighted ? SP_GLM_MODE0 + (int)d.f_loss : d.f_loss == BZ_LOSS_LOGISTIC ? SP_LOGIT_R : SP_LS_R;
+            }
+            if (sparse_mn) {
+                // (the three row launches are the K-wide kernels of bz_spmm.h; x is n / K rows of K)
+                mn_K_ = (int)d.f_classes;
+                mn_KP_ = 2;
+                while (mn_KP_ < mn_K_) mn_KP_ *= 2;
+            }
         }
         if (d.c_kind == BZ_C_SPARSE_AFFINE) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseAffine: the slack (ALS) form is not lowered with a sparse c");
@@ -489,16 +451,16 @@ template <class T> class Solver final : public SolverBase {
             FR_.alloc(nx);
         }
         if (sparse_ls) {
-            // (the generic kernel chain too; the value convention of the dense LeastSquares: sum r^2, halved by fscale ;
-            // the logistic f: the plain sum of the rows' losses)
+            // (the generic kernel chain too; the two least-squares modes keep the value convention of the dense LeastSquares: sum
+            // r^2, halved by fscale ; every other mode: the plain sum of the rows' losses)
             frows = d.f_rows;
             sparse_ls_create(d);
             upload(fb_, d.f_b, frows);
             FR_.alloc(sparse_mn ? frows * mn_K_ : frows);                   // (the multinomial f: R is m rows of K)
             if (d.c_kind == BZ_C_SPARSE_AFFINE || !spls_fused_on()) DFX_.alloc(nx);
-            fscale = sparse_logit || sparse_mn || (sparse_glm && glm_loss_ != BZ_LOSS_LEAST_SQUARES) ? T(1) : T(0.5);
+            fscale = spf_.mode == SP_LS_R || spf_.mode == SP_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES ? T(0.5) : T(1);
             if (sparse_mn) mn_labels_check(d);
-            if (sparse_glm || sparse_mn) glm_weights_create(d);
+            if (d.f_kind == BZ_F_SPARSE_GLM || sparse_mn) glm_weights_create(d);
         }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             A_.alloc((size_t)ny * nx);
@@ -2090,7 +2052,9 @@ template <class T> class Solver final : public SolverBase {
     };
     SpCsr spA_, spAt_, spQ_;               // (Q: the sparse quadratic f; symmetric, so no transpose)
     DBuf<int64_t> spQ_rowptr_;             // a cut Q: the row pointers as given (k_spmv_q_algrad walks rows, not virtual rows)
-    std::string sp_form_[4];               // by the epilogue's MODE (MODE 4 .. 6: spls_form_ ; MODE 7: splogit_form_)
+    // the profile labels of the row launches by the epilogue's MODE (SPMM_SOFTMAX's behind the others), filled at creation
+    static constexpr int sp_label_at(int mode) { return mode == SPMM_SOFTMAX ? SP_NMODES : mode; }
+    std::string sp_label_[SP_NMODES + 1];
     template <class V> static void sp_upload(DBuf<V>& dst, const std::vector<V>& src) {
         dst.alloc(src.size());
         if (!src.empty()) BZ_HIP(hipMemcpy(dst.p, src.data(), src.size() * sizeof(V), hipMemcpyHostToDevice));
@@ -2173,64 +2137,78 @@ template <class T> class Solver final : public SolverBase {
                 if (col[k] < 0 || (int64_t)col[k] >= (ncols >= 0 ? ncols : n))
                     throw Error(BZ_ERR_ARG, what + (ncols >= 0 ? ": column index outside [0, n / K) (row " : ": column index outside [0, n) (row ") + std::to_string(r) + ")");
     }
-    static std::string sp_form(const char* kernel, const SpCsr& m) {
-        return std::string(kernel) + "<L=" + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
+    // (`lead`: what a kind puts in front — the GLM f "LOSS=…,W=…,", the multinomial f "K=…,")
+    static std::string sp_form(const char* kernel, const SpCsr& m, const std::string& lead = "") {
+        return std::string(kernel) + "<" + lead + "L=" + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
     }
+    void sp_name(int mode, const SpCsr& m) { sp_label_[mode] = sp_form(sp_kernel_name(mode), m); }
     // f = SparseQuadratic: Q validated on a host copy and put in HBM as one CSR matrix with A's segment and lane rules
     void sparse_f_create(const bz_problem_desc& d) {
         std::vector<int64_t> rp; std::vector<int32_t> col; std::vector<T> val;
         sp_read("SparseQuadratic", "n", nx, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
         sp_build(spQ_, nx, nx, rp, col, val);
         if (spQ_.ncut) sp_upload(spQ_rowptr_, rp);        // (a cut matrix keeps the virtual rows in ptr: the rows as given too)
-        sp_form_[2] = sp_form("k_spmv_q_algrad", spQ_);
-        sp_form_[3] = sp_form("k_spmv_q", spQ_);
+        sp_name(SP_Q_ALGRAD, spQ_);
+        sp_name(SP_Q, spQ_);
     }
-    // f = SparseLeastSquares or SparseLogistic: A_f validated on a host copy; A_f and A_f' in HBM with the segment and lane
-    // rules of A and A'
+    // the refusals and argument errors the row-wise sparse kinds share, worded from the kind's row of SPARSE_ROW_F.  (The
+    // multinomial f's class count is checked where its own block had it.)
+    void sparse_rowwise_check(const bz_problem_desc& d) const {
+        const std::string kind = spf_.name, f = std::string("sparse ") + spf_.noun + " f";
+        if (slack) throw Error(BZ_ERR_UNSUPPORTED, kind + ": the slack (ALS) form is not lowered with a " + f);
+        if (d.c_kind == BZ_C_DENSE_AFFINE)
+            throw Error(BZ_ERR_UNSUPPORTED, kind + ": a " + f + " beside a dense c (DenseAffine) is not lowered");
+        if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, kind + ": the " + f + " is not sharded (one rank)");
+        if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
+            throw Error(BZ_ERR_UNSUPPORTED, kind + ": the " + f + " does not mix with host callbacks");
+        if (d.f_kind == BZ_F_SPARSE_MULTINOMIAL) {
+            if (d.f_classes < 2 || d.f_classes > 64)
+                throw Error(BZ_ERR_ARG, kind + ": f_classes = K must be in 2 .. 64");
+            if (n % d.f_classes != 0)
+                throw Error(BZ_ERR_ARG, kind + ": n must be a multiple of f_classes (x is n / K rows of K)");
+        }
+        if (d.f_rows <= 0 || !d.f_b || !d.f_sp_rowptr || d.f_sp_nnz < 0 || (d.f_sp_nnz > 0 && (!d.f_sp_col || !d.f_sp_val)))
+            throw Error(BZ_ERR_ARG, kind + " needs f_rows = m > 0, rowptr[m + 1], col[nnz], val[nnz] and " + spf_.b);
+        // (32-bit: the column indices of A_f and of A_f', below m; an index into the multinomial f's X or R is formed in 64 bits)
+        if (n > (int64_t)std::numeric_limits<int32_t>::max() || d.f_rows > (int64_t)std::numeric_limits<int32_t>::max())
+            throw Error(BZ_ERR_ARG, kind + ": n and m must fit 32-bit indices");
+    }
+    // a row-wise sparse f: A_f validated on a host copy; A_f and A_f' in HBM with the segment and lane rules of A and A'
     void sparse_ls_create(const bz_problem_desc& d) {
         std::vector<int64_t> rp, tp; std::vector<int32_t> col, tcol; std::vector<T> val, tval;
+        // (the multinomial f: A_f is m x n_f, n_f = n / K, and the transpose is built over n_f columns)
+        const int64_t nf = sparse_mn ? nx / mn_K_ : nx;
+        sp_read(spf_.name, "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val, sparse_mn ? nf : -1);
+        csr_transpose(frows, nf, rp, col, val, tp, tcol, tval);
+        sp_build(spF_, frows, nf, rp, col, val);
+        sp_build(spFt_, nf, frows, tp, tcol, tval);
+        std::string lead, lead_t;              // what the kind puts in front of L and SEG in its labels
         if (sparse_mn) {
-            // A_f is m x n_f, n_f = n / K: the transpose is built over n_f columns; a segment of a cut row leaves K sums
-            const int64_t nf = nx / mn_K_;
-            sp_read("SparseMultinomial", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val, nf);
-            csr_transpose(frows, nf, rp, col, val, tp, tcol, tval);
-            sp_build(spF_, frows, nf, rp, col, val);
-            sp_build(spFt_, nf, frows, tp, tcol, tval);
             for (SpCsr* m : {&spF_, &spFt_}) {
                 m->kw = mn_K_;
                 m->L = spmm_lanes(m->nnz, m->nv, mn_KP_);
                 if (cenv_.spmv_l) m->L = std::min(*cenv_.spmv_l, 64 / mn_KP_);
-                if (m->ncut) m->part.alloc(m->part.n * (size_t)mn_K_);
+                if (m->ncut) m->part.alloc(m->part.n * (size_t)mn_K_);      // (a segment of a cut row leaves K sums)
             }
-            spmm_form_[0] = spmm_form("k_spmm_softmax_r", spF_);
-            spmm_form_[1] = spmm_form("k_spmm_t_algrad", spFt_);
-            spmm_form_[2] = spmm_form("k_spmm_t", spFt_);
-            return;
-        }
-        sp_read(sparse_glm ? "SparseGLM" : sparse_logit ? "SparseLogistic" : "SparseLeastSquares", "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val);
-        csr_transpose(frows, nx, rp, col, val, tp, tcol, tval);
-        sp_build(spF_, frows, nx, rp, col, val);
-        sp_build(spFt_, nx, frows, tp, tcol, tval);
-        spls_form_[0] = sp_form("k_spmv_ls_r", spF_);
-        spls_form_[1] = sp_form("k_spmv_ls_t_algrad", spFt_);
-        spls_form_[2] = sp_form("k_spmv_ls_t", spFt_);
-        if (sparse_logit) splogit_form_ = sp_form("k_spmv_logit_r", spF_);
-        if (glm_own_kernel()) {
+            lead = lead_t = "K=" + std::to_string(mn_K_) + ",";
+        } else if (spf_.mode >= SP_GLM_MODE0) {
             static const char* const names[] = {"least_squares", "logistic", "huber", "squared_hinge", "poisson"};
-            glm_form_ = std::string("k_spmv_glm_r<LOSS=") + names[glm_loss_] + ",W=" + (desc.f_w ? "1" : "0") + ",L=" +
-                        std::to_string(spF_.L) + ",SEG=" + (spF_.ncut ? "1" : "0") + ">";
+            lead = std::string("LOSS=") + names[spf_.mode - SP_GLM_MODE0] + ",W=" + (desc.f_w ? "1" : "0") + ",";
         }
+        auto kernel = [&](int mode) { return sparse_mn ? spmm_kernel_name(mode) : sp_kernel_name(mode); };
+        sp_label_[sp_label_at(spf_.mode)] = sp_form(kernel(spf_.mode), spF_, lead);
+        for (int mode : {SP_LS_T_ALGRAD, SP_T}) sp_label_[mode] = sp_form(kernel(mode), spFt_, lead_t);
     }
     // the GLM f: w^_i = T(scale * w_i), the product in double and rounded once; without a weight vector the one number T(scale).
     // Every w_i finite and >= 0, checked on a host copy.
     void glm_weights_create(const bz_problem_desc& d) {
-        const std::string what = sparse_mn ? "SparseMultinomial" : "SparseGLM";     // (the multinomial f: the same two fields, the same rules)
+        const std::string what = spf_.name;     // (the multinomial f: the same two fields, the same rules)
         glm_w_uniform_ = (T)d.f_scale;
         glm_delta_ = (T)d.f_loss_delta;
         // (what the kernel multiplies by is the ROUNDED number: an fp32 problem can overflow where the double was finite)
         if (!std::isfinite((double)glm_w_uniform_))
             throw Error(BZ_ERR_ARG, what + ": f_scale must be finite and > 0 in the problem's type");
-        if (sparse_glm && d.f_loss == BZ_LOSS_HUBER && !(std::isfinite((double)glm_delta_) && glm_delta_ > T(0)))
+        if (d.f_kind == BZ_F_SPARSE_GLM && d.f_loss == BZ_LOSS_HUBER && !(std::isfinite((double)glm_delta_) && glm_delta_ > T(0)))
             throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0 in the problem's type");
         if (!d.f_w) return;
         std::vector<T> w((size_t)frows);
@@ -2262,9 +2240,6 @@ template <class T> class Solver final : public SolverBase {
         while (KP * L * 2 <= 64 && mean > 4.0 * L) L *= 2;
         return L;
     }
-    std::string spmm_form(const char* kernel, const SpCsr& m) const {
-        return std::string(kernel) + "<K=" + std::to_string(mn_K_) + ",L=" + std::to_string(m.L) + ",SEG=" + (m.ncut ? "1" : "0") + ">";
-    }
     // go(KP, L, NT) with the run-time class width, lane count and stream policy as compile-time constants (KP * L <= 64)
     template <int KP, class F> static void spmm_with_l(int L, bool nt, F&& go) {
         with_bool(nt, [&](auto nt_) {
@@ -2288,37 +2263,42 @@ template <class T> class Solver final : public SolverBase {
         default: spmm_with_l<64>(L, nt, go); break;
         }
     }
-    // one pass of the K-wide row kernel (WHICH 0: k_spmm_softmax_r over A_f, 1: k_spmm_t_algrad and 2: k_spmm_t over A_f') and,
-    // for a cut matrix, the fold of its cut rows; returns the number of block partials left in `slot`.  The byte model counts
-    // the matrix once per pass (m.bytes(): the entries, the row pointers, one read of the K-wide gathered vector) and the
-    // K-wide per-row vectors in vec_bytes.
-    template <int WHICH> int spmm_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
-        constexpr int MODE = WHICH == 0 ? SPMM_SOFTMAX : WHICH == 1 ? 5 : 6;
+    // What every pass over a CSR matrix fixes before it launches: the bytes of its model — the matrix once (m.bytes(): the
+    // entries, the row pointers, one read of the gathered vector) and the per-row vectors in vec_bytes —, the stream policy and
+    // the grid of the fold of a cut matrix's cut rows.
+    struct SpPlan { double bytes; bool nt; int gfold; };
+    bool sp_nontemporal(double bytes) const { return env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6; }
+    SpPlan sp_plan(const SpCsr& m, double vec_bytes) const {
         const double bytes = m.bytes() + vec_bytes;
-        const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
-        const int gfold = m.ncut ? (int)std::min<int64_t>(512, (m.ncut + WAVES - 1) / WAVES) : 0;
+        return {bytes, sp_nontemporal(bytes), m.ncut ? (int)std::min<int64_t>(512, (m.ncut + WAVES - 1) / WAVES) : 0};
+    }
+    // right before the row launch: notes its bytes and its label, and returns its grid for rpb rows per workgroup (in front of
+    // the fold's workgroups)
+    int sp_row_grid(const SpCsr& m, const SpPlan& pl, int64_t rpb, int mode) {
+        pending_bytes_ += pl.bytes;
+        nm(sp_label_[sp_label_at(mode)].c_str());
+        return (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - pl.gfold, (m.nv + rpb - 1) / rpb));
+    }
+    // the fold behind the row launch: `tail` is what the fold kernel takes behind the cut rows
+    template <class K, class... A> void sp_fold(K kernel, SpCsr& m, const SpPlan& pl, A... tail) {
+        if (!pl.gfold) return;
+        pending_bytes_ += (double)m.part.n * 8 + (double)m.ncut * 8;
+        launch(C_MISC, kernel, pl.gfold, (const double*)m.part.p, (const int32_t*)m.crow.p, (const int32_t*)m.cptr.p, m.ncut, tail...);
+    }
+    // one pass of the K-wide row kernel (spmm_kernel: SPMM_SOFTMAX over A_f, SP_LS_T_ALGRAD and SP_T over A_f') and, for a cut
+    // matrix, the fold of its cut rows; returns the number of block partials left in `slot`.  vec_bytes: the K-wide per-row vectors.
+    template <int MODE> int spmm_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
+        const SpPlan pl = sp_plan(m, vec_bytes);
         const int K = mn_K_;
         int g = 1;
-        spmm_with_lanes(m.L, nt, [&](auto kp_, auto l_, auto nt_) {
+        spmm_with_lanes(m.L, pl.nt, [&](auto kp_, auto l_, auto nt_) {
             constexpr int KP = decltype(kp_)::value, L = decltype(l_)::value;
-            constexpr bool NT = decltype(nt_)::value;
-            const int64_t rpb = BLOCK / (KP * L);
-            g = (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - gfold, (m.nv + rpb - 1) / rpb));
-            pending_bytes_ += bytes;
-            nm(spmm_form_[WHICH].c_str());
-            if constexpr (WHICH == 0) launch(C_GEMV, k_spmm_softmax_r<T, KP, L, NT>, g, m.mat(), gathered, K, E, parts_.p, slot);
-            else if constexpr (WHICH == 1) launch(C_GEMV, k_spmm_t_algrad<T, KP, L, NT>, g, m.mat(), gathered, K, E, parts_.p, slot);
-            else launch(C_GEMV, k_spmm_t<T, KP, L, NT>, g, m.mat(), gathered, K, E, parts_.p, slot);
-            if (gfold) {
-                pending_bytes_ += (double)m.part.n * 8 + (double)m.ncut * 8;
-                launch(C_MISC, k_spmm_fold<T, KP, MODE>, gfold, (const double*)m.part.p, (const int32_t*)m.crow.p,
-                       (const int32_t*)m.cptr.p, m.ncut, K, E, parts_.p, slot, g);
-            }
+            g = sp_row_grid(m, pl, BLOCK / (KP * L), MODE);
+            launch(C_GEMV, spmm_kernel<T, KP, L, decltype(nt_)::value, MODE>(), g, m.mat(), gathered, K, E, parts_.p, slot);
+            sp_fold(k_spmm_fold<T, KP, MODE>, m, pl, K, E, parts_.p, slot, g);
         });
-        return g + gfold;
+        return g + pl.gfold;
     }
-    // (the plain least-squares and logistic losses run k_spmv_ls_r / k_spmv_logit_r)
-    bool glm_own_kernel() const { return sparse_glm && (glm_weighted_ || glm_loss_ >= BZ_LOSS_HUBER); }
     // c = SparseAffine: validate the caller's CSR on a host copy, build A' (csr_transpose: a column's entries stay in ascending row
     // order) and put both in HBM
     void sparse_create(const bz_problem_desc& d) {
@@ -2328,8 +2308,8 @@ template <class T> class Solver final : public SolverBase {
         csr_transpose(ny, n, rp, col, val, tp, tcol, tval);
         sp_build(spA_, ny, n, rp, col, val);
         sp_build(spAt_, n, ny, tp, tcol, tval);
-        sp_form_[0] = sp_form("k_spmv_yupd", spA_);
-        sp_form_[1] = sp_form("k_spmv_t_finish", spAt_);
+        sp_name(SP_YUPD, spA_);
+        sp_name(SP_T_FINISH, spAt_);
     }
     // go(L, NT) with the run-time lane count and stream policy as compile-time constants
     template <class F> static void sp_with_lanes(int L, bool nt, F&& go) {
@@ -2345,43 +2325,24 @@ template <class T> class Solver final : public SolverBase {
             }
         });
     }
-    // one pass of the row kernel (MODE 0: k_spmv_yupd over A, 1: k_spmv_t_finish over A', 3: k_spmv_q over Q, 4: k_spmv_ls_r
-    // over A_f, 5: k_spmv_ls_t_algrad and 6: k_spmv_ls_t over A_f', 7: k_spmv_logit_r and 8 .. 12: k_spmv_glm_r over A_f) and, for a cut matrix, the fold of its cut rows; returns
-    // the number of block partials left in `slot`
+    // one pass of the row kernel (sp_kernel: MODE -> entry point) and, for a cut matrix, the fold of its cut rows; returns the
+    // number of block partials left in `slot`
     template <int MODE> int sp_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
-        const double bytes = m.bytes() + vec_bytes;
-        const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
-        const int gfold = m.ncut ? (int)std::min<int64_t>(512, (m.ncut + WAVES - 1) / WAVES) : 0;
+        const SpPlan pl = sp_plan(m, vec_bytes);
         int g = 1;
-        auto go = [&](auto l_, auto nt_) {
+        sp_with_lanes(m.L, pl.nt, [&](auto l_, auto nt_) {
             constexpr int L = decltype(l_)::value;
-            constexpr bool NT = decltype(nt_)::value;
-            const int64_t rpb = BLOCK / L;
-            g = (int)std::max<int64_t>(1, std::min<int64_t>(PSTRIDE - gfold, (m.nv + rpb - 1) / rpb));
-            pending_bytes_ += bytes;
-            nm((MODE < 4 ? sp_form_[MODE & 3] : MODE >= SP_GLM_MODE0 ? glm_form_ : MODE == 7 ? splogit_form_ : spls_form_[MODE >= 4 && MODE < 7 ? MODE - 4 : 0]).c_str());
-            if constexpr (MODE == 0) launch(C_GEMV, k_spmv_yupd<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else if constexpr (MODE == 1) launch(C_GEMV, k_spmv_t_finish<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else if constexpr (MODE == 3) launch(C_GEMV, k_spmv_q<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else if constexpr (MODE == 4) launch(C_GEMV, k_spmv_ls_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else if constexpr (MODE == 5) launch(C_GEMV, k_spmv_ls_t_algrad<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else if constexpr (MODE == 6) launch(C_GEMV, k_spmv_ls_t<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else if constexpr (MODE == 7) launch(C_GEMV, k_spmv_logit_r<T, L, NT>, g, m.mat(), gathered, E, parts_.p, slot);
-            else launch(C_GEMV, k_spmv_glm_r<T, L, NT, MODE>, g, m.mat(), gathered, E, parts_.p, slot);
-        };
-        sp_with_lanes(m.L, nt, go);
-        if (gfold) {
-            pending_bytes_ += (double)m.part.n * 8 + (double)m.ncut * 8;
-            launch(C_MISC, k_spmv_fold<T, MODE>, gfold, (const double*)m.part.p, (const int32_t*)m.crow.p,
-                   (const int32_t*)m.cptr.p, m.ncut, E, parts_.p, slot, g);
-        }
-        return g + gfold;
+            g = sp_row_grid(m, pl, BLOCK / L, MODE);
+            launch(C_GEMV, sp_kernel<T, L, decltype(nt_)::value, MODE>(), g, m.mat(), gathered, E, parts_.p, slot);
+        });
+        sp_fold(k_spmv_fold<T, MODE>, m, pl, E, parts_.p, slot, g);
+        return g + pl.gfold;
     }
     // rows of A: c(x) -> cx (where the caller keeps it), yhat -> yupd and the penalty partials -> slot (yupd null: c(x) alone)
     int spmv_yupd(const T* x, T* cx, T* yupd, int slot) {
         SpEpi<T> E{cb_.p, cx, yupd, nullptr, P};
         const double vecs = (1 + (cx ? 1 : 0) + (yupd ? 1 + pstreams(false, true, false) : 0)) * (double)ny * sizeof(T);
-        return sp_pass<0>(spA_, x, E, slot, vecs);
+        return sp_pass<SP_YUPD>(spA_, x, E, slot, vecs);
     }
     // rows of A': grad = grad f(x) + A'yhat and the f partials -> slot
     // (the sparse quadratic f: its terms from FR_ = Q x, which spq_product has left there ; the sparse least squares or
@@ -2389,7 +2350,7 @@ template <class T> class Solver final : public SolverBase {
     int spmv_t_finish(const T* x, T* grad, int slot) {
         SpEpi<T> E{nullptr, nullptr, grad, x, P, sparse_f ? (const T*)FR_.p : sparse_ls ? (const T*)DFX_.p : (const T*)nullptr};
         const double vecs = ((grad ? 1 : 0) + (P.f_kind == BZ_F_DIAG_QUADRATIC || sparse_f ? 3 : 0) + (sparse_ls ? 1 : 0)) * (double)n * sizeof(T);
-        return sp_pass<1>(spAt_, YU_.p, E, slot, vecs);
+        return sp_pass<SP_T_FINISH>(spAt_, YU_.p, E, slot, vecs);
     }
     // rows of Q, c = Identity: the whole AL gradient — grad = (Q x + q) + yhat, the f partials -> slot, the penalty
     // partials -> slot + 1.  Per row: x, q, mu and mu*y (and D's vector bounds), the gradient.
@@ -2400,11 +2361,11 @@ template <class T> class Solver final : public SolverBase {
         SpCsr& m = spQ_;
         SpEpi<T> E{nullptr, nullptr, grad, x, P, nullptr};
         const double bytes = m.bytes() + (2 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T);
-        const bool nt = env_.nt >= 0 ? env_.nt != 0 : bytes > 340e6;
+        const bool nt = sp_nontemporal(bytes);
         const SpRows R{m.ncut ? spQ_rowptr_.p : m.ptr.p, m.crow.p, m.cptr.p, m.ncut, m.S, n};
         sp_with_lanes(m.L, nt, [&](auto l_, auto nt_) {
             pending_bytes_ += bytes;
-            nm(sp_form_[2].c_str());
+            nm(sp_label_[SP_Q_ALGRAD].c_str());
             launch(C_GEMV, k_spmv_q_algrad<T, decltype(l_)::value, decltype(nt_)::value>, grid, m.mat(), R, x, E, parts_.p, slot);
         });
         return grid;
@@ -2413,49 +2374,39 @@ template <class T> class Solver final : public SolverBase {
     int spq_product(const T* x, T* out, bool with_f, int slot) {
         SpEpi<T> E{nullptr, nullptr, out, with_f ? x : (const T*)nullptr, P, nullptr};
         const double vecs = ((out ? 1 : 0) + (with_f ? 2 : 0)) * (double)n * sizeof(T);
-        return sp_pass<3>(spQ_, x, E, slot, vecs);
+        return sp_pass<SP_Q>(spQ_, x, E, slot, vecs);
     }
     // (pairwise D: the projection of element i needs its partner, which a row's first lane does not have)
     bool spq_fused_on() const { return cenv_.spq_fused && !(desc.D_kind >= BZ_D_VC_PAIRS && desc.D_kind <= BZ_D_XOR_PAIRS); }
 
-    // ---- f = SparseLeastSquares / SparseLogistic / SparseGLM
-    // rows of A_f: r = A_f x - b -> r_out (null: not kept) and the partials of sum r^2 -> slot.  Per row: b (and r).
-    // The logistic f: r_i = -b_i sigma(-b_i a_i'x) and the partials of the rows' losses, the same streams.
-    // The GLM f: r_i = w_i l'(b_i, a_i'x) and the partials of the weighted losses; a weight vector is one more stream.
+    // ---- a row-wise sparse f (SparseRowF)
+    // rows of A_f: r_i = w_i l'(b_i, a_i'x) -> r_out (null: not kept) and the partials of the rows' losses -> slot, in the kind's
+    // mode (least squares: r = A_f x - b and sum r^2 ; the multinomial f: R = w (softmax(A_f X) - onehot(b)), m rows of K).
+    // Per row: b (and r, the multinomial f's K values); a weight vector is one more stream.
     int spls_residual(const T* x, T* r_out, int slot) {
         SpEpi<T> E{fb_.p, nullptr, r_out, nullptr, P, nullptr};
-        if (sparse_mn) {
-            // the multinomial f: R = w (softmax(A_f X) - onehot(b)), m rows of K, and the partials of the rows' losses.  Per row:
-            // the label (and K of R); a weight vector is one more stream.
-            E.w = glm_w_.p; E.w_uniform = glm_w_uniform_;
-            return spmm_pass<0>(spF_, x, E, slot, (1 + (r_out ? mn_K_ : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T));
-        }
-        if (glm_own_kernel()) {
-            E.w = glm_w_.p; E.w_uniform = glm_w_uniform_; E.delta = glm_delta_;
-            const double vecs = (1 + (r_out ? 1 : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T);
-            switch (glm_loss_) {
-            case BZ_LOSS_LEAST_SQUARES: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES>(spF_, x, E, slot, vecs);
-            case BZ_LOSS_LOGISTIC: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_LOGISTIC>(spF_, x, E, slot, vecs);
-            case BZ_LOSS_HUBER: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_HUBER>(spF_, x, E, slot, vecs);
-            case BZ_LOSS_SQUARED_HINGE: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE>(spF_, x, E, slot, vecs);
-            default: return sp_pass<SP_GLM_MODE0 + BZ_LOSS_POISSON>(spF_, x, E, slot, vecs);
-            }
-        }
-        if (sparse_logit) return sp_pass<7>(spF_, x, E, slot, (1 + (r_out ? 1 : 0)) * (double)frows * sizeof(T));
-        return sp_pass<4>(spF_, x, E, slot, (1 + (r_out ? 1 : 0)) * (double)frows * sizeof(T));
+        if (spf_.weighted) { E.w = glm_w_.p; E.w_uniform = glm_w_uniform_; E.delta = glm_delta_; }
+        const double vecs = (1 + (r_out ? (sparse_mn ? mn_K_ : 1) : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T);
+        int nparts = 0;
+        with_sparse_f_mode(spf_.mode, [&](auto mode_) {
+            constexpr int MODE = decltype(mode_)::value;
+            if constexpr (MODE == SPMM_SOFTMAX) nparts = spmm_pass<MODE>(spF_, x, E, slot, vecs);
+            else nparts = sp_pass<MODE>(spF_, x, E, slot, vecs);
+        });
+        return nparts;
     }
     // rows of A_f', c = Identity: grad = A_f' r + yhat (r in FR_) and the penalty partials -> slot.  Per row: x, mu and mu*y
     // (and D's vector bounds), the gradient.
     int spls_t_algrad(const T* x, T* grad, int slot) {
         SpEpi<T> E{nullptr, nullptr, grad, x, P, nullptr};
-        if (sparse_mn) return spmm_pass<1>(spFt_, FR_.p, E, slot, (1 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T));
-        return sp_pass<5>(spFt_, FR_.p, E, slot, (1 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T));
+        const double vecs = (1 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T);
+        return sparse_mn ? spmm_pass<SP_LS_T_ALGRAD>(spFt_, FR_.p, E, slot, vecs) : sp_pass<SP_LS_T_ALGRAD>(spFt_, FR_.p, E, slot, vecs);
     }
     // rows of A_f': A_f' r -> DFX_ (r in FR_)
     void spls_product() {
         SpEpi<T> E{nullptr, nullptr, DFX_.p, nullptr, P, nullptr};
-        if (sparse_mn) { spmm_pass<2>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T)); return; }
-        sp_pass<6>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
+        if (sparse_mn) spmm_pass<SP_T>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
+        else sp_pass<SP_T>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
     }
     // (pairwise D: the projection of element j needs its partner, which a row's first lane does not have)
     bool spls_fused_on() const { return cenv_.spls_fused && !(desc.D_kind >= BZ_D_VC_PAIRS && desc.D_kind <= BZ_D_XOR_PAIRS); }
@@ -3910,25 +3861,27 @@ template <class T> class Solver final : public SolverBase {
         st->n_affine_blends = state_.n_affine_blends;
     }
 
-    // ---- f = SparseLeastSquares (kept behind every older member: their layout is the parent's)
-    bool sparse_ls = false;
+    // ---- a row-wise sparse f (kept behind every older member: their layout is the parent's).  SparseLeastSquares,
+    // SparseLogistic, SparseGLM and SparseMultinomial are one path, `sparse_ls`: a pass over A_f that leaves r and the rows'
+    // losses, then the passes over A_f' on r.  What a kind differs in is one row, copied to spf_ at creation:
+    struct SparseRowF {
+        int f_kind;
+        const char *name, *noun, *b;       // in the messages: the kind, "a sparse <noun> f" and what the kind calls its vector
+        int mode;                          // the epilogue of the pass over A_f (SPMM_SOFTMAX: the K-wide kernels of bz_spmm.h)
+        bool weighted;                     // the epilogue takes w, w_uniform and delta (one more stream with a weight vector)
+    };
+    static constexpr SparseRowF SPARSE_ROW_F[] = {
+        {BZ_F_SPARSE_LEAST_SQUARES, "SparseLeastSquares", "least-squares", "b[m]", SP_LS_R, false},
+        {BZ_F_SPARSE_LOGISTIC, "SparseLogistic", "logistic", "the labels b[m]", SP_LOGIT_R, false},
+        {BZ_F_SPARSE_GLM, "SparseGLM", "GLM", "b[m]", SP_GLM_MODE0, true},       // (mode and weighted: from f_loss, f_w and f_scale)
+        {BZ_F_SPARSE_MULTINOMIAL, "SparseMultinomial", "multinomial", "the labels b[m]", SPMM_SOFTMAX, true},
+    };
+    SparseRowF spf_ = SPARSE_ROW_F[0];
+    bool sparse_ls = false, sparse_mn = false;     // (sparse_mn: spf_.mode == SPMM_SOFTMAX)
     SpCsr spF_, spFt_;                     // A_f (m x n) and A_f' (n x m)
-    std::string spls_form_[3];             // by the epilogue's MODE - 4
-    // ---- f = SparseLogistic: a sparse_ls problem (both flags set) whose rows of A_f run k_spmv_logit_r
-    bool sparse_logit = false;
-    std::string splogit_form_;
-    // ---- f = SparseGLM: a sparse_ls problem whose rows of A_f run k_spmv_glm_r<loss> (the plain least-squares and logistic
-    // losses: k_spmv_ls_r / k_spmv_logit_r, sparse_logit set with the latter)
-    bool sparse_glm = false, glm_weighted_ = false;
-    int glm_loss_ = 0;
     DBuf<T> glm_w_;                        // [m] scale * w, or empty: glm_w_uniform_ = scale for every row
     T glm_w_uniform_ = T(1), glm_delta_ = T(0);
-    std::string glm_form_;
-    // ---- f = SparseMultinomial: a sparse_ls problem whose three row launches are bz_spmm.h's (K values behind every index);
-    // the weights are glm_w_ / glm_w_uniform_
-    bool sparse_mn = false;
-    int mn_K_ = 0, mn_KP_ = 0;             // the classes, and the power of two >= K
-    std::string spmm_form_[3];             // k_spmm_softmax_r, k_spmm_t_algrad, k_spmm_t
+    int mn_K_ = 0, mn_KP_ = 0;             // the multinomial f: the classes, and the power of two >= K
 };
 
 // one-pass kernel of an oracle family: the instantiations live in bz_families_dk*.hip (one file per D class, so that

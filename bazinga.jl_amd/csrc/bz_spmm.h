@@ -5,8 +5,8 @@
 //   k_spmm_softmax_r  rows of A_f :  t_ik = sum_j a_ij x_jk, and on the K sums of a row the softmax: r_ik = w_i (p_ik - [k = b_i])
 //                     -> R[i * K + k] (if kept) and the row's loss w_i ((mx - t_{i,b_i}) + log S)
 //   k_spmm_t_algrad   rows of A_f', c = Identity:  (A_f' R)_jk, and on element j * K + k what k_algrad_elem does in its mode 1
-//                     (sp_epilogue's MODE 5 on every class lane): the whole AL gradient in two launches, grad f never in HBM
-//   k_spmm_t          rows of A_f':  A_f' R -> DFX (MODE 6) for the forms that finish element-wise or in k_spmv_t_finish
+//                     (sp_epilogue's SP_LS_T_ALGRAD on every class lane): the whole AL gradient in two launches, grad f never in HBM
+//   k_spmm_t          rows of A_f':  A_f' R -> DFX (SP_T) for the forms that finish element-wise or in k_spmv_t_finish
 //
 // The lane map.  A (virtual) row is walked by a group of KP * L <= 64 lanes, KP the power of two >= K.  The CLASS is the fastest
 // lane index (k = lane % KP, l = lane / KP): the gather of one entry's K values is one contiguous access of K elements (a full
@@ -32,7 +32,8 @@ namespace bz {
 __device__ __forceinline__ float sp_log(float v) { return logf(v); }
 __device__ __forceinline__ double sp_log(double v) { return log(v); }
 
-// what a row's K sums go into: SPMM_SOFTMAX (rows of A_f), or sp_epilogue's MODE 5 / MODE 6 per element j * K + k (rows of A_f')
+// what a row's K sums go into: SPMM_SOFTMAX (rows of A_f), or sp_epilogue's SP_LS_T_ALGRAD / SP_T per element j * K + k (rows
+// of A_f')
 constexpr int SPMM_SOFTMAX = 100;
 
 // the entries [s, e) of one row for class kc, this lane being entry lane l of the row's L: spmv_row with K values behind
@@ -74,7 +75,7 @@ __device__ __forceinline__ double spmm_row(const SpMat<T>& M, const T* __restric
 //   copy of t_{K-1} cannot change the max; its e is dropped from S).  The max is an ordered compare, which drops a NaN — the
 //   lanes may then disagree on mx — but the NaN lane's own e = exp(NaN - .) is NaN and the sum gives it to every lane: p, r and
 //   the loss of the whole row are NaN.  The lane of class b_i adds the row's loss.
-//   MODE 5 / 6: sp_epilogue on element r * K + k.
+//   SP_LS_T_ALGRAD / SP_T: sp_epilogue on element r * K + k.
 template <class T, int KP, int MODE>
 __device__ __forceinline__ void spmm_epilogue(const SpEpi<T>& E, int K, int64_t r, double d, int k, bool lead, double (&acc)[1]) {
     if constexpr (MODE == SPMM_SOFTMAX) {
@@ -138,7 +139,7 @@ template <class T, int KP, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmm_t_algrad(SpMat<T> M, const T* __restrict__ r, int K, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmm_rows<T, KP, L, NT, 5>(M, r, K, E, acc);
+    spmm_rows<T, KP, L, NT, SP_LS_T_ALGRAD>(M, r, K, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -147,7 +148,7 @@ template <class T, int KP, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmm_t(SpMat<T> M, const T* __restrict__ r, int K, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmm_rows<T, KP, L, NT, 6>(M, r, K, E, acc);
+    spmm_rows<T, KP, L, NT, SP_T>(M, r, K, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -172,6 +173,17 @@ k_spmm_fold(const double* __restrict__ part, const int32_t* __restrict__ crow, c
         spmm_epilogue<T, KP, MODE>(E, K, (int64_t)crow[j], a, k, l == 0, acc);
     }
     block_reduce_store<1>(acc, 0u, parts, slot0, vb0 + (int)blockIdx.x);
+}
+
+// MODE -> the K-wide row kernel's entry point and its name, as sp_kernel and sp_kernel_name
+template <class T, int KP, int L, bool NT, int MODE> constexpr auto spmm_kernel() {
+    static_assert(MODE == SPMM_SOFTMAX || MODE == SP_LS_T_ALGRAD || MODE == SP_T, "a mode of the K-wide row loop");
+    if constexpr (MODE == SPMM_SOFTMAX) return &k_spmm_softmax_r<T, KP, L, NT>;
+    else if constexpr (MODE == SP_LS_T_ALGRAD) return &k_spmm_t_algrad<T, KP, L, NT>;
+    else return &k_spmm_t<T, KP, L, NT>;
+}
+constexpr const char* spmm_kernel_name(int MODE) {
+    return MODE == SPMM_SOFTMAX ? "k_spmm_softmax_r" : MODE == SP_LS_T_ALGRAD ? "k_spmm_t_algrad" : "k_spmm_t";
 }
 
 }  // namespace bz

@@ -23,10 +23,13 @@
 //   k_spmv_logit_r      rows of A_f, the logistic f:  r_i = -b_i sigma(-b_i a_i'x) -> R (if kept) and the terms
 //                       softplus(-b_i a_i'x); the two kernels over A_f' then run on that r as they do on a residual
 //   k_spmv_glm_r<LOSS>  rows of A_f, the GLM f:  r_i = w_i l'(b_i, a_i'x) -> R (if kept) and the terms w_i l(b_i, a_i'x), the
-//                       loss a template argument (MODE 8 .. 12); the same two kernels over A_f' behind it
+//                       loss a template argument (MODE SP_GLM_MODE0 + BZ_LOSS_*); the same two kernels over A_f' behind it
 // Rows longer than S entries (S fixed at creation from the matrix alone) are cut into segments that run as rows of
 // their own ("virtual rows": the row pointers refined at the cuts); a segment leaves its sum in a side buffer and
 // k_spmv_fold, one wave per cut row, adds a row's segment sums in a fixed order and runs the row's epilogue.
+// What a row's value goes into is the epilogue's MODE (SP_YUPD .. SP_GLM_MODE0 + BZ_LOSS_POISSON): sp_epilogue is its one body,
+// with one arm for the row losses of every kind over A_f; sp_kernel / sp_kernel_name are the one map from a MODE to its entry
+// point and its label.
 //
 // Kept apart from bz_kernels.h because only bz_solver.hip instantiates these templates: the sixteen family translation
 // units do not see (or rebuild for) them.
@@ -46,29 +49,35 @@ template <class T> struct SpMat {
     int64_t nv;
 };
 
-// what a row's value goes into.  MODE 0 (rows of A): cx (if kept), yupd (if wanted: null = eval!(cx, c, x) alone) and
-// the penalty term; MODE 1 (rows of A'): the gradient and the f term; MODE 2 (rows of Q, c = Identity): the gradient, the
-// f term and the penalty term; MODE 3 (rows of Q): Q x (if kept) and the f term (if x is given); MODE 4 (rows of A_f): the
-// residual (if kept) and its square; MODE 5 (rows of A_f', c = Identity): the gradient and the penalty term; MODE 6 (rows
-// of A_f'): the product alone; MODE 7 (rows of A_f, logistic): the derivative of the row's loss (if kept) and the loss;
-// MODE 8 .. 12 (rows of A_f, the GLM f): the same for the weighted loss SP_GLM_MODE0 + BZ_LOSS_*.
-constexpr int SP_GLM_MODE0 = 8;      // MODE 8 + loss: 8 least squares, 9 logistic, 10 Huber, 11 squared hinge, 12 Poisson
+// what a row's value goes into: the epilogue's MODE.  (Plain ints, not an enum: a MODE is a template argument of k_spmv_fold,
+// k_spmv_glm_r and k_spmm_fold, so its type is part of those kernels' names.)
+constexpr int SP_YUPD = 0;           // rows of A: cx (if kept), yupd (if wanted: null = eval!(cx, c, x) alone) and the penalty term
+constexpr int SP_T_FINISH = 1;       // rows of A': the gradient and the f term
+constexpr int SP_Q_ALGRAD = 2;       // rows of Q, c = Identity: the gradient, the f term and the penalty term
+constexpr int SP_Q = 3;              // rows of Q: Q x (if kept) and the f term (if x is given)
+constexpr int SP_LS_R = 4;           // rows of A_f: the residual (if kept) and its square
+constexpr int SP_LS_T_ALGRAD = 5;    // rows of A_f', c = Identity: the gradient and the penalty term
+constexpr int SP_T = 6;              // rows of A_f': the product alone
+constexpr int SP_LOGIT_R = 7;        // rows of A_f, logistic: the derivative of the row's loss (if kept) and the loss
+constexpr int SP_GLM_MODE0 = 8;      // rows of A_f, the GLM f: the same for the weighted loss SP_GLM_MODE0 + BZ_LOSS_* (8 least
+                                     // squares, 9 logistic, 10 Huber, 11 squared hinge, 12 Poisson)
+constexpr int SP_NMODES = SP_GLM_MODE0 + BZ_LOSS_POISSON + 1;
 template <class T> struct SpEpi {
-    const T* b;              // MODE 0: b[ny] ; MODE 4: b[m] of f ; MODE 7: the labels b[m] of f
-    T* cx;                   // MODE 0: c(x) for the caller that keeps it, or null
-    T* out;                  // MODE 0: yupd[ny] or null ; MODE 1, 2, 5: grad[n] or null ; MODE 3: (Q x)[n] or null ;
-                             // MODE 4, 7: r[m] or null ; MODE 6: (A_f' r)[n]
-    const T* x;              // MODE 1, 2, 5: x[n] ; MODE 3: x[n], or null for the product alone
+    const T* b;              // SP_YUPD: b[ny] ; SP_LS_R and the GLM modes: b[m] of f ; SP_LOGIT_R: the labels b[m] of f
+    T* cx;                   // SP_YUPD: c(x) for the caller that keeps it, or null
+    T* out;                  // SP_YUPD: yupd[ny] or null ; SP_T_FINISH, SP_Q_ALGRAD, SP_LS_T_ALGRAD: grad[n] or null ;
+                             // SP_Q: (Q x)[n] or null ; the modes over A_f: r[m] or null ; SP_T: (A_f' r)[n]
+    const T* x;              // SP_T_FINISH, SP_Q_ALGRAD, SP_LS_T_ALGRAD: x[n] ; SP_Q: x[n], or null for the product alone
     ElemParams<T> P;
-    const T* ext;            // MODE 1 with the sparse quadratic f: (Q x)[n], left by k_spmv_q ; with the sparse least
-                             // squares, logistic or GLM f: (A_f' r)[n], left by k_spmv_ls_t
-    const T* w;              // MODE 8 .. 12: the row weights w[m] (scale folded in), or null: w_uniform for every row
+    const T* ext;            // SP_T_FINISH with the sparse quadratic f: (Q x)[n], left by k_spmv_q ; with a row-wise sparse
+                             // f: (A_f' r)[n], left by k_spmv_ls_t
+    const T* w;              // the GLM modes: the row weights w[m] (scale folded in), or null: w_uniform for every row
     T w_uniform;
-    T delta;                 // MODE 10: Huber's delta
+    T delta;                 // SP_GLM_MODE0 + BZ_LOSS_HUBER: Huber's delta
 };
 
-// scalars a mode leaves per row: MODE 2 the f term and the penalty term, the others (MODE 7 .. 12: the loss) one
-template <int MODE> constexpr int sp_nacc() { return MODE == 2 ? 2 : 1; }
+// scalars a mode leaves per row: SP_Q_ALGRAD the f term and the penalty term, the others (over A_f: the loss) one
+template <int MODE> constexpr int sp_nacc() { return MODE == SP_Q_ALGRAD ? 2 : 1; }
 
 // exp and log1p in T: an fp32 problem takes the fp32 functions
 __device__ __forceinline__ float sp_exp(float v) { return expf(v); }
@@ -76,11 +85,13 @@ __device__ __forceinline__ double sp_exp(double v) { return exp(v); }
 __device__ __forceinline__ float sp_log1p(float v) { return log1pf(v); }
 __device__ __forceinline__ double sp_log1p(double v) { return log1p(v); }
 
-// (called by the row's first lane alone: the per-row parameters are loaded once per row)
+// (called by the row's first lane alone; every arm is written into this one body and none behind a call: the inlined form of a
+// helper gives the same instructions in another order, and the kernels are kept instruction for instruction.  The per-row
+// parameters are loaded once per row.)
 template <class T, int MODE>
 __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double d, double (&acc)[sp_nacc<MODE>()]) {
     const ElemParams<T>& P = E.P;
-    if constexpr (MODE == 0) {
+    if constexpr (MODE == SP_YUPD) {
         const T c = (T)d - E.b[r];                                  // eval!(cx, c, x)
         if (E.cx) E.cx[r] = c;
         if (!E.out) return;
@@ -95,7 +106,7 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
         const T pterm = (t * t) / mu;
         E.out[r] = t / mu;
         acc[0] += (double)pterm;
-    } else if constexpr (MODE == 1) {
+    } else if constexpr (MODE == SP_T_FINISH) {
         // dlx = dfx + jtv ; f element-wise (Zero | DiagQuadratic)               (k_gemv_t_finish)
         // or the sparse quadratic from ext = Q x, P.b = q                      (k_gemv_t_finish_ext, fext 2)
         T dfx = T(0), fterm = T(0);
@@ -114,65 +125,54 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
         }
         if (E.out) E.out[r] = dfx + (T)d;
         acc[0] += (double)fterm;
-    } else if constexpr (MODE == 2) {
-        // element r of k_algrad_elem in its mode 2 with ext[r] = d: the same operations in the same order (never launched
-        // with a pairwise D, whose projection needs the partner element)
-        const T xv = E.x[r], qv = P.b[r], e = (T)d;
+    } else if constexpr (MODE == SP_Q_ALGRAD || MODE == SP_LS_T_ALGRAD) {
+        // element r of k_algrad_elem with ext[r] = d, in its mode 2 (rows of Q: with the f term from q = P.b) or its mode 1 (rows
+        // of A_f': without): the same operations in the same order (never launched with a pairwise D, whose projection needs
+        // the partner element)
+        const T xv = E.x[r];
+        [[maybe_unused]] T qv = T(0);
+        if constexpr (MODE == SP_Q_ALGRAD) qv = P.b[r];
+        const T e = (T)d;
         const T mu = P.uni >= 1 ? P.mu_uniform : P.mu[r];
         const T muy = P.uni >= 2 ? T(0) : P.muy[r];
         const T lo = P.D_lo_vec ? P.D_lo_vec[r] : P.D_lo;
         const T hi = P.D_hi_vec ? P.D_hi_vec[r] : P.D_hi;
         const ALOut<T> o = al_elem(BZ_F_ZERO, P.D_kind, xv, T(0), T(0), mu, muy, lo, hi);
-        const T dfx = e + qv;
-        const T fterm = xv * (T(0.5) * e + qv);
-        if (E.out) E.out[r] = dfx + o.grad;
-        acc[0] += (double)fterm;
-        acc[1] += (double)o.pterm;
-    } else if constexpr (MODE == 3) {
+        if constexpr (MODE == SP_Q_ALGRAD) {
+            const T dfx = e + qv;
+            const T fterm = xv * (T(0.5) * e + qv);
+            if (E.out) E.out[r] = dfx + o.grad;
+            acc[0] += (double)fterm;
+            acc[1] += (double)o.pterm;
+        } else {
+            if (E.out) E.out[r] = e + o.grad;
+            acc[0] += (double)o.pterm;
+        }
+    } else if constexpr (MODE == SP_Q) {
         const T e = (T)d;
         if (E.out) E.out[r] = e;
         if (E.x) acc[0] += (double)(E.x[r] * (T(0.5) * e + P.b[r]));            // k_fvalue_elem with ext
-    } else if constexpr (MODE == 4) {
-        const T rv = (T)d - E.b[r];                                 // r = A_f x - b ; sum r^2, halved on the host (fscale)
-        if (E.out) E.out[r] = rv;
-        acc[0] += (double)(rv * rv);
-    } else if constexpr (MODE == 5) {
-        // element r of k_algrad_elem in its mode 1 with ext[r] = d: MODE 2's operations in MODE 2's order without the f
-        // term (never launched with a pairwise D, whose projection needs the partner element)
-        const T xv = E.x[r], e = (T)d;
-        const T mu = P.uni >= 1 ? P.mu_uniform : P.mu[r];
-        const T muy = P.uni >= 2 ? T(0) : P.muy[r];
-        const T lo = P.D_lo_vec ? P.D_lo_vec[r] : P.D_lo;
-        const T hi = P.D_hi_vec ? P.D_hi_vec[r] : P.D_hi;
-        const ALOut<T> o = al_elem(BZ_F_ZERO, P.D_kind, xv, T(0), T(0), mu, muy, lo, hi);
-        if (E.out) E.out[r] = e + o.grad;
-        acc[0] += (double)o.pterm;
-    } else if constexpr (MODE == 7) {
-        // u = b_i a_i'x ; loss = softplus(-u), r_i = -b_i sigma(-u), both from e = exp(-|u|) in [0, 1]: nothing overflows and
-        // nothing cancels.  Ordered compares and arithmetic alone (no fmax / fmin, which drop a NaN): a NaN in u makes every
-        // compare false, e NaN, and reaches the loss and r_i.
-        const T bv = E.b[r];
-        const T u = bv * (T)d;
-        const T e = sp_exp(u < T(0) ? u : -u);
-        const T loss = (u < T(0) ? -u : T(0)) + sp_log1p(e);
-        const T s = u >= T(0) ? e / (T(1) + e) : T(1) / (T(1) + e);
-        if (E.out) E.out[r] = -bv * s;
-        acc[0] += (double)loss;
-    } else if constexpr (MODE >= SP_GLM_MODE0) {
-        // the GLM f: the row's term w l(b, t) and r = w l'(b, t), t = a_i'x, the loss fixed at compile time.  One pointer test
-        // and one load for the weight, as mu has it; every branch below is a select on values already at hand.  Ordered
-        // compares and arithmetic alone: a NaN in t makes every compare false and reaches both the loss and r.
-        constexpr int LOSS = MODE - SP_GLM_MODE0;
-        const T wv = E.w ? E.w[r] : E.w_uniform;
+    } else if constexpr (MODE == SP_LS_R || MODE == SP_LOGIT_R || MODE >= SP_GLM_MODE0) {
+        // rows of A_f: the row's term w l(b, t) and r = w l'(b, t), t = a_i'x, the loss fixed at compile time.  The plain
+        // least-squares and logistic kinds (W false) are the same losses without the weight: no load and no product for it.
+        // The weight: one pointer test and one load, as mu has it; every branch below is a select on values already at hand.
+        // Ordered compares and arithmetic alone (no fmax / fmin, which drop a NaN): a NaN in t makes every compare false and
+        // reaches both the loss and r.
+        constexpr bool W = MODE >= SP_GLM_MODE0;
+        constexpr int LOSS = W ? MODE - SP_GLM_MODE0 : MODE == SP_LS_R ? BZ_LOSS_LEAST_SQUARES : BZ_LOSS_LOGISTIC;
+        [[maybe_unused]] T wv = T(1);
+        if constexpr (W) wv = E.w ? E.w[r] : E.w_uniform;
         const T bv = E.b[r];
         const T t = (T)d;
         T loss, dl;
         if constexpr (LOSS == BZ_LOSS_LEAST_SQUARES) {
-            const T v = t - bv;                                     // sum w v^2, halved on the host (fscale)
+            const T v = t - bv;                                     // r = A_f x - b ; sum w v^2, halved on the host (fscale)
             loss = v * v;
             dl = v;
         } else if constexpr (LOSS == BZ_LOSS_LOGISTIC) {
-            const T u = bv * t;                                     // MODE 7's operations
+            // u = b_i a_i'x ; loss = softplus(-u), dl = -b_i sigma(-u), both from e = exp(-|u|) in [0, 1]: nothing overflows and
+            // nothing cancels
+            const T u = bv * t;
             const T e = sp_exp(u < T(0) ? u : -u);
             loss = (u < T(0) ? -u : T(0)) + sp_log1p(e);
             const T s = u >= T(0) ? e / (T(1) + e) : T(1) / (T(1) + e);
@@ -196,8 +196,13 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
             loss = e < std::numeric_limits<T>::infinity() ? e - bt : e;
             dl = e - bv;
         }
-        if (E.out) E.out[r] = wv * dl;
-        acc[0] += (double)(wv * loss);
+        if constexpr (W) {
+            if (E.out) E.out[r] = wv * dl;
+            acc[0] += (double)(wv * loss);
+        } else {
+            if (E.out) E.out[r] = dl;
+            acc[0] += (double)loss;
+        }
     } else {
         if (E.out) E.out[r] = (T)d;
     }
@@ -264,7 +269,7 @@ template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_yupd(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmv_rows<T, L, NT, 0>(M, x, E, acc);
+    spmv_rows<T, L, NT, SP_YUPD>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -272,7 +277,7 @@ template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_t_finish(SpMat<T> M, const T* __restrict__ yupd, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmv_rows<T, L, NT, 1>(M, yupd, E, acc);
+    spmv_rows<T, L, NT, SP_T_FINISH>(M, yupd, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -318,7 +323,7 @@ k_spmv_q_algrad(SpMat<T> M, SpRows R, const T* __restrict__ x, SpEpi<T> E, doubl
             const double d = spmv_row<T, L, NT>(M, x, s, e, sub);
             if (sub == 0 && whole) {
                 double t2[2] = {0.0, 0.0};
-                sp_epilogue<T, 2>(E, r, d, t2);
+                sp_epilogue<T, SP_Q_ALGRAD>(E, r, d, t2);
                 shf[lr] = t2[0]; shp[lr] = t2[1];
             }
         }
@@ -346,7 +351,7 @@ k_spmv_q_algrad(SpMat<T> M, SpRows R, const T* __restrict__ x, SpEpi<T> E, doubl
                     for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o, 64);
                     if (lane == 0) {
                         double t2[2] = {0.0, 0.0};
-                        sp_epilogue<T, 2>(E, r, a, t2);
+                        sp_epilogue<T, SP_Q_ALGRAD>(E, r, a, t2);
                         shf[r - i0] = t2[0]; shp[r - i0] = t2[1];
                     }
                 }
@@ -368,7 +373,7 @@ template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_q(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmv_rows<T, L, NT, 3>(M, x, E, acc);
+    spmv_rows<T, L, NT, SP_Q>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -377,7 +382,7 @@ template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_ls_r(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmv_rows<T, L, NT, 4>(M, x, E, acc);
+    spmv_rows<T, L, NT, SP_LS_R>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -386,7 +391,7 @@ template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_logit_r(SpMat<T> M, const T* __restrict__ x, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmv_rows<T, L, NT, 7>(M, x, E, acc);
+    spmv_rows<T, L, NT, SP_LOGIT_R>(M, x, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -406,7 +411,7 @@ template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_ls_t_algrad(SpMat<T> M, const T* __restrict__ r, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmv_rows<T, L, NT, 5>(M, r, E, acc);
+    spmv_rows<T, L, NT, SP_LS_T_ALGRAD>(M, r, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -415,12 +420,12 @@ template <class T, int L, bool NT>
 __global__ void __launch_bounds__(BLOCK)
 k_spmv_ls_t(SpMat<T> M, const T* __restrict__ r, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
-    spmv_rows<T, L, NT, 6>(M, r, E, acc);
+    spmv_rows<T, L, NT, SP_T>(M, r, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
 // the cut rows: one wave per row adds the row's segment sums (lane l the sums l, l + 64, ... in order, then the fixed
-// xor tree) and runs the row's epilogue; its block partials continue the slot (MODE 2: the two slots) behind the row
+// xor tree) and runs the row's epilogue; its block partials continue the slot (SP_Q_ALGRAD: the two slots) behind the row
 // kernel's (vb0).
 template <class T, int MODE>
 __global__ void __launch_bounds__(BLOCK)
@@ -438,6 +443,25 @@ k_spmv_fold(const double* __restrict__ part, const int32_t* __restrict__ crow, c
         if (lane == 0) sp_epilogue<T, MODE>(E, crow[j], a, acc);
     }
     block_reduce_store<K>(acc, 0u, parts, slot0, vb0 + (int)blockIdx.x);
+}
+
+// MODE -> the row kernel's entry point, and its name as the profile labels spell it.  (k_spmv_q_algrad takes the rows as given
+// beside the matrix: another signature, launched by name.)
+template <class T, int L, bool NT, int MODE> constexpr auto sp_kernel() {
+    static_assert(MODE >= 0 && MODE < SP_NMODES && MODE != SP_Q_ALGRAD, "a mode of the row loop");
+    if constexpr (MODE == SP_YUPD) return &k_spmv_yupd<T, L, NT>;
+    else if constexpr (MODE == SP_T_FINISH) return &k_spmv_t_finish<T, L, NT>;
+    else if constexpr (MODE == SP_Q) return &k_spmv_q<T, L, NT>;
+    else if constexpr (MODE == SP_LS_R) return &k_spmv_ls_r<T, L, NT>;
+    else if constexpr (MODE == SP_LS_T_ALGRAD) return &k_spmv_ls_t_algrad<T, L, NT>;
+    else if constexpr (MODE == SP_T) return &k_spmv_ls_t<T, L, NT>;
+    else if constexpr (MODE == SP_LOGIT_R) return &k_spmv_logit_r<T, L, NT>;
+    else return &k_spmv_glm_r<T, L, NT, MODE>;
+}
+constexpr const char* sp_kernel_name(int MODE) {
+    constexpr const char* names[] = {"k_spmv_yupd", "k_spmv_t_finish", "k_spmv_q_algrad", "k_spmv_q",
+                                     "k_spmv_ls_r", "k_spmv_ls_t_algrad", "k_spmv_ls_t", "k_spmv_logit_r"};
+    return MODE < SP_GLM_MODE0 ? names[MODE] : "k_spmv_glm_r";
 }
 
 }  // namespace bz
