@@ -1141,7 +1141,9 @@ template <class T> class Solver final : public SolverBase {
     int xr_run_ = 0;             // consecutive plain, pair-inserting iterations so far
     bool sy_stale_ = false;      // S_/Y_ do not hold the stored pairs (they live in the x ring)
     double gring_[NXR] = {0};    // the gamma the residual of each iterate in the ring was (or would be) formed with
-    void materialize_pairs() {
+    void materialize_pairs() { materialize_pairs((double)state_.gamma); }
+    // gam_cur: the gamma the current iterate's residual is formed with (state_.gamma, but for a state whose last trial halved it)
+    void materialize_pairs(double gam_cur) {
         if (!sy_stale_) return;
         SnapVecs<T, CM> V;
         std::memset(&V, 0, sizeof(V));
@@ -1149,7 +1151,7 @@ template <class T> class Solver final : public SolverBase {
         for (int i = 0; i <= CM; ++i) {
             const int back = std::max(0, m - i);
             V.XH[i] = X_[(xc - back + NXR) % NXR].p;
-            V.gam[i] = back ? gring_[(xc - back + NXR) % NXR] : (double)state_.gamma;
+            V.gam[i] = back ? gring_[(xc - back + NXR) % NXR] : gam_cur;
         }
         for (int i = 0; i < m; ++i) { V.S[i] = S_[state_.lbfgs.order[m - 1 - i]].p; V.Y[i] = Y_[state_.lbfgs.order[m - 1 - i]].p; }
         if (slack) {
@@ -1721,16 +1723,18 @@ template <class T> class Solver final : public SolverBase {
     // (likewise the residual res = x - z into RES_[rc] when the pass did not store it)
     // need_res = false: the caller reads z only (the solution of a subproblem, alps.jl:67): a z that the last pass stored is
     // enough, whatever the state of res (the iterate-history passes never write it)
-    void ensure_z(bool need_res = true) {
+    void ensure_z(bool need_res = true) { ensure_z(need_res, state_.gamma); }
+    // gam: the gamma z and res of the current state belong to (see materialize_pairs)
+    void ensure_z(bool need_res, T gam) {
         if (state_.z_valid && (state_.res_valid || !need_res)) return;
         if (begin_fb_ok()) {
             mv(1 + pstreams(true, true, true) + 1 + (state_.res_valid ? 0 : 1));
-            launch(C_FB, k_zres_elem<T>, grid, (const T*)X_[xc].p, P, state_.gamma, Z_[zc].p,
+            launch(C_FB, k_zres_elem<T>, grid, (const T*)X_[xc].p, P, gam, Z_[zc].p,
                    state_.res_valid ? (T*)nullptr : RES_[rc].p, n);      // the two kernels below in one pass
         } else {
             dense_redo([&] {
                 algrad(X_[xc].p, D_.p, SL_AUX);              // scratch gradient: GX_/GZ_ keep their meaning
-                fbstep(X_[xc].p, D_.p, state_.gamma, Z_[zc].p, state_.res_valid ? (T*)nullptr : RES_[rc].p, SL_ZS);
+                fbstep(X_[xc].p, D_.p, gam, Z_[zc].p, state_.res_valid ? (T*)nullptr : RES_[rc].p, SL_ZS);
             });
         }
         state_.z_valid = true; state_.res_valid = true;
@@ -3229,6 +3233,11 @@ template <class T> class Solver final : public SolverBase {
         bool tail_used = false; unsigned long long tail_ticket = 0;      // the trial's scalars come back through the ticket
         bool head_on = false, head_fb = false;   // cfg 4: k_dense_head serves this iteration ; ... and has made the FB step of its first trial
         bool state_imgs = false, halved_here = false;      // cfg 4: the state's images are valid ; gamma was halved inside this step
+        // the step's last trial (k = max_backtracks) asked for a halving: the loop ends there, the trial is not repeated and
+        // becomes the state with z, res and the pair formed with the gamma BEFORE the halving (gamma_res); whether that
+        // trial was the first one-pass launch (z, res possibly not stored), and whether its pair lives in the iterate ring only
+        bool halved_last = false, last_fused = false, last_ring = false;
+        T gamma_res = T(0);
         // a backtracked trial point can go through the one-pass kernel too ("trial given" variant) when this iteration's
         // first trial did: that launch's plan and coefficients
         bool trial_ok = false; GatePlan trial_plan; CompactCoef<CM> trial_coef;
@@ -3714,6 +3723,8 @@ template <class T> class Solver final : public SolverBase {
             // that state) as vectors
             // a pass pre-launched for the next iteration assumed this trial is accepted and its pair inserted
             if (gate_pending_ && !(k == 1 && !halve && (FBE_new <= threshold || k >= max_bt) && T(v[7]) > T(0))) gate_abort();
+            it.halved_last = halve && k >= max_bt;
+            if (it.halved_last) { it.last_fused = it.fused_this; it.last_ring = sy_stale_; it.gamma_res = state_.gamma; }
             if (halve) it.trial_ok = false;
             if (sy_stale_ && !it.trial_ok && (halve || !(FBE_new <= threshold || k >= max_bt))) materialize_pairs();
             if ((!state_.z_valid || !state_.res_valid) && (halve || !(FBE_new <= threshold || k >= max_bt))) ensure_z();
@@ -3833,12 +3844,28 @@ template <class T> class Solver final : public SolverBase {
         // (xr_run_: how many of the newest stored pairs are differences of ring neighbours.  The pair of an
         // iteration that halved gamma is one too — y = res_new(gamma/2) - res_prev(gamma), as upstream has it —
         // because every iterate in the ring remembers the gamma of its residual, gring_)
-        xr_run_ = (fused_ok && compact_ok && (ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON) && it.xcur == it.xd) ? (it.reset_this ? 1 : xr_run_ + 1) : 0;
+        const bool inserted = ys > T(0) || dir_kind_ == BZ_DIR_ANDERSON;
+        xr_run_ = (fused_ok && compact_ok && inserted && it.xcur == it.xd) ? (it.reset_this ? 1 : xr_run_ + 1) : 0;
         gring_[it.xcur] = (double)state_.gamma;
         stop_norm_ = it.v[9];
         xc = it.xcur; rc = it.rn; zc = it.zn;
-        state_.z_valid = !(it.z_skipped && it.fused_this);      // the generic trial writes z; an accepted fused one may not have
-        state_.res_valid = !(it.res_skipped && it.fused_this);  // ... nor res
+        // the generic trial writes z; an accepted fused one may not have, nor res.  (The trial that became the state: the
+        // accepted one, or the last one where the loop ended on its halving, fused_this being cleared by then)
+        const bool trial_fused = it.halved_last ? it.last_fused : it.fused_this;
+        state_.z_valid = !(it.z_skipped && trial_fused);
+        state_.res_valid = !(it.res_skipped && trial_fused);
+        if (it.halved_last) {
+            // The loop ended on a halving in its last trial.  That trial was not repeated: it is the new state, and its z,
+            // res and pair belong to the gamma before the halving, as upstream has it.  The iterate-history passes would
+            // re-evaluate this iterate's residual with the halved gamma, so the run of ring differences starts over and
+            // the ring remembers the gamma the residual was formed with.  What the trial did not leave as vectors (a
+            // one-pass launch stores neither res nor, as a rule, z; the iterate-history forms keep the pair in the ring)
+            // is formed here, with that gamma.
+            xr_run_ = 0;
+            gring_[xc] = (double)it.gamma_res;
+            if (it.last_ring && inserted && it.xcur == it.xd) { sy_stale_ = true; materialize_pairs(gring_[xc]); }
+            ensure_z(true, it.gamma_res);
+        }
         last_nbt = it.nbt; last_fused = it.fused_this;
         if (it.fused_this) ++cnt_.n_fused;
     }
