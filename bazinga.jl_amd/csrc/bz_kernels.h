@@ -502,11 +502,26 @@ __device__ __noinline__ T lp_prox(T x, T p, T alpha, T u, bool box, T& zp) {
     const T psi = zbar + ap * pow(zbar, p - T(1));
     if (psi >= x) return T(0);
     T z = zbar + (box ? T(0.1) : T(1));          // perturbation to the right
+    // dphi is convex and increasing right of zbar: once an iterate is right of the root, the exact iteration stays
+    // there and dphi falls strictly.  The absolute 1e-12 of the reference is below an ulp of x for a large x (and for
+    // nearly every x in fp32), where its loop runs all 1000 steps within a few ulps of the root; so the loop also
+    // ends when |dphi|, after dphi has once been positive, no longer falls (and returns the iterate before, whose
+    // |dphi| was the smallest), or when a step leaves z as it is: rounding has taken over.  (A NaN passes none of
+    // these tests but the last: the iterate is lost, as in the reference.)
+    T prev = T(0), zprev = z;
+    bool seen = false;
     for (int iter = 0; iter < 1000; ++iter) {
         const T dphi = z - x + ap * pow(z, p - T(1));
-        if ((dphi < T(0) ? -dphi : dphi) <= T(1e-12)) break;
+        const T adphi = dphi < T(0) ? -dphi : dphi;
+        if (adphi <= T(1e-12)) break;
+        if (seen && adphi >= prev) { z = zprev; break; }
+        if (dphi > T(0)) seen = true;
+        if (seen) { prev = adphi; zprev = z; }
         const T ddphi = T(1) + ap * (p - T(1)) * pow(z, p - T(2));
-        z -= dphi / ddphi;
+        const T zn = z - dphi / ddphi;
+        if (zn == z) break;
+        z = zn;
+        if (zn != zn) break;
     }
     const T phi0 = T(0.5) * (x * x);
     const T dz = z - x;

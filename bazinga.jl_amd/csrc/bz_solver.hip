@@ -1935,12 +1935,14 @@ template <class T> class Solver final : public SolverBase {
         if (slack) {
             for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = grid_y;
             mv(2 * (1 + (g ? 1 : 0) + 1 + (res ? 1 : 0)) + pstreams(false, false, true) + (P.D_lo_vec ? 1 : 0) + (P.D_hi_vec ? 1 : 0), nx);
+            nm(lp_g ? "k_fbstep_slack<LP=1>" : "k_fbstep_slack<LP=0>");
             if (lp_g) launch(C_FB, k_fbstep_slack<T, true>, grid_y, x, g, gam, P, z, res, nx, parts_.p, slot0);
             else launch(C_FB, k_fbstep_slack<T, false>, grid_y, x, g, gam, P, z, res, nx, parts_.p, slot0);
             return;
         }
         for (int k = 0; k < 3; ++k) slot_n[slot0 + k] = grid;
         mv(1 + (g ? 1 : 0) + 1 + (res ? 1 : 0) + pstreams(false, false, true));
+        nm(lp_g ? "k_fbstep<LP=1>" : "k_fbstep<LP=0>");
         if (lp_g) launch(C_FB, k_fbstep<T, true>, grid, x, g, gam, P, z, res, n, parts_.p, slot0);
         else launch(C_FB, k_fbstep<T, false>, grid, x, g, gam, P, z, res, n, parts_.p, slot0);
     }

@@ -336,8 +336,9 @@ class NormL0Box:
 def _solve_lp_quasi_norm(x, p, a, gamma, u=None):
     """Vectorised transcription of solve_lp_quasi_norm_subproblem_nonneg / _box
     (src/proxoperators/normLpNonneg.jl:44-84, normLpBox.jl:47-97): per element the same Newton
-    iteration with the same start, stopping rule (|dphi| <= 1e-12, at most 1000 steps) and the same
-    global-minimum tests; elements that have stopped are frozen."""
+    iteration with the same start, the reference's stopping rule (|dphi| <= 1e-12, at most 1000 steps) and the same
+    global-minimum tests; elements that have stopped are frozen.  One departure, shared with the device: the loop also
+    ends once rounding has taken over (below), where the reference runs out its 1000 steps."""
     T = x.dtype.type
     box = u is not None
     alpha = T(a) * T(gamma)
@@ -356,13 +357,30 @@ def _solve_lp_quasi_norm(x, p, a, gamma, u=None):
     xa = x[act]
     z = np.full_like(xa, zbar + (T(0.1) if box else T(1)))
     run = np.ones(xa.shape, bool)
+    # Beside the reference's rule the loop ends once rounding has taken over: dphi is convex and
+    # increasing right of zbar, so once it has been positive it falls strictly in exact arithmetic; the loop ends when
+    # |dphi| then no longer falls (and returns the iterate before, whose |dphi| was the smallest), or when a step leaves z
+    # as it is, or makes it NaN.
+    seen = np.zeros(xa.shape, bool)
+    prev = np.zeros_like(xa)
+    zprev = z.copy()
     for _ in range(1000):
         dphi = z - xa + ap * z ** (p - T(1))
-        run &= ~(np.abs(dphi) <= 1e-12)
+        adphi = np.abs(dphi)
+        run &= ~(adphi <= 1e-12)
+        back = run & seen & (adphi >= prev)
+        z = np.where(back, zprev, z)
+        run &= ~back
         if not np.any(run):
             break
+        seen |= run & (dphi > 0)
+        upd = run & seen
+        prev = np.where(upd, adphi, prev)
+        zprev = np.where(upd, z, zprev)
         ddphi = T(1) + ap * (p - T(1)) * z ** (p - T(2))
-        z = np.where(run, z - dphi / ddphi, z)
+        zn = np.where(run, z - dphi / ddphi, z)
+        run &= ~(zn == z) & ~(zn != zn)
+        z = zn
     phi0 = T(0.5) * (xa * xa)
     phiz = T(0.5) * (z - xa) ** 2 + alpha * z ** p
     res = np.where(phi0 <= phiz, T(0), z)

@@ -22,6 +22,7 @@ import pytest
 from tests.stress.stress_als import draw_case
 from tests.test_gpu_family_table import D_VEC_FORMS, G_VEC_FORMS
 from tests.test_gpu_parity import RTOL_ITER, LongDoubleReducer, _err, iter_tol
+from tests.test_lp_prox_host import g_bound as lp_g_bound, g_exact as lp_g_exact
 
 pytestmark = [pytest.mark.gpu, pytest.mark.timeout(900)]
 
@@ -195,7 +196,7 @@ def test_slack_elements_bit_exact_over_the_table(bz, ref, g, D, dt):
     two reduced values to 1e-13 in fp64 and within 100 x the oracle's own two roundings (floored at eps) in fp32.
     The Newton kinds' x half of the prox follows test_lp_power_prox (pow is not correctly rounded on either side): the same
     support but for ties, 1e-10 on it in fp64; in fp32 the device stays within 10 x the fp32 oracle's own distance to the
-    fp64 oracle on the same arguments."""
+    fp64 oracle on the same arguments.  Their value of g is held, in both types, to alpha * sum z^p over the device's own z."""
     dtype = np.dtype(dt).type
     fp64 = dtype == np.float64
     pk = pack_of(dtype)
@@ -258,6 +259,11 @@ def test_slack_elements_bit_exact_over_the_table(bz, ref, g, D, dt):
                             print("fp32 value %s %s n=%d: |device - oracle| = %.3e, oracle's two roundings %.3e, bound %.3e"
                                   % (name, cid((g, D)), n, abs(v_d - v0) / scale, abs(v0 - v1) / scale, tol))
                         assert abs(v_d - v0) <= tol * scale, (case, name, v_d, v0, v1)
+                if g in LP_KINDS:
+                    # the Newton kinds' value of g in both types: alpha * sum z^p in long double over the device's own z,
+                    # within the bound of tests/test_lp_prox_host.py (the sum, the power, the two conversions)
+                    ex = lp_g_exact(z_dev[:n], 0.5, 0.8, dtype)
+                    assert abs(np.longdouble(gz_dev) - ex) <= lp_g_bound(n, dtype) * ex, (case, gz_dev, ex)
         finally:
             prob.close()
 
