@@ -104,7 +104,113 @@ class Quadratic(ProximableFunction):
         return x.dtype.type(0.5) * np.dot(x, Qx) + np.dot(self.q, x)
 
 
-class SparseQuadratic(ProximableFunction):
+_REALS = (np.float64, np.float32)
+_I32_MAX = 2 ** 31 - 1
+
+
+def _real_array(a, name, dtype):
+    """labels, b or weights as a contiguous real array: float64 / float32 as given, integers taking `dtype` (that of data)"""
+    a = np.asarray(a)
+    if not (np.issubdtype(a.dtype, np.integer) or a.dtype in _REALS):
+        raise ValueError(f"{name} must be float64, float32 or integers")
+    return np.asarray(a, dtype=dtype if np.issubdtype(a.dtype, np.integer) else a.dtype, order="C")
+
+
+class _CSR:
+    """What the six classes below that carry a CSR matrix share: its validation in two steps (`_csr_types` before a class's
+    own checks of b / labels, `_csr_shape` after them, so that the first error of a faulty input is the same in every class),
+    the matrix methods, and the two products."""
+
+    def _csr_types(self, indptr, indices, data, other, name, both=False):
+        """step one: one-dimensional arrays (`other`, called `name` in the messages, is q, b or the labels), integer
+        indptr / indices, a float64 / float32 data (both=True: and `other`)"""
+        ip, ix = np.asarray(indptr), np.asarray(indices)
+        self.data = np.ascontiguousarray(data)
+        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or other.ndim != 1:
+            raise ValueError(f"indptr, indices, data and {name} must be one-dimensional")
+        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
+            raise ValueError("indptr and indices must be integer arrays")
+        if self.data.dtype not in _REALS or (both and other.dtype not in _REALS):
+            raise ValueError(f"data{' and ' + name if both else ''} must be float64 or float32")
+        self.indptr, self.indices = ip, ix                   # (as given until _csr_shape has checked them)
+
+    def _csr_shape(self, rows, cols, rows_name):
+        """step two: indptr / indices against `rows` (called `rows_name` in the message) and `cols`, then their int64 /
+        int32 forms and the row of every entry"""
+        ip, ix = self.indptr, self.indices
+        if ip.shape[0] != rows + 1:
+            raise ValueError(f"indptr must have length {rows_name} + 1 = {rows + 1}")
+        if ix.shape[0] != self.data.shape[0]:
+            raise ValueError("indices and data must have the same length")
+        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
+            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
+        if ix.shape[0] and (ix.min() < 0 or ix.max() >= cols):
+            raise ValueError(f"column indices must lie in [0, {cols})")
+        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
+        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
+        self._shape = (rows, cols)
+        self._rows = np.repeat(np.arange(rows, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+
+    @property
+    def nnz(self):
+        return int(self.indices.shape[0])
+
+    @staticmethod
+    def _csr_of_dense(A, what, square=False):
+        """((indptr, indices, data), columns) of the non-zeros of a dense matrix; `what` is the class's "A must be ..." """
+        A = np.asarray(A)
+        if A.ndim != 2 or (square and A.shape[0] != A.shape[1]):
+            raise ValueError(what)
+        mask = A != 0
+        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
+        indices = np.nonzero(mask)[1].astype(np.int32)
+        return (indptr, indices, np.ascontiguousarray(A[mask])), A.shape[1]
+
+    @staticmethod
+    def _csr_of_scipy(M):
+        """the same of any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
+        import scipy.sparse as sp
+        M = sp.csr_matrix(M)
+        return (M.indptr, M.indices, M.data), M.shape[1]
+
+    def toarray(self):
+        A = np.zeros(self._shape, self.data.dtype)
+        np.add.at(A, (self._rows, self.indices), self.data)
+        return A
+
+    def _matvec(self, x):
+        """A x: the float64 sums, not rounded (every caller rounds where its formula does)"""
+        return np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self._shape[0])
+
+    def _rmatvec(self, v):
+        """A'v, as _matvec"""
+        return np.bincount(self.indices, weights=self.data * v[self._rows], minlength=self._shape[1])
+
+
+class _RowWeighted:
+    """`weights` and `scale` of SparseGLM and SparseMultinomial: a weight per row (w[m] >= 0, or None) and one number > 0"""
+
+    def _set_row_weights(self, weights, scale):
+        if not (np.ndim(scale) == 0 and np.isfinite(scale) and scale > 0):
+            raise ValueError("scale must be a finite number > 0")
+        self.scale = float(scale)
+        self.weights = None
+        if weights is not None:
+            w = _real_array(weights, "weights", self.data.dtype)
+            if w.shape != (self.m,) or not np.all(np.isfinite(w) & (w >= 0)):
+                raise ValueError(f"weights must be {self.m} finite numbers >= 0")
+            self.weights = w
+
+    def row_weights(self, dtype):
+        """w^ in dtype: scale * w with the product in float64, rounded once (without weights the one number scale)"""
+        dt = np.dtype(dtype).type
+        with np.errstate(over="ignore"):                 # (a product beyond the dtype's range rounds to inf: lower() refuses it)
+            if self.weights is None:
+                return dt(self.scale)
+            return (self.scale * self.weights.astype(np.float64)).astype(dt)
+
+
+class SparseQuadratic(_CSR, ProximableFunction):
     """ProximalOperators.Quadratic(Q, q) with a sparse Q: f(x) = 0.5 x'Qx + q'x, Q symmetric n-by-n in CSR (indptr[n + 1],
     indices[nnz] 0-based, data[nnz]), never densified.  The conventions of SparseAffine: the column indices of a row
     need not be sorted, an index that occurs twice in a row contributes twice, an empty row gives (Qx)_i = 0.  Symmetry
@@ -113,29 +219,12 @@ class SparseQuadratic(ProximableFunction):
     generic-oracle protocol); on the device the kind is BZ_F_SPARSE_QUADRATIC."""
 
     def __init__(self, indptr, indices, data, q, *, check_symmetric=True):
-        ip, ix = np.asarray(indptr), np.asarray(indices)
-        self.data = np.ascontiguousarray(data)
         self.q = np.ascontiguousarray(q)
-        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or self.q.ndim != 1:
-            raise ValueError("indptr, indices, data and q must be one-dimensional")
-        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
-            raise ValueError("indptr and indices must be integer arrays")
-        if self.data.dtype not in (np.float64, np.float32) or self.q.dtype not in (np.float64, np.float32):
-            raise ValueError("data and q must be float64 or float32")
+        self._csr_types(indptr, indices, data, self.q, "q", both=True)
         self.n = self.q.shape[0]
-        if self.n <= 0 or self.n > 2 ** 31 - 1:
+        if self.n <= 0 or self.n > _I32_MAX:
             raise ValueError("n must be in 1 .. 2^31 - 1")
-        if ip.shape[0] != self.n + 1:
-            raise ValueError(f"indptr must have length n + 1 = {self.n + 1}")
-        if ix.shape[0] != self.data.shape[0]:
-            raise ValueError("indices and data must have the same length")
-        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
-            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
-        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
-            raise ValueError(f"column indices must lie in [0, {self.n})")
-        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
-        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
-        self._rows = np.repeat(np.arange(self.n, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
+        self._csr_shape(self.n, self.n, "n")
         if check_symmetric and not self._is_symmetric():
             raise ValueError("Q must be symmetric (the summed entries of Q and Q' differ)")
 
@@ -156,34 +245,17 @@ class SparseQuadratic(ProximableFunction):
         fb[np.searchsorted(keys, kb)] = vb
         return bool(np.array_equal(fa, fb))
 
-    @property
-    def nnz(self):
-        return int(self.indices.shape[0])
-
     @classmethod
     def from_dense(cls, Q, q, **kw):
-        Q = np.asarray(Q)
-        if Q.ndim != 2 or Q.shape[0] != Q.shape[1]:
-            raise ValueError("Q must be n-by-n")
-        mask = Q != 0
-        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
-        indices = np.nonzero(mask)[1].astype(np.int32)
-        return cls(indptr, indices, np.ascontiguousarray(Q[mask]), q, **kw)
+        csr, _ = cls._csr_of_dense(Q, "Q must be n-by-n", square=True)
+        return cls(*csr, q, **kw)
 
     @classmethod
     def from_scipy(cls, M, q, **kw):
-        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
-        import scipy.sparse as sp
-        M = sp.csr_matrix(M)
-        return cls(M.indptr, M.indices, M.data, q, **kw)
-
-    def toarray(self):
-        Q = np.zeros((self.n, self.n), self.data.dtype)
-        np.add.at(Q, (self._rows, self.indices), self.data)
-        return Q
+        return cls(*cls._csr_of_scipy(M)[0], q, **kw)
 
     def _Qx(self, x):
-        return np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.n).astype(x.dtype, copy=False)
+        return self._matvec(x).astype(x.dtype, copy=False)
 
     def __call__(self, x):
         return x.dtype.type(0.5) * np.dot(x, self._Qx(x)) + np.dot(x, self.q)
@@ -195,7 +267,7 @@ class SparseQuadratic(ProximableFunction):
         return fx + np.dot(x, self.q)
 
 
-class SparseLeastSquares(ProximableFunction):
+class SparseLeastSquares(_CSR, ProximableFunction):
     """ProximalOperators.LeastSquares(A, b) with a sparse A: f(x) = 0.5||A x - b||^2, A m-by-n in CSR (indptr[m + 1],
     indices[nnz] 0-based, data[nnz]), never densified and never squared into A'A.  The conventions of SparseAffine: the
     column indices of a row need not be sorted, an index that occurs twice in a row contributes twice, an empty row gives
@@ -203,59 +275,26 @@ class SparseLeastSquares(ProximableFunction):
     ref.LeastSquares' formulas (the generic-oracle protocol); on the device the kind is BZ_F_SPARSE_LEAST_SQUARES."""
 
     def __init__(self, indptr, indices, data, b, n):
-        ip, ix = np.asarray(indptr), np.asarray(indices)
-        self.data = np.ascontiguousarray(data)
         self.b = np.ascontiguousarray(b)
         self.n = int(n)
-        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or self.b.ndim != 1:
-            raise ValueError("indptr, indices, data and b must be one-dimensional")
-        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
-            raise ValueError("indptr and indices must be integer arrays")
-        if self.data.dtype not in (np.float64, np.float32) or self.b.dtype not in (np.float64, np.float32):
-            raise ValueError("data and b must be float64 or float32")
+        self._csr_types(indptr, indices, data, self.b, "b", both=True)
         self.m = self.b.shape[0]
-        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+        if self.n <= 0 or self.n > _I32_MAX or self.m <= 0 or self.m > _I32_MAX:
             raise ValueError("n and the length of b must be in 1 .. 2^31 - 1")
-        if ip.shape[0] != self.m + 1:
-            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
-        if ix.shape[0] != self.data.shape[0]:
-            raise ValueError("indices and data must have the same length")
-        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
-            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
-        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
-            raise ValueError(f"column indices must lie in [0, {self.n})")
-        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
-        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
-        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
-
-    @property
-    def nnz(self):
-        return int(self.indices.shape[0])
+        self._csr_shape(self.m, self.n, "m")
 
     @classmethod
     def from_dense(cls, A, b):
-        A = np.asarray(A)
-        if A.ndim != 2:
-            raise ValueError("A must be m-by-n")
-        mask = A != 0
-        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
-        indices = np.nonzero(mask)[1].astype(np.int32)
-        return cls(indptr, indices, np.ascontiguousarray(A[mask]), b, A.shape[1])
+        csr, n = cls._csr_of_dense(A, "A must be m-by-n")
+        return cls(*csr, b, n)
 
     @classmethod
     def from_scipy(cls, M, b):
-        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
-        import scipy.sparse as sp
-        M = sp.csr_matrix(M)
-        return cls(M.indptr, M.indices, M.data, b, M.shape[1])
-
-    def toarray(self):
-        A = np.zeros((self.m, self.n), self.data.dtype)
-        np.add.at(A, (self._rows, self.indices), self.data)
-        return A
+        csr, n = cls._csr_of_scipy(M)
+        return cls(*csr, b, n)
 
     def _residual(self, x):
-        return (np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.m) - self.b).astype(x.dtype, copy=False)
+        return (self._matvec(x) - self.b).astype(x.dtype, copy=False)
 
     def __call__(self, x):
         r = self._residual(x)
@@ -263,11 +302,11 @@ class SparseLeastSquares(ProximableFunction):
 
     def gradient(self, dfx, x):
         r = self._residual(x)
-        dfx[...] = np.bincount(self.indices, weights=self.data * r[self._rows], minlength=self.n)
+        dfx[...] = self._rmatvec(r)
         return x.dtype.type(0.5) * np.dot(r, r)
 
 
-class SparseLogistic(ProximableFunction):
+class SparseLogistic(_CSR, ProximableFunction):
     """The logistic loss of a sparse design matrix: f(x) = sum_i log(1 + exp(-b_i a_i'x)), A m-by-n in CSR (indptr[m + 1],
     indices[nnz] 0-based, data[nnz]), labels b in {-1, +1}^m, never densified.  The plain sum: no 1/2 and no 1/m.  The matrix
     conventions of SparseLeastSquares (unsorted and repeated column indices, empty rows and columns, nnz = 0).  With
@@ -277,66 +316,31 @@ class SparseLogistic(ProximableFunction):
     (the generic-oracle protocol); on the device the kind is BZ_F_SPARSE_LOGISTIC."""
 
     def __init__(self, indptr, indices, data, labels, n):
-        ip, ix = np.asarray(indptr), np.asarray(indices)
-        self.data = np.ascontiguousarray(data)
         lab = np.asarray(labels)
         self.n = int(n)
-        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or lab.ndim != 1:
-            raise ValueError("indptr, indices, data and labels must be one-dimensional")
-        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
-            raise ValueError("indptr and indices must be integer arrays")
-        if self.data.dtype not in (np.float64, np.float32):
-            raise ValueError("data must be float64 or float32")
-        if not (np.issubdtype(lab.dtype, np.integer) or lab.dtype in (np.float64, np.float32)):
-            raise ValueError("labels must be float64, float32 or integers")
-        if not np.all(np.abs(lab) == 1):
+        self._csr_types(indptr, indices, data, lab, "labels")
+        self.b = _real_array(lab, "labels", self.data.dtype)
+        if not np.all(np.abs(self.b) == 1):
             raise ValueError("labels must be -1 or +1")
-        self.b = np.ascontiguousarray(lab, dtype=self.data.dtype if np.issubdtype(lab.dtype, np.integer) else lab.dtype)
         self.m = self.b.shape[0]
-        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+        if self.n <= 0 or self.n > _I32_MAX or self.m <= 0 or self.m > _I32_MAX:
             raise ValueError("n and the number of labels must be in 1 .. 2^31 - 1")
-        if ip.shape[0] != self.m + 1:
-            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
-        if ix.shape[0] != self.data.shape[0]:
-            raise ValueError("indices and data must have the same length")
-        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
-            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
-        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
-            raise ValueError(f"column indices must lie in [0, {self.n})")
-        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
-        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
-        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
-
-    @property
-    def nnz(self):
-        return int(self.indices.shape[0])
+        self._csr_shape(self.m, self.n, "m")
 
     @classmethod
     def from_dense(cls, A, labels):
-        A = np.asarray(A)
-        if A.ndim != 2:
-            raise ValueError("A must be m-by-n")
-        mask = A != 0
-        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
-        indices = np.nonzero(mask)[1].astype(np.int32)
-        return cls(indptr, indices, np.ascontiguousarray(A[mask]), labels, A.shape[1])
+        csr, n = cls._csr_of_dense(A, "A must be m-by-n")
+        return cls(*csr, labels, n)
 
     @classmethod
     def from_scipy(cls, M, labels):
-        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
-        import scipy.sparse as sp
-        M = sp.csr_matrix(M)
-        return cls(M.indptr, M.indices, M.data, labels, M.shape[1])
-
-    def toarray(self):
-        A = np.zeros((self.m, self.n), self.data.dtype)
-        np.add.at(A, (self._rows, self.indices), self.data)
-        return A
+        csr, n = cls._csr_of_scipy(M)
+        return cls(*csr, labels, n)
 
     def _loss_r(self, x):
         """the rows' losses softplus(-u) and r = -b sigma(-u), u = b * (A x), in the dtype of x"""
         dt = x.dtype.type
-        t = np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.m).astype(x.dtype, copy=False)
+        t = self._matvec(x).astype(x.dtype, copy=False)
         b = self.b.astype(x.dtype, copy=False)
         u = b * t
         with np.errstate(over="ignore", invalid="ignore"):
@@ -350,11 +354,11 @@ class SparseLogistic(ProximableFunction):
 
     def gradient(self, dfx, x):
         loss, r = self._loss_r(x)
-        dfx[...] = np.bincount(self.indices, weights=self.data * r[self._rows], minlength=self.n)
+        dfx[...] = self._rmatvec(r)
         return x.dtype.type(np.sum(loss))
 
 
-class SparseGLM(ProximableFunction):
+class SparseGLM(_CSR, _RowWeighted, ProximableFunction):
     """A row loss of a sparse design matrix with a weight per row: f(x) = sum_i w^_i l(b_i, t_i), t = A x, w^_i = scale * w_i,
     A m-by-n in CSR (indptr[m + 1], indices[nnz] 0-based, data[nnz]), never densified; the gradient is A'r with
     r_i = w^_i dl/dt(b_i, t_i).  The matrix conventions of SparseLeastSquares (unsorted and repeated column indices, empty rows
@@ -373,24 +377,16 @@ class SparseGLM(ProximableFunction):
     LOSSES = ("least_squares", "logistic", "huber", "squared_hinge", "poisson")
 
     def __init__(self, indptr, indices, data, b, n, loss, delta=None, weights=None, scale=1.0):
-        ip, ix = np.asarray(indptr), np.asarray(indices)
-        self.data = np.ascontiguousarray(data)
         bb = np.asarray(b)
         self.n = int(n)
         if loss not in self.LOSSES:
             raise ValueError(f"unknown loss {loss!r}: one of {self.LOSSES}")
         self.loss = loss
-        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or bb.ndim != 1:
-            raise ValueError("indptr, indices, data and b must be one-dimensional")
-        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
-            raise ValueError("indptr and indices must be integer arrays")
-        if self.data.dtype not in (np.float64, np.float32):
-            raise ValueError("data must be float64 or float32")
-        if not (np.issubdtype(bb.dtype, np.integer) or bb.dtype in (np.float64, np.float32)):
-            raise ValueError("b must be float64, float32 or integers")
-        if loss in ("logistic", "squared_hinge") and not np.all(np.abs(bb) == 1):
+        self._csr_types(indptr, indices, data, bb, "b")
+        self.b = _real_array(bb, "b", self.data.dtype)
+        if loss in ("logistic", "squared_hinge") and not np.all(np.abs(self.b) == 1):
             raise ValueError(f"labels must be -1 or +1 for the {loss} loss")
-        if loss == "poisson" and not np.all(np.isfinite(bb) & (bb >= 0)):
+        if loss == "poisson" and not np.all(np.isfinite(self.b) & (self.b >= 0)):
             raise ValueError("counts must be finite and >= 0 for the poisson loss")
         if loss == "huber":
             if delta is None or not (np.isfinite(delta) and delta > 0):
@@ -398,66 +394,21 @@ class SparseGLM(ProximableFunction):
         elif delta is not None:
             raise ValueError(f"delta is the huber loss's parameter, not the {loss} loss's")
         self.delta = None if delta is None else float(delta)
-        if not (np.ndim(scale) == 0 and np.isfinite(scale) and scale > 0):
-            raise ValueError("scale must be a finite number > 0")
-        self.scale = float(scale)
-        self.b = np.ascontiguousarray(bb, dtype=self.data.dtype if np.issubdtype(bb.dtype, np.integer) else bb.dtype)
         self.m = self.b.shape[0]
-        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+        if self.n <= 0 or self.n > _I32_MAX or self.m <= 0 or self.m > _I32_MAX:
             raise ValueError("n and the length of b must be in 1 .. 2^31 - 1")
-        self.weights = None
-        if weights is not None:
-            w = np.asarray(weights)
-            if not (np.issubdtype(w.dtype, np.integer) or w.dtype in (np.float64, np.float32)):
-                raise ValueError("weights must be float64, float32 or integers")
-            if w.shape != (self.m,) or not np.all(np.isfinite(w) & (w >= 0)):
-                raise ValueError(f"weights must be {self.m} finite numbers >= 0")
-            self.weights = np.ascontiguousarray(w, dtype=self.data.dtype if np.issubdtype(w.dtype, np.integer) else w.dtype)
-        if ip.shape[0] != self.m + 1:
-            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
-        if ix.shape[0] != self.data.shape[0]:
-            raise ValueError("indices and data must have the same length")
-        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
-            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
-        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
-            raise ValueError(f"column indices must lie in [0, {self.n})")
-        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
-        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
-        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
-
-    @property
-    def nnz(self):
-        return int(self.indices.shape[0])
+        self._set_row_weights(weights, scale)
+        self._csr_shape(self.m, self.n, "m")
 
     @classmethod
     def from_dense(cls, A, b, loss, **kw):
-        A = np.asarray(A)
-        if A.ndim != 2:
-            raise ValueError("A must be m-by-n")
-        mask = A != 0
-        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
-        indices = np.nonzero(mask)[1].astype(np.int32)
-        return cls(indptr, indices, np.ascontiguousarray(A[mask]), b, A.shape[1], loss, **kw)
+        csr, n = cls._csr_of_dense(A, "A must be m-by-n")
+        return cls(*csr, b, n, loss, **kw)
 
     @classmethod
     def from_scipy(cls, M, b, loss, **kw):
-        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
-        import scipy.sparse as sp
-        M = sp.csr_matrix(M)
-        return cls(M.indptr, M.indices, M.data, b, M.shape[1], loss, **kw)
-
-    def toarray(self):
-        A = np.zeros((self.m, self.n), self.data.dtype)
-        np.add.at(A, (self._rows, self.indices), self.data)
-        return A
-
-    def row_weights(self, dtype):
-        """w^ in dtype: scale * w with the product in float64, rounded once (without weights the one number scale)"""
-        dt = np.dtype(dtype).type
-        with np.errstate(over="ignore"):                 # (a product beyond the dtype's range rounds to inf: lower() refuses it)
-            if self.weights is None:
-                return dt(self.scale)
-            return (self.scale * self.weights.astype(np.float64)).astype(dt)
+        csr, n = cls._csr_of_scipy(M)
+        return cls(*csr, b, n, loss, **kw)
 
     @staticmethod
     def loss_and_derivative(loss, delta, b, t):
@@ -488,7 +439,7 @@ class SparseGLM(ProximableFunction):
 
     def _loss_r(self, x):
         """the rows' terms w^ l (least_squares: w^ v^2) and r = w^ l' in the dtype of x"""
-        t = np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.m).astype(x.dtype, copy=False)
+        t = self._matvec(x).astype(x.dtype, copy=False)
         l, dl = self.loss_and_derivative(self.loss, self.delta, self.b.astype(x.dtype, copy=False), t)
         w = self.row_weights(x.dtype)
         with np.errstate(over="ignore", invalid="ignore"):
@@ -503,11 +454,11 @@ class SparseGLM(ProximableFunction):
 
     def gradient(self, dfx, x):
         terms, r = self._loss_r(x)
-        dfx[...] = np.bincount(self.indices, weights=self.data * r[self._rows], minlength=self.n)
+        dfx[...] = self._rmatvec(r)
         return self._value(terms, x.dtype.type)
 
 
-class SparseMultinomial(ProximableFunction):
+class SparseMultinomial(_CSR, _RowWeighted, ProximableFunction):
     """Multinomial (softmax) regression on a sparse design matrix: f(X) = sum_i w^_i (logsumexp_k(t_ik) - t_{i,b_i}), T = A X,
     w^_i = scale * w_i; A m-by-n_features in CSR (indptr[m + 1], indices[nnz] 0-based, data[nnz]), never densified; labels b in
     {0 .. K - 1}^m, K = n_classes in 2 .. 64.  X is n_features x K ROW-MAJOR (class fastest): the variable is the flat vector x of
@@ -523,82 +474,35 @@ class SparseMultinomial(ProximableFunction):
     and gamma = alpha / 0, as in the reference's algorithm.  Give the step size: PANOCplus(gamma=1.0, adaptive=True), or Lf."""
 
     def __init__(self, indptr, indices, data, labels, n_features, n_classes, weights=None, scale=1.0):
-        ip, ix = np.asarray(indptr), np.asarray(indices)
-        self.data = np.ascontiguousarray(data)
         lab = np.asarray(labels)
         self.n_features, self.n_classes = int(n_features), int(n_classes)
         if not 2 <= self.n_classes <= 64:
             raise ValueError("n_classes must be in 2 .. 64")
-        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or lab.ndim != 1:
-            raise ValueError("indptr, indices, data and labels must be one-dimensional")
-        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
-            raise ValueError("indptr and indices must be integer arrays")
-        if self.data.dtype not in (np.float64, np.float32):
-            raise ValueError("data must be float64 or float32")
-        if not (np.issubdtype(lab.dtype, np.integer) or lab.dtype in (np.float64, np.float32)):
-            raise ValueError("labels must be float64, float32 or integers")
+        self._csr_types(indptr, indices, data, lab, "labels")
+        self.b = lab = _real_array(lab, "labels", self.data.dtype)
         with np.errstate(invalid="ignore"):
             if not np.all(np.isfinite(lab) & (lab == np.floor(lab)) & (lab >= 0) & (lab < self.n_classes)):
                 raise ValueError(f"labels must be integers in [0, {self.n_classes})")
-        if not (np.ndim(scale) == 0 and np.isfinite(scale) and scale > 0):
-            raise ValueError("scale must be a finite number > 0")
-        self.scale = float(scale)
-        self.b = np.ascontiguousarray(lab, dtype=self.data.dtype if np.issubdtype(lab.dtype, np.integer) else lab.dtype)
         self.m = self.b.shape[0]
         self.n = self.n_features * self.n_classes
-        if self.n_features <= 0 or self.n > 2 ** 31 - 1 or self.m <= 0 or self.m > 2 ** 31 - 1:
+        if self.n_features <= 0 or self.n > _I32_MAX or self.m <= 0 or self.m > _I32_MAX:
             raise ValueError("n_features * n_classes and the number of labels must be in 1 .. 2^31 - 1")
-        self.weights = None
-        if weights is not None:
-            w = np.asarray(weights)
-            if not (np.issubdtype(w.dtype, np.integer) or w.dtype in (np.float64, np.float32)):
-                raise ValueError("weights must be float64, float32 or integers")
-            if w.shape != (self.m,) or not np.all(np.isfinite(w) & (w >= 0)):
-                raise ValueError(f"weights must be {self.m} finite numbers >= 0")
-            self.weights = np.ascontiguousarray(w, dtype=self.data.dtype if np.issubdtype(w.dtype, np.integer) else w.dtype)
-        if ip.shape[0] != self.m + 1:
-            raise ValueError(f"indptr must have length m + 1 = {self.m + 1}")
-        if ix.shape[0] != self.data.shape[0]:
-            raise ValueError("indices and data must have the same length")
-        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
-            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
-        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n_features):
-            raise ValueError(f"column indices must lie in [0, {self.n_features})")
-        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
-        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
-        self._rows = np.repeat(np.arange(self.m, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
-
-    @property
-    def nnz(self):
-        return int(self.indices.shape[0])
+        self._set_row_weights(weights, scale)
+        self._csr_shape(self.m, self.n_features, "m")
 
     @classmethod
     def from_dense(cls, A, labels, n_classes, **kw):
-        A = np.asarray(A)
-        if A.ndim != 2:
-            raise ValueError("A must be m-by-n_features")
-        mask = A != 0
-        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
-        indices = np.nonzero(mask)[1].astype(np.int32)
-        return cls(indptr, indices, np.ascontiguousarray(A[mask]), labels, A.shape[1], n_classes, **kw)
+        csr, n_features = cls._csr_of_dense(A, "A must be m-by-n_features")
+        return cls(*csr, labels, n_features, n_classes, **kw)
 
     @classmethod
     def from_scipy(cls, M, labels, n_classes, **kw):
-        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
-        import scipy.sparse as sp
-        M = sp.csr_matrix(M)
-        return cls(M.indptr, M.indices, M.data, labels, M.shape[1], n_classes, **kw)
-
-    def toarray(self):
-        A = np.zeros((self.m, self.n_features), self.data.dtype)
-        np.add.at(A, (self._rows, self.indices), self.data)
-        return A
+        csr, n_features = cls._csr_of_scipy(M)
+        return cls(*csr, labels, n_features, n_classes, **kw)
 
     def coef(self, x):
         """the (n_features, n_classes) view of the flat variable"""
         return np.asarray(x).reshape(self.n_features, self.n_classes)
-
-    row_weights = SparseGLM.row_weights
 
     @staticmethod
     def softmax_terms(t, labels, w):
@@ -988,7 +892,7 @@ class DenseAffine(SmoothFunction):
         jtv[...] = self.A.T @ v
 
 
-class SparseAffine(SmoothFunction):
+class SparseAffine(_CSR, SmoothFunction):
     """c(x) = A x - b with A[ny][n] in CSR (indptr[ny + 1], indices[nnz] 0-based, data[nnz]): the structured, never
     densified constraint map of demo/obstacle.jl:93-113 (c(x) = x1 + T x2 - x3).  The column indices of a row need not
     be sorted, an index that occurs twice in a row contributes twice, an empty row gives -b_i and an empty column a
@@ -996,62 +900,29 @@ class SparseAffine(SmoothFunction):
     the kind is BZ_C_SPARSE_AFFINE."""
 
     def __init__(self, indptr, indices, data, b, n):
-        ip, ix = np.asarray(indptr), np.asarray(indices)
-        self.data = np.ascontiguousarray(data)
         self.b = np.ascontiguousarray(b)
         self.n = int(n)
-        if ip.ndim != 1 or ix.ndim != 1 or self.data.ndim != 1 or self.b.ndim != 1:
-            raise ValueError("indptr, indices, data and b must be one-dimensional")
-        if not (np.issubdtype(ip.dtype, np.integer) and np.issubdtype(ix.dtype, np.integer)):
-            raise ValueError("indptr and indices must be integer arrays")
-        if self.data.dtype not in (np.float64, np.float32) or self.b.dtype not in (np.float64, np.float32):
-            raise ValueError("data and b must be float64 or float32")
+        self._csr_types(indptr, indices, data, self.b, "b", both=True)
         self.ny = self.b.shape[0]
-        if self.n <= 0 or self.n > 2 ** 31 - 1 or self.ny <= 0:
+        if self.n <= 0 or self.n > _I32_MAX or self.ny <= 0:
             raise ValueError("n must be in 1 .. 2^31 - 1 and b non-empty")
-        if ip.shape[0] != self.ny + 1:
-            raise ValueError(f"indptr must have length ny + 1 = {self.ny + 1}")
-        if ix.shape[0] != self.data.shape[0]:
-            raise ValueError("indices and data must have the same length")
-        if ip[0] != 0 or ip[-1] != ix.shape[0] or np.any(np.diff(ip) < 0):
-            raise ValueError("indptr must start at 0, be non-decreasing and end at nnz")
-        if ix.shape[0] and (ix.min() < 0 or ix.max() >= self.n):
-            raise ValueError(f"column indices must lie in [0, {self.n})")
-        self.indptr = np.ascontiguousarray(ip, dtype=np.int64)
-        self.indices = np.ascontiguousarray(ix, dtype=np.int32)
-        self._rows = np.repeat(np.arange(self.ny, dtype=np.int64), np.diff(self.indptr))      # the row of every entry
-
-    @property
-    def nnz(self):
-        return int(self.indices.shape[0])
+        self._csr_shape(self.ny, self.n, "ny")
 
     @classmethod
     def from_dense(cls, A, b):
-        A = np.asarray(A)
-        if A.ndim != 2:
-            raise ValueError("A must be ny-by-n")
-        mask = A != 0
-        indptr = np.concatenate(([0], np.cumsum(mask.sum(axis=1)))).astype(np.int64)
-        indices = np.nonzero(mask)[1].astype(np.int32)
-        return cls(indptr, indices, np.ascontiguousarray(A[mask]), b, A.shape[1])
+        csr, n = cls._csr_of_dense(A, "A must be ny-by-n")
+        return cls(*csr, b, n)
 
     @classmethod
     def from_scipy(cls, M, b):
-        """from any scipy.sparse matrix (scipy is imported here and nowhere else: it is not a dependency)"""
-        import scipy.sparse as sp
-        M = sp.csr_matrix(M)
-        return cls(M.indptr, M.indices, M.data, b, M.shape[1])
-
-    def toarray(self):
-        A = np.zeros((self.ny, self.n), self.data.dtype)
-        np.add.at(A, (self._rows, self.indices), self.data)
-        return A
+        csr, n = cls._csr_of_scipy(M)
+        return cls(*csr, b, n)
 
     def eval(self, cx, x):
-        cx[...] = np.bincount(self._rows, weights=self.data * x[self.indices], minlength=self.ny) - self.b
+        cx[...] = self._matvec(x) - self.b
 
     def jtprod(self, jtv, x, v):
-        jtv[...] = np.bincount(self.indices, weights=self.data * v[self._rows], minlength=self.n)
+        jtv[...] = self._rmatvec(v)
 
 
 # ------------------------------------------------------------------------- D
@@ -1173,8 +1044,16 @@ def _vec(a, dtype, n, name):
     return v
 
 
-_LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, SparseQuadratic, SparseLeastSquares,
-                                      SparseLogistic, SparseGLM, SparseMultinomial, Stencil5ptQuadratic))
+# the f kinds that carry a CSR matrix: class -> (kind, what a wrong column count raises, the name of the vector in f_b)
+_SPARSE_F = {
+    SparseQuadratic: (L.BZ_F_SPARSE_QUADRATIC, "Q must be {n}-by-{n}", "q"),
+    SparseLeastSquares: (L.BZ_F_SPARSE_LEAST_SQUARES, "A must have {n} columns", "b"),
+    SparseLogistic: (L.BZ_F_SPARSE_LOGISTIC, "A must have {n} columns", "labels"),
+    SparseGLM: (L.BZ_F_SPARSE_GLM, "A must have {n} columns", "b"),
+    SparseMultinomial: (L.BZ_F_SPARSE_MULTINOMIAL, "x must have n_features * n_classes = {fn} elements, not {n}", "labels"),
+}
+
+_LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, *_SPARSE_F, Stencil5ptQuadratic))
 _LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL21, GroupLasso, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
@@ -1273,6 +1152,50 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         keep.append(a)
         return a.ctypes.data
 
+    def csr(side, a):
+        """the matrix of a (_CSR) in the four <side>_sp_* fields"""
+        setattr(d, side + "_sp_rowptr", ptr(a.indptr))
+        setattr(d, side + "_sp_col", ptr(a.indices))
+        setattr(d, side + "_sp_val", ptr(np.ascontiguousarray(a.data, dtype=dtype)))
+        setattr(d, side + "_sp_nnz", a.nnz)
+
+    def num_or_vec(field, value, cnt, name):
+        """a number in d.<field>, or a vector of cnt elements behind d.<field>_vec"""
+        if np.ndim(value) == 0:
+            setattr(d, field, float(value))
+        else:
+            setattr(d, field + "_vec", ptr(_vec(value, dtype, cnt, name)))
+
+    def sparse_f(cls, kind, columns, name):
+        """any f with a CSR matrix (a row of _SPARSE_F)"""
+        # what the library refuses with these kinds, refused here before any device call
+        if slack:
+            raise UnsupportedOracle(f"{cls.__name__} is not lowered in the slack (ALS) form")
+        if isinstance(c, DenseAffine):
+            raise UnsupportedOracle(f"{cls.__name__} is not lowered beside a dense c (DenseAffine)")
+        if f.n != n:
+            raise ValueError(columns.format(n=n, fn=f.n))
+        d.f_kind = kind
+        csr("f", f)
+        if cls is SparseQuadratic:                       # (n-by-n: f_rows stays 0, and f_b carries q)
+            d.f_b = ptr(_vec(f.q, dtype, n, name))
+            return
+        d.f_rows = f.m
+        d.f_b = ptr(_vec(f.b, dtype, f.m, name))
+        delta, finite = None, "scale and scale * weights"          # what must be finite in dtype
+        if cls is SparseGLM:
+            d.f_loss = SparseGLM.LOSSES.index(f.loss)
+            d.f_loss_delta = 0.0 if f.delta is None else f.delta
+            delta, finite = f.delta, "scale, scale * weights and delta"
+        elif cls is SparseMultinomial:
+            d.f_classes = f.n_classes
+        if isinstance(f, _RowWeighted):
+            d.f_scale = f.scale
+            if not np.all(np.isfinite(f.row_weights(dtype))) or (delta is not None and not np.isfinite(dtype.type(delta))):
+                raise ValueError(f"{finite} must be finite in {dtype}")
+            if f.weights is not None:
+                d.f_w = ptr(_vec(f.weights, dtype, f.m, "weights"))
+
     # f
     if isinstance(f, Zero):
         d.f_kind = L.BZ_F_ZERO
@@ -1294,93 +1217,8 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.f_A = ptr(np.ascontiguousarray(f.Q, dtype=dtype))
         d.f_rows = n
         d.f_b = ptr(_vec(f.q, dtype, n, "q"))
-    elif isinstance(f, SparseQuadratic):
-        # what the library refuses with this kind, refused here before any device call
-        if slack:
-            raise UnsupportedOracle("SparseQuadratic is not lowered in the slack (ALS) form")
-        if isinstance(c, DenseAffine):
-            raise UnsupportedOracle("SparseQuadratic is not lowered beside a dense c (DenseAffine)")
-        if f.n != n:
-            raise ValueError(f"Q must be {n}-by-{n}")
-        d.f_kind = L.BZ_F_SPARSE_QUADRATIC
-        d.f_sp_rowptr = ptr(f.indptr)
-        d.f_sp_col = ptr(f.indices)
-        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
-        d.f_sp_nnz = f.nnz
-        d.f_b = ptr(_vec(f.q, dtype, n, "q"))
-    elif isinstance(f, SparseLeastSquares):
-        # what the library refuses with this kind, refused here before any device call
-        if slack:
-            raise UnsupportedOracle("SparseLeastSquares is not lowered in the slack (ALS) form")
-        if isinstance(c, DenseAffine):
-            raise UnsupportedOracle("SparseLeastSquares is not lowered beside a dense c (DenseAffine)")
-        if f.n != n:
-            raise ValueError(f"A must have {n} columns")
-        d.f_kind = L.BZ_F_SPARSE_LEAST_SQUARES
-        d.f_rows = f.m
-        d.f_sp_rowptr = ptr(f.indptr)
-        d.f_sp_col = ptr(f.indices)
-        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
-        d.f_sp_nnz = f.nnz
-        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "b")))
-    elif isinstance(f, SparseLogistic):
-        # what the library refuses with this kind, refused here before any device call
-        if slack:
-            raise UnsupportedOracle("SparseLogistic is not lowered in the slack (ALS) form")
-        if isinstance(c, DenseAffine):
-            raise UnsupportedOracle("SparseLogistic is not lowered beside a dense c (DenseAffine)")
-        if f.n != n:
-            raise ValueError(f"A must have {n} columns")
-        d.f_kind = L.BZ_F_SPARSE_LOGISTIC
-        d.f_rows = f.m
-        d.f_sp_rowptr = ptr(f.indptr)
-        d.f_sp_col = ptr(f.indices)
-        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
-        d.f_sp_nnz = f.nnz
-        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "labels")))
-    elif isinstance(f, SparseGLM):
-        # what the library refuses with this kind, refused here before any device call
-        if slack:
-            raise UnsupportedOracle("SparseGLM is not lowered in the slack (ALS) form")
-        if isinstance(c, DenseAffine):
-            raise UnsupportedOracle("SparseGLM is not lowered beside a dense c (DenseAffine)")
-        if f.n != n:
-            raise ValueError(f"A must have {n} columns")
-        d.f_kind = L.BZ_F_SPARSE_GLM
-        d.f_rows = f.m
-        d.f_sp_rowptr = ptr(f.indptr)
-        d.f_sp_col = ptr(f.indices)
-        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
-        d.f_sp_nnz = f.nnz
-        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "b")))
-        d.f_loss = SparseGLM.LOSSES.index(f.loss)
-        d.f_loss_delta = 0.0 if f.delta is None else f.delta
-        d.f_scale = f.scale
-        if not np.all(np.isfinite(f.row_weights(dtype))) or (f.delta is not None and not np.isfinite(dtype.type(f.delta))):
-            raise ValueError(f"scale, scale * weights and delta must be finite in {dtype}")
-        if f.weights is not None:
-            d.f_w = ptr(np.ascontiguousarray(_vec(f.weights, dtype, f.m, "weights")))
-    elif isinstance(f, SparseMultinomial):
-        # what the library refuses with this kind, refused here before any device call
-        if slack:
-            raise UnsupportedOracle("SparseMultinomial is not lowered in the slack (ALS) form")
-        if isinstance(c, DenseAffine):
-            raise UnsupportedOracle("SparseMultinomial is not lowered beside a dense c (DenseAffine)")
-        if f.n != n:
-            raise ValueError(f"x must have n_features * n_classes = {f.n} elements, not {n}")
-        d.f_kind = L.BZ_F_SPARSE_MULTINOMIAL
-        d.f_rows = f.m
-        d.f_classes = f.n_classes
-        d.f_sp_rowptr = ptr(f.indptr)
-        d.f_sp_col = ptr(f.indices)
-        d.f_sp_val = ptr(np.ascontiguousarray(f.data, dtype=dtype))
-        d.f_sp_nnz = f.nnz
-        d.f_b = ptr(np.ascontiguousarray(_vec(f.b, dtype, f.m, "labels")))
-        d.f_scale = f.scale
-        if not np.all(np.isfinite(f.row_weights(dtype))):
-            raise ValueError(f"scale and scale * weights must be finite in {dtype}")
-        if f.weights is not None:
-            d.f_w = ptr(np.ascontiguousarray(_vec(f.weights, dtype, f.m, "weights")))
+    elif isinstance(f, tuple(_SPARSE_F)):
+        sparse_f(*next((cls, *row) for cls, row in _SPARSE_F.items() if isinstance(f, cls)))
     elif isinstance(f, Stencil5ptQuadratic):
         d.f_kind = L.BZ_F_STENCIL5
         d.f_grid_nx, d.f_grid_ny = f.nx, f.ny
@@ -1392,10 +1230,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.g_kind = L.BZ_G_ZERO
     elif isinstance(g, NormL1):
         d.g_kind = L.BZ_G_NORM_L1
-        if np.ndim(g.lam) == 0:
-            d.g_lambda = g.lam
-        else:
-            d.g_lambda_vec = ptr(_vec(g.lam, dtype, n, "λ"))
+        num_or_vec("g_lambda", g.lam, n, "λ")
     elif isinstance(g, NormL21):
         # what the library refuses with this kind, refused here before any device call
         if slack:
@@ -1405,10 +1240,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         if n % g.group:
             raise ValueError(f"n = {n} must be a multiple of the group size {g.group}")
         d.g_kind, d.g_group = L.BZ_G_NORM_L21, g.group
-        if np.ndim(g.lam) == 0:
-            d.g_lambda = g.lam
-        else:
-            d.g_lambda_vec = ptr(_vec(g.lam, dtype, n // g.group, "λ"))
+        num_or_vec("g_lambda", g.lam, n // g.group, "λ")
     elif isinstance(g, GroupLasso):
         # what the library refuses with this kind, refused here before any device call
         if slack:
@@ -1419,10 +1251,7 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
             raise ValueError(f"indptr[-1] = {g.indptr[-1]} must be n = {n}")
         d.g_kind, d.g_ngroups, d.g_l1 = L.BZ_G_GROUP_LASSO, g.ngroups, g.l1
         d.g_group_ptr = ptr(g.indptr)
-        if np.ndim(g.lam) == 0:
-            d.g_lambda = g.lam
-        else:
-            d.g_lambda_vec = ptr(_vec(g.lam, dtype, g.ngroups, "λ"))
+        num_or_vec("g_lambda", g.lam, g.ngroups, "λ")
     elif isinstance(g, NormL1Nonneg):
         d.g_kind, d.g_lambda = L.BZ_G_NORM_L1_NONNEG, g.lam
     elif isinstance(g, NormL1Box):
@@ -1438,14 +1267,8 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.g_u = ptr(_vec(g.u, dtype, n, "u"))
     elif isinstance(g, IndBox):
         d.g_kind = L.BZ_G_IND_BOX
-        if np.ndim(g.lb) == 0:
-            d.g_lo = float(g.lb)
-        else:
-            d.g_lo_vec = ptr(_vec(g.lb, dtype, n, "lb"))
-        if np.ndim(g.ub) == 0:
-            d.g_hi = float(g.ub)
-        else:
-            d.g_hi_vec = ptr(_vec(g.ub, dtype, n, "ub"))
+        num_or_vec("g_lo", g.lb, n, "lb")
+        num_or_vec("g_hi", g.ub, n, "ub")
     else:
         raise UnsupportedOracle(f"g of type {type(g).__name__} is not lowered to the device")
     # c
@@ -1464,17 +1287,14 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         # what the library refuses with this kind, refused here before any device call
         if slack:
             raise UnsupportedOracle("SparseAffine is not lowered in the slack (ALS) form")
-        if not isinstance(f, (Zero, DiagQuadratic, SparseQuadratic, SparseLeastSquares, SparseLogistic, SparseGLM, SparseMultinomial)):
+        if not isinstance(f, (Zero, DiagQuadratic, *_SPARSE_F)):
             raise UnsupportedOracle(f"SparseAffine is lowered with an element-wise f (Zero, DiagQuadratic), not {type(f).__name__}")
         if isinstance(D, PairwiseSet):
             raise UnsupportedOracle("pairwise D sets need c = IdentityFunction")
         if (c.ny, c.n) != (ny, n):
             raise ValueError(f"A must be {ny}-by-{n}")
         d.c_kind = L.BZ_C_SPARSE_AFFINE
-        d.c_sp_rowptr = ptr(c.indptr)
-        d.c_sp_col = ptr(c.indices)
-        d.c_sp_val = ptr(np.ascontiguousarray(c.data, dtype=dtype))
-        d.c_sp_nnz = c.nnz
+        csr("c", c)
         d.c_b = ptr(_vec(c.b, dtype, ny, "b"))
     else:
         raise UnsupportedOracle(f"c of type {type(c).__name__} is not lowered to the device")
@@ -1485,14 +1305,8 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
         d.D_kind = L.BZ_D_FREE
     elif isinstance(D, IndicatorSet) and isinstance(D.f, IndBox):
         d.D_kind = L.BZ_D_BOX
-        if np.ndim(D.f.lb) == 0:
-            d.D_lo = float(D.f.lb)
-        else:
-            d.D_lo_vec = ptr(_vec(D.f.lb, dtype, ny, "lb"))
-        if np.ndim(D.f.ub) == 0:
-            d.D_hi = float(D.f.ub)
-        else:
-            d.D_hi_vec = ptr(_vec(D.f.ub, dtype, ny, "ub"))
+        num_or_vec("D_lo", D.f.lb, ny, "lb")
+        num_or_vec("D_hi", D.f.ub, ny, "ub")
     elif isinstance(D, IndicatorSet) and isinstance(D.f, IndFree):
         d.D_kind = L.BZ_D_FREE
     elif isinstance(D, PairwiseSet):
