@@ -19,6 +19,7 @@ BZ_G_ZERO, BZ_G_NORM_L1, BZ_G_NORM_L1_NONNEG, BZ_G_NORM_L1_BOX, BZ_G_IND_BOX, BZ
 BZ_G_NORM_LP_NONNEG, BZ_G_NORM_LP_BOX = 6, 7
 BZ_G_NORM_L21 = 9
 BZ_G_GROUP_LASSO = 10
+BZ_G_ELASTIC_NET = 11
 BZ_C_IDENTITY, BZ_C_DENSE_AFFINE, BZ_C_SPARSE_AFFINE = 0, 1, 3
 BZ_D_ZERO, BZ_D_FREE, BZ_D_BOX = 0, 1, 2
 BZ_D_VC_PAIRS, BZ_D_CC_PAIRS, BZ_D_EITHEROR_PAIRS, BZ_D_XOR_PAIRS = 3, 4, 5, 6
@@ -64,6 +65,7 @@ class ProblemDesc(C.Structure):
         ("f_A", C.c_void_p), ("f_rows", C.c_int64), ("f_classes", C.c_int64),
         ("g_lambda", C.c_double), ("g_p", C.c_double), ("g_group", C.c_int64), ("g_u", C.c_void_p),
         ("g_group_ptr", C.c_void_p), ("g_ngroups", C.c_int64), ("g_l1", C.c_double), ("g_lo", C.c_double), ("g_hi", C.c_double),
+        ("g_l2", C.c_double), ("g_weights", C.c_void_p),
         ("g_lo_vec", C.c_void_p), ("g_hi_vec", C.c_void_p), ("g_lambda_vec", C.c_void_p),
         ("c_A", C.c_void_p), ("c_b", C.c_void_p),
         ("D_lo", C.c_double), ("D_hi", C.c_double), ("D_lo_vec", C.c_void_p), ("D_hi_vec", C.c_void_p),
@@ -132,6 +134,7 @@ SIGNATURES = {
     "bz_panoc_default_opts": (None, [_P(PanocOpts)]),
     "bz_problem_set_multipliers": (C.c_int, [_vp, _vp, _vp]),
     "bz_problem_set_g_lambda": (C.c_int, [_vp, C.c_double, _vp]),
+    "bz_problem_set_g_elastic_net": (C.c_int, [_vp, C.c_double, C.c_double]),
     "bz_panoc_solve": (C.c_int, [_vp, _P(PanocOpts), _vp, _vp, _P(PanocStats)]),
     "bz_panoc_begin": (C.c_int, [_vp, _P(PanocOpts), _vp]),
     "bz_problem_halo_export": (C.c_int, [_vp, _vp]),

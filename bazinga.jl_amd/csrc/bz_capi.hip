@@ -13,7 +13,7 @@ struct bz_problem {
     bz::SolverBase* s;
     int dtype;
     int device;       // kept here so destroy never dereferences a context that was freed first
-    bool stepping;    // between bz_panoc_begin and bz_panoc_finish (bz_problem_set_g_lambda is refused there)
+    bool stepping;    // between bz_panoc_begin and bz_panoc_finish (bz_problem_set_g_lambda and bz_problem_set_g_elastic_net are refused there)
 };
 
 namespace {
@@ -204,6 +204,14 @@ int bz_problem_set_g_lambda(bz_problem* p, double lambda, const void* lambda_vec
         need(p, "problem"); on_device(p->device);
         if (p->stepping) throw bz::Error(BZ_ERR_STATE, "bz_problem_set_g_lambda between bz_panoc_begin and bz_panoc_finish");
         p->s->set_g_lambda(lambda, lambda_vec);
+    });
+}
+
+int bz_problem_set_g_elastic_net(bz_problem* p, double l1, double l2) {
+    return guard([&] {
+        need(p, "problem"); on_device(p->device);
+        if (p->stepping) throw bz::Error(BZ_ERR_STATE, "bz_problem_set_g_elastic_net between bz_panoc_begin and bz_panoc_finish");
+        p->s->set_g_elastic_net(l1, l2);
     });
 }
 

@@ -64,6 +64,11 @@ template <class T> struct ElemParams {
                                // host keeps a problem that has it away from every compile-time form
         const T* g_group_lambda; // NormL21, GroupLasso: lambda[ngroups], one entry per group, or null.  Read through group_lambda_vec() by
                                // k_fbstep_group / k_fbstep_ragged (bz_group.h, bz_group_ragged.h) alone: no element-wise kernel runs with these kinds
+        const T* g_weights;    // ElasticNet: w[n], g = sum w_i (l1 |x_i| + l2/2 x_i^2), or null (every w_i = 1).  Read through weights(),
+                               // and with NormL1's vector through scale_vec(), by the run-time-kind kernels only.  This kind
+                               // holds g_lambda = 1, g_lo = l1, g_hi = l2 (it has no box): every gamma * g_lambda a kernel forms
+                               // is then gamma itself, bit for bit, which is the t of prox_elem's arm, and l1 and l2 reach the
+                               // arm in ElemLoads::glo / ghi with no further argument
     };
     T g_lo, g_hi;
     const T* g_lo_vec;
@@ -73,6 +78,9 @@ template <class T> struct ElemParams {
     const T* D_hi_vec;
     T mu_uniform;          // the value of every mu[i] when the penalties are uniform (k_muy's probe), else unused
     __host__ __device__ const T* lambda_vec() const { return g_kind == BZ_G_NORM_L1 ? g_lambda_vec : nullptr; }
+    __host__ __device__ const T* weights() const { return g_kind == BZ_G_ELASTIC_NET ? g_weights : nullptr; }
+    // the per-element factor of t = gamma * (.) and of the g term: NormL1's lambda or ElasticNet's weights
+    __host__ __device__ const T* scale_vec() const { const T* lam = lambda_vec(); return lam ? lam : weights(); }
     __host__ __device__ const T* group_lambda_vec() const { return g_kind == BZ_G_NORM_L21 || g_kind == BZ_G_GROUP_LASSO ? g_group_lambda : nullptr; }
 };
 
@@ -537,7 +545,8 @@ __device__ __noinline__ T lp_prox(T x, T p, T alpha, T u, bool box, T& zp) {
     return z;
 }
 
-template <class T, bool LP = false>
+// EN = false: a caller the host keeps ElasticNet away from (the fast slack forms): the arm is not compiled into it
+template <class T, bool LP = false, bool EN = true>
 __device__ __forceinline__ T prox_elem(int g_kind, T y, T gl, T u, T lo, T hi, T& gterm, T gp = T(0)) {
     T z;
     if (LP) {                       // the Newton/pow kinds live in their own kernel instantiation
@@ -578,28 +587,44 @@ __device__ __forceinline__ T prox_elem(int g_kind, T y, T gl, T u, T lo, T hi, T
         gterm = T(0);
         break;
     }
+    case BZ_G_ELASTIC_NET: {        // ProximalOperators.ElasticNet with penalty factors: the definition is bazinga_hip.h's list,
+                                    // operation for operation.  gl = t (gamma, or gamma * w_i: gl_elem), lo = l1, hi = l2
+                                    // (ElemParams); 0.5 * l2 has launch-wide operands, so it is formed once; the caller
+                                    // multiplies gterm by w_i (gterm_elem)
+        if constexpr (!EN) { z = y; gterm = T(0); break; }
+        const T a = gl * lo;
+        const T d = T(1) + gl * hi;
+        const T s = y - clamp_mm(y, -a, a);
+        z = s / d;
+        const T az = z > T(0) ? z : -z;
+        const T h2 = T(0.5) * hi;
+        gterm = lo * az + h2 * (z * z);
+        break;
+    }
     default: z = y; gterm = T(0);
     }
     return z;
 }
 
 template <class T> struct ElemLoads {
-    Pack<T> q, b, mu, muy, dlo, dhi, gu, glo, ghi;      // gu: u of the box kinds, or lambda of NormL1 with a vector lambda
+    Pack<T> q, b, mu, muy, dlo, dhi, gu, glo, ghi;      // gu: u of the box kinds, or lambda of NormL1 with a vector lambda, or the weights of ElasticNet
 };
 
 // NormL1 with a per-element lambda (ProximalOperators.NormL1 with an array): gamma*lambda and the g term of element e.
 // The test on the pointer is uniform over the launch; without the vector these return the launch-wide gl and the
 // |z| that the host multiplies by lambda, with it gamma*lambda_e formed in T and lambda_e*|z|, which the host sums as is.
+// ElasticNet with weights goes the same way: gamma*w_e is its t and w_e*term its weighted term (without weights gl is
+// gamma * 1, see ElemParams::g_weights, and the term is summed as it is).
 template <class T>
 __device__ __forceinline__ T gl_elem(const ElemParams<T>& P, const ElemLoads<T>& L, int e, T gamma, T gl) {
-    return P.lambda_vec() ? gamma * L.gu.v[e] : gl;
+    return P.scale_vec() ? gamma * L.gu.v[e] : gl;
 }
 template <class T>
 __device__ __forceinline__ T gterm_elem(const ElemParams<T>& P, const ElemLoads<T>& L, int e, T gterm) {
-    return P.lambda_vec() ? L.gu.v[e] * gterm : gterm;
+    return P.scale_vec() ? L.gu.v[e] * gterm : gterm;
 }
 
-// LAMV = false: a caller whose kinds are compile-time facts (it never holds NormL1's vector lambda)
+// LAMV = false: a caller whose kinds are compile-time facts (it never holds NormL1's vector lambda or ElasticNet's weights)
 template <class T, bool NT = false, bool LAMV = true>
 __device__ __forceinline__ void load_params(const ElemParams<T>& P, int64_t i0, int cnt,
                                             ElemLoads<T>& L, bool need_f, bool need_al,
@@ -615,7 +640,7 @@ __device__ __forceinline__ void load_params(const ElemParams<T>& P, int64_t i0, 
     if (need_g) {
         L.gu = (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX || P.g_kind == BZ_G_NORM_LP_BOX)
                    ? ldp<T, NT>(P.g_u, i0, cnt) : splat(T(0));
-        if constexpr (LAMV) { if (P.lambda_vec()) L.gu = ldp<T, NT>(P.g_lambda_vec, i0, cnt); }
+        if constexpr (LAMV) { if (const T* sv = P.scale_vec()) L.gu = ldp<T, NT>(sv, i0, cnt); }
         L.glo = P.g_lo_vec ? ldp<T, NT>(P.g_lo_vec, i0, cnt) : splat(P.g_lo);
         L.ghi = P.g_hi_vec ? ldp<T, NT>(P.g_hi_vec, i0, cnt) : splat(P.g_hi);
     }
@@ -3753,7 +3778,7 @@ template <class T, int MM> struct SlackIterates {
     const T* XH[MM + 1];
     int m;
 };
-template <class T>
+template <bool EN = true, class T>
 __device__ __forceinline__ void slack_resid(const ElemParams<T>& P, T x, T sv, const ElemLoads<T>& L, int e, T dlo, T dhi, T yv,
                                             T gam, T lam, T& rx, T& rs, T& zx, T& zs, bool udiv = false, T rmu = T(0)) {
     const SlackOut<T> o = slack_elem(P.f_kind, x, sv, L.q.v[e], L.b.v[e], L.mu.v[e], L.muy.v[e], yv, udiv, rmu);
@@ -3762,7 +3787,7 @@ __device__ __forceinline__ void slack_resid(const ElemParams<T>& P, T x, T sv, c
     T u = gam * o.gs;
     const T ys = sv - u;
     T gterm;
-    zx = prox_elem(P.g_kind, yx, gam * lam, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+    zx = prox_elem<T, false, EN>(P.g_kind, yx, gam * lam, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
     zs = proj_D(P.D_kind, ys, dlo, dhi);
     rx = x - zx;
     rs = sv - zs;
@@ -3860,8 +3885,8 @@ k_fused_slack_xr(SlackIterates<T, MM> V, CompactCoef<MM> C, ElemParams<T> P, con
                 for (int e = 0; e < N; ++e) {
                     T zx, zs;
                     T lam = P.g_lambda;                    // (the run-time form alone may hold a vector lambda)
-                    if constexpr (UNI < 0) lam = P.lambda_vec() ? L.gu.v[e] : P.g_lambda;
-                    slack_resid(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, lam, rh[0][i].v[e], rh[1][i].v[e], zx, zs, udiv, rmu);
+                    if constexpr (UNI < 0) lam = P.scale_vec() ? L.gu.v[e] : P.g_lambda;
+                    slack_resid<(UNI < 0)>(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, lam, rh[0][i].v[e], rh[1][i].v[e], zx, zs, udiv, rmu);
                 }
             }
         Pack<T> px[2], prp[2], ps[2][MM], py[2][MM], d[2];
@@ -3898,7 +3923,7 @@ k_fused_slack_xr(SlackIterates<T, MM> V, CompactCoef<MM> C, ElemParams<T> P, con
             T gterm;
             T gle = gl;                                    // (the run-time form alone may hold a vector lambda)
             if constexpr (UNI < 0) gle = gl_elem(P, L, e, gamma, gl);
-            const T a = prox_elem(P.g_kind, yx, gle, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
+            const T a = prox_elem<T, false, (UNI < 0)>(P.g_kind, yx, gle, L.gu.v[e], L.glo.v[e], L.ghi.v[e], gterm);
             if constexpr (UNI < 0) gterm = gterm_elem(P, L, e, gterm);
             const T b = proj_D(P.D_kind, ys, dlo.v[e], dhi.v[e]);
             const T r1 = xd - a, r2 = sd - b;
@@ -4013,7 +4038,7 @@ k_pairs_from_iterates_slack(SnapVecs<T, MM> V, int m, ElemParams<T> P, const T* 
 #pragma unroll
             for (int e = 0; e < N; ++e) {
                 T zx, zs;
-                slack_resid(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, P.lambda_vec() ? L.gu.v[e] : P.g_lambda, rh[0][i].v[e], rh[1][i].v[e], zx, zs);
+                slack_resid(P, xh[0][i].v[e], xh[1][i].v[e], L, e, dlo.v[e], dhi.v[e], pyv.v[e], gi, P.scale_vec() ? L.gu.v[e] : P.g_lambda, rh[0][i].v[e], rh[1][i].v[e], zx, zs);
                 if (i == MM) { pz[0].v[e] = zx; pz[1].v[e] = zs; }
             }
         }

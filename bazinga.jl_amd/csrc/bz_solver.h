@@ -119,6 +119,7 @@ struct SolverBase {
     virtual ~SolverBase() = default;
     virtual void set_multipliers(const void* mu, const void* y) = 0;
     virtual void set_g_lambda(double lambda, const void* lambda_vec) = 0;
+    virtual void set_g_elastic_net(double l1, double l2) = 0;
     virtual void begin(const bz_panoc_opts& o, const void* x0_host) = 0;
     virtual void step() = 0;
     virtual void steps(int64_t k) = 0;

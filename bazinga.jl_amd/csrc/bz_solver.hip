@@ -264,6 +264,13 @@ template <class T> class Solver final : public SolverBase {
             while (grp_KP_ < grp_K_) grp_KP_ *= 2;
             grp_ng_ = n / grp_K_;
         }
+        enet_g = d.g_kind == BZ_G_ELASTIC_NET;
+        if (enet_g) {
+            // (an element-wise run-time kind outside the one-pass family table: it goes wherever NormL1 with a vector lambda goes)
+            if (d.g_lambda_vec)
+                throw Error(BZ_ERR_ARG, "ElasticNet: g_lambda_vec must be null (the per-element penalty factors travel in g_weights)");
+            enet_check(d.g_lambda, d.g_l2);
+        }
         sparse_f = d.f_kind == BZ_F_SPARSE_QUADRATIC;
         if (sparse_f) {
             if (slack) throw Error(BZ_ERR_UNSUPPORTED, "SparseQuadratic: the slack (ALS) form is not lowered with a sparse quadratic f");
@@ -376,7 +383,7 @@ template <class T> class Solver final : public SolverBase {
             if (ctx->nranks > 1 && !ctx->p2p_on)
                 throw Error(BZ_ERR_UNSUPPORTED, "a sharded Stencil5pt needs the p2p mailboxes (bz_ctx_p2p_connect)");
         }
-        if ((d.g_kind < BZ_G_ZERO || d.g_kind > BZ_G_NORM_LP_BOX) && !group_g && !generic_)
+        if ((d.g_kind < BZ_G_ZERO || d.g_kind > BZ_G_NORM_LP_BOX) && !group_g && !enet_g && !generic_)
             throw Error(BZ_ERR_ARG, "unknown g kind");
         if ((d.D_kind < BZ_D_ZERO || d.D_kind > BZ_D_XOR_PAIRS) && !generic_) throw Error(BZ_ERR_ARG, "unknown D kind");
         if (d.D_kind >= BZ_D_VC_PAIRS && d.D_kind <= BZ_D_XOR_PAIRS) {
@@ -527,6 +534,16 @@ template <class T> class Solver final : public SolverBase {
             upload(gu_, d.g_u, nx); P.g_u = gu_.p;
         }
         P.g_lo = (T)d.g_lo; P.g_hi = (T)d.g_hi;
+        if (enet_g) {
+            // (gamma * 1 is gamma: the kernels' gl is the arm's t; l1 and l2 travel where a box's bounds do, see ElemParams::g_weights)
+            P.g_lambda = T(1); P.g_lo = (T)d.g_lambda; P.g_hi = (T)d.g_l2;
+            if (d.g_weights) {
+                // (the x half in the slack form: the s half has no g)
+                std::vector<T> w;
+                read_elem_vec(d.g_weights, w, "ElasticNet", "g_weights");
+                upload(glam_, w.data(), nx); P.g_weights = glam_.p;      // (shares its slot with g_u: read through P.weights())
+            }
+        }
         if (d.g_kind == BZ_G_IND_BOX) {
             if (d.g_lo_vec) { upload(glo_, d.g_lo_vec, nx); P.g_lo_vec = glo_.p; }
             if (d.g_hi_vec) { upload(ghi_, d.g_hi_vec, nx); P.g_hi_vec = ghi_.p; }
@@ -603,6 +620,23 @@ template <class T> class Solver final : public SolverBase {
         if (lam_vec) copy_in(glam_.p, h.data(), nx);
         else { P.g_lambda = (T)lam; desc.g_lambda = lam; }
     }
+    // l1 and l2 of a live ElasticNet problem, between solves; the weights stay.  As set_g_lambda: P is all that holds them.
+    void set_g_elastic_net(double l1, double l2) override {
+        if (!enet_g) throw Error(BZ_ERR_ARG, "bz_problem_set_g_elastic_net: g must be ElasticNet");
+        enet_check(l1, l2);
+        gate_abort();
+        BZ_HIP(hipStreamSynchronize(ctx->stream));
+        P.g_lo = (T)l1; P.g_hi = (T)l2;
+        desc.g_lambda = l1; desc.g_l2 = l2;
+    }
+    // ElasticNet's two numbers: finite and >= 0, in the problem's type too (an fp32 problem rounds them)
+    static void enet_check(double l1, double l2) {
+        const double big = (double)std::numeric_limits<T>::max();
+        if (!(std::isfinite(l1) && l1 >= 0 && l1 <= big))
+            throw Error(BZ_ERR_ARG, "ElasticNet: g_lambda (l1) must be finite and >= 0 in the problem's type");
+        if (!(std::isfinite(l2) && l2 >= 0 && l2 <= big))
+            throw Error(BZ_ERR_ARG, "ElasticNet: g_l2 (l2) must be finite and >= 0 in the problem's type");
+    }
     const char* gname() const { return ragged_g ? "GroupLasso" : "NormL21"; }
     // ... of NormL21 and GroupLasso: a number for a number, a vector (one entry per group) for a vector; a refused call changes nothing
     void set_group_lambda(double lam, const void* lam_vec) {
@@ -627,12 +661,14 @@ template <class T> class Solver final : public SolverBase {
                 throw Error(BZ_ERR_ARG, std::string(gname()) + ": every entry of the vector lambda must be finite and >= 0 (entry " + std::to_string(i) + ")");
     }
     // NormL1's per-element lambda on a host copy: every entry finite and >= 0 (zeros are the unpenalised coefficients)
-    void read_lambda_vec(const void* src, std::vector<T>& h) {
+    void read_lambda_vec(const void* src, std::vector<T>& h) { read_elem_vec(src, h, "NormL1", "the vector lambda"); }
+    // a per-element vector of g (NormL1's lambda, ElasticNet's penalty factors) on a host copy: nx entries, finite and >= 0
+    void read_elem_vec(const void* src, std::vector<T>& h, const char* kind, const char* field) {
         h.resize((size_t)nx);
         BZ_HIP(hipMemcpy(h.data(), src, h.size() * sizeof(T), hipMemcpyDefault));
         for (int64_t i = 0; i < nx; ++i)
             if (!(std::isfinite((double)h[i]) && h[i] >= T(0)))
-                throw Error(BZ_ERR_ARG, "NormL1: every entry of the vector lambda must be finite and >= 0 (entry " + std::to_string(i) + ")");
+                throw Error(BZ_ERR_ARG, std::string(kind) + ": every entry of " + field + " must be finite and >= 0 (entry " + std::to_string(i) + ")");
     }
 
     void set_multipliers(const void* mu, const void* y) override {
@@ -1013,6 +1049,7 @@ template <class T> class Solver final : public SolverBase {
     bool group_g = false;                    // g = NormL21 or GroupLasso: kept on the kernel chain wherever lp_g is; k_fbstep_group / k_fbstep_ragged its one kernel
     int grp_K_ = 0, grp_KP_ = 0;             // ... its group size K and the power of two >= K
     int64_t grp_ng_ = 0;                     // ... the number of groups (of both group kinds)
+    bool enet_g = false;                     // g = ElasticNet: an element-wise run-time kind, no one-pass family, no fast slack form
     bool ragged_g = false;                   // g = GroupLasso (a group pointer; group_g holds too): k_fbstep_ragged its one kernel
     std::vector<int64_t> grp_ptr_h_;         // ... ptr[ng + 1] on the host, validated
     DBuf<int64_t> gptr_;                     // ... and on the device
@@ -1441,7 +1478,7 @@ template <class T> class Solver final : public SolverBase {
         if (need_f && P.f_kind == BZ_F_DIAG_QUADRATIC) k += 2;
         if (need_al) k += 2 - (P.uni >= 1 ? 1 : 0) - (P.uni >= 2 ? 1 : 0) + (P.D_lo_vec ? 1 : 0) + (P.D_hi_vec ? 1 : 0);
         if (need_g) k += (P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX || P.g_kind == BZ_G_NORM_LP_BOX) ? 1 : 0) +
-                         (P.lambda_vec() ? 1 : 0) + (P.g_lo_vec ? 1 : 0) + (P.g_hi_vec ? 1 : 0);
+                         (P.scale_vec() ? 1 : 0) + (P.g_lo_vec ? 1 : 0) + (P.g_hi_vec ? 1 : 0);
         return k;
     }
     void account(int cat, ProfRec* r) {
@@ -2033,6 +2070,7 @@ template <class T> class Solver final : public SolverBase {
             // (a vector lambda, or l1 > 0: the kernel summed the finished terms)
             if (P.group_lambda_vec() || desc.g_l1 > 0) return T(gsum);
             return P.g_lambda * T(gsum);
+        case BZ_G_ELASTIC_NET: return T(gsum);   // (the kernels summed the finished terms, weighted or not)
         case BZ_G_CALLBACK: return T(gsum);      // the callback returned g(z) itself
         default: return T(0);
         }
@@ -2686,6 +2724,7 @@ template <class T> class Solver final : public SolverBase {
     int fused_family() const {
         if (desc.c_kind != BZ_C_IDENTITY || slack || ny != n || lp_g || group_g) return -1;
         if (P.lambda_vec()) return -1;      // (a per-element lambda: no family for it, the stored-pair forms)
+        if (enet_g) return -1;              // (the elastic net, with weights or without: the same)
         int fk, gk, dk;
         switch (desc.f_kind) {
         case BZ_F_ZERO: fk = FAM_F_ZERO; break;
@@ -3328,7 +3367,7 @@ template <class T> class Solver final : public SolverBase {
         // pipelined like the headline kernel, 256 VGPRs + spill AGPRs: one workgroup per CU there too)
         const bool slack_fast = slack && xr == 2 && env_.slackfast && m_now == CM && desc.f_kind == BZ_F_DIAG_QUADRATIC &&
                                 pstreams(false, true, true) == 2 - std::min(2, (int)P.uni) &&
-                                !(P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX)) && !P.lambda_vec();
+                                !(P.g_u && (P.g_kind == BZ_G_NORM_L1_BOX || P.g_kind == BZ_G_NORM_L0_BOX)) && !P.lambda_vec() && !enet_g;
         // ... with the kinds fixed too (g = NormL1, D = Box: the ALS form of cfg 2), one pack of loads ahead
         const bool slack_hk = slack_fast && env_.slackkind && P.g_kind == BZ_G_NORM_L1 && P.D_kind == BZ_D_BOX;
         if (xr == 2 && env_.gfc <= 0 && (!slack || slack_hk)) gfc = std::min(grid, std::max(1, num_cus));

@@ -173,6 +173,11 @@ class Problem:
             v = self._in(lam, self._nlam)
             self._call(L.load().bz_problem_set_g_lambda(self._h, 0.0, v.ctypes.data))
 
+    def set_g_elastic_net(self, l1, l2):
+        """l1 and l2 of g = ElasticNet between solves, without a new problem (a glmnet path moves lambda, hence both); the
+        weights stay as created."""
+        self._call(L.load().bz_problem_set_g_elastic_net(self._h, float(l1), float(l2)))
+
     def panoc_solve(self, opts: L.PanocOpts, x0):
         x0 = self._in(x0, self.n)
         out = np.empty(self.n, self.dtype)

@@ -590,6 +590,60 @@ class NormL1(ProximableFunction):
         return np.sum(lam * np.abs(z))
 
 
+class ElasticNet(ProximableFunction):
+    """ProximalOperators.ElasticNet(mu, lambda) with penalty factors: g(x) = sum_i w_i (l1 |x_i| + l2/2 x_i^2), l1 and l2
+    finite and >= 0, `weights` a 1-D array of finite entries >= 0 or None (every w_i = 1; a zero leaves its element wholly
+    unpenalised: an intercept).  glmnet's penalty lambda sum pf_j (alpha |b_j| + (1 - alpha)/2 b_j^2) is
+    ElasticNet.glmnet(lam, alpha, penalty_factor).  `prox` restates the device's arm (include/bazinga_hip.h,
+    BZ_G_ELASTIC_NET) operation for operation in the type of x, so it gives the device's bits."""
+
+    def __init__(self, l1=1.0, l2=1.0, weights=None):
+        for name, v in (("l1", l1), ("l2", l2)):
+            if np.ndim(v) != 0 or not (np.isfinite(v) and v >= 0):
+                raise ValueError(f"parameter {name} must be a finite, nonnegative number")
+        self.l1, self.l2 = float(l1), float(l2)
+        if weights is not None:
+            weights = np.array(weights, dtype=np.float64)
+            if weights.ndim != 1:
+                raise ValueError("weights must be None or a 1-D array")
+            if not np.all(np.isfinite(weights) & (weights >= 0)):
+                raise ValueError("weights must have finite, nonnegative entries")
+        self.weights = weights
+
+    @classmethod
+    def glmnet(cls, lam, alpha, penalty_factor=None):
+        """glmnet's parametrisation: l1 = lam * alpha, l2 = lam * (1 - alpha), weights = penalty.factor"""
+        if np.ndim(alpha) != 0 or not (0 <= alpha <= 1):
+            raise ValueError("alpha must be a number in [0, 1]")
+        return cls(lam * alpha, lam * (1 - alpha), penalty_factor)
+
+    def _check(self, dtype):
+        """the C side's rule for the problem's type: neither number above its largest"""
+        if max(self.l1, self.l2) > float(np.finfo(dtype).max):
+            raise ValueError(f"l1 and l2 must be finite in {np.dtype(dtype)}")
+
+    def __call__(self, x):
+        term = self.l1 * np.abs(x) + (0.5 * self.l2) * (x * x)
+        return np.sum(term if self.weights is None else self.weights * term)
+
+    def prox(self, z, x, gamma):
+        T = x.dtype.type
+        l1, l2 = T(self.l1), T(self.l2)
+        w = None if self.weights is None else np.asarray(self.weights, dtype=x.dtype)
+        with np.errstate(all="ignore"):
+            t = T(gamma) if w is None else T(gamma) * w
+            a = t * l1
+            d = T(1) + t * l2
+            # y - min(max(y, -a), a): NormL1's expression (its `where` form has the same bits for every y and a, the
+            # signed zeros, infinities and NaN included)
+            s = x + np.where(x <= -a, a, np.where(x >= a, -a, -x))
+            z[...] = s / d
+            term = l1 * np.abs(z) + (T(0.5) * l2) * (z * z)
+            if w is not None:
+                term = w * term
+            return np.sum(term)
+
+
 class NormL21(ProximableFunction):
     """The group Lasso: g(x) = sum_j lambda_j ||x[jK : (j+1)K]||_2 over the n / K contiguous groups of K = `group`
     elements, 1 <= K <= 64 (no reference class; with SparseMultinomial's layout and K = n_classes a group is a feature's
@@ -1054,7 +1108,7 @@ _SPARSE_F = {
 }
 
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, *_SPARSE_F, Stencil5ptQuadratic))
-_LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, NormL21, GroupLasso, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
+_LOWERED_G = lambda g: isinstance(g, (Zero, IndFree, NormL1, ElasticNet, NormL21, GroupLasso, NormL1Nonneg, NormL1Box, NormL0Box, NormLpPowerNonneg,
                                       NormLpPowerBox, IndBox))
 _LOWERED_C = lambda c: isinstance(c, (IdentityFunction, DenseAffine, SparseAffine))
 _LOWERED_D = lambda D: isinstance(D, (ZeroSet, FreeSet, PairwiseSet)) or \
@@ -1231,6 +1285,11 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
     elif isinstance(g, NormL1):
         d.g_kind = L.BZ_G_NORM_L1
         num_or_vec("g_lambda", g.lam, n, "λ")
+    elif isinstance(g, ElasticNet):
+        g._check(dtype)
+        d.g_kind, d.g_lambda, d.g_l2 = L.BZ_G_ELASTIC_NET, g.l1, g.l2
+        if g.weights is not None:
+            d.g_weights = ptr(_vec(g.weights, dtype, n, "weights"))
     elif isinstance(g, NormL21):
         # what the library refuses with this kind, refused here before any device call
         if slack:

@@ -158,6 +158,21 @@ extern "C" {
                                     The group's term of g(z) is lambda_j * (scal * nrm), and with l1 > 0 also (l1 * scal) * the
                                     sum of |u_k| in the same accumulator order.  Every f, c and D of the kernel chain, slack = 0,
                                     one rank; refused (BZ_ERR_UNSUPPORTED): slack = 1, more than one rank, callbacks mixed in.  */
+#define BZ_G_ELASTIC_NET     11  /* The elastic net, ProximalOperators.ElasticNet(mu, lambda) with penalty factors (glmnet's penalty:
+                                    l1 = lambda alpha, l2 = lambda (1 - alpha), w = penalty.factor):
+                                    g(x) = sum_i w_i (l1 |x_i| + (l2 / 2) x_i^2), l1 = g_lambda and l2 = g_l2 finite and >= 0,
+                                    w = g_weights[n] finite and >= 0 or NULL (every w_i = 1; a zero leaves its element wholly
+                                    unpenalised: an intercept).  g_lambda_vec must be NULL.  The prox of one element, y the
+                                    argument, every operation in the problem's type and in this order (this list is the definition;
+                                    bz.ElasticNet restates it):
+                                        t = gamma (no weights)  |  t = gamma * w_i (weights)
+                                        a = t * l1
+                                        d = 1 + t * l2
+                                        s = y - min(max(y, -a), a)      (NORM_L1's expression, on a)
+                                        z = s / d                       (a division)
+                                        term = l1 * |z| + (0.5 * l2) * (z * z), times w_i with weights
+                                    g(z) is the sum of the terms.  Every f, c and D of the kernel chain, the slack form too;
+                                    no one-pass family (the stored-pair forms); callbacks mixed in are refused.                 */
 /* c: constraint map.  eval!(cx,c,x), jtprod!(jtv,c,x,v)                             */
 #define BZ_C_IDENTITY        0   /* test/definitions/identityFunction.jl:3-13         */
 #define BZ_C_DENSE_AFFINE    1   /* A x - b, demo/basispursuit.jl:38-49               */
@@ -288,6 +303,10 @@ typedef struct {
     int64_t     g_ngroups;         /* GROUP_LASSO alone: the number of groups, 1 .. n; the other kinds ignore it              */
     double      g_l1;              /* GROUP_LASSO alone: l1 >= 0, the weight of ||x||_1 (0: the pure group penalty); the other kinds ignore it */
     double      g_lo, g_hi;        /* IND_BOX scalar bounds                           */
+    double      g_l2;              /* ELASTIC_NET alone: l2 >= 0, finite, the ridge weight (l1 travels in g_lambda); the other kinds
+                                      ignore it, so a zeroed descriptor changes nothing                                        */
+    const void* g_weights;         /* ELASTIC_NET alone: w[n] >= 0 in the problem's type (finite; a zero: an unpenalised element),
+                                      or NULL: every w_i = 1.  In the slack form n entries, the x half.  The other kinds ignore it */
     const void* g_lo_vec;          /* IND_BOX vector bounds (or NULL)                 */
     const void* g_hi_vec;
     const void* g_lambda_vec;      /* NORM_L1 alone: lambda[n] >= 0 (finite; zeros allowed: an unpenalised coefficient), g(x) =
@@ -328,7 +347,9 @@ typedef struct {
     const int32_t* c_sp_col;       /* col[nnz], 0-based, in [0, n)                    */
     const void*    c_sp_val;       /* val[nnz]                                        */
     int64_t        c_sp_nnz;
-} bz_problem_desc;
+} bz_problem_desc;   /* NOT binary-stable across versions of this header: new fields go into the block of the oracle they belong to (g_l2
+                        and g_weights behind g_hi), which moves every later field.  A caller is rebuilt against the header it links
+                        with; a zeroed descriptor selects nothing new.                                                          */
 
 int  bz_problem_create(bz_ctx* ctx, const bz_problem_desc* desc, bz_problem** out);
 void bz_problem_destroy(bz_problem* p);
@@ -460,6 +481,11 @@ int bz_problem_set_multipliers(bz_problem* p, const void* mu, const void* y);
  * device copy (lambda is ignored).  Number <-> vector would change the kernel forms the problem runs and stays a creation-time decision:
  * BZ_ERR_ARG, as for any other g kind.  Between bz_panoc_begin and bz_panoc_finish: BZ_ERR_STATE.                         */
 int bz_problem_set_g_lambda(bz_problem* p, double lambda, const void* lambda_vec);
+
+/* l1 and l2 of a live ELASTIC_NET problem, between solves (a glmnet path moves lambda, hence both); the weights stay as
+ * created.  Both finite and >= 0 (and finite in the problem's type), else BZ_ERR_ARG, as on any other g kind; between
+ * bz_panoc_begin and bz_panoc_finish: BZ_ERR_STATE.  A solve after the call is bit for bit that of a fresh problem.       */
+int bz_problem_set_g_elastic_net(bz_problem* p, double l1, double l2);
 
 /* One-shot subsolve.  x_out receives state.z.                                      */
 int bz_panoc_solve(bz_problem* p, const bz_panoc_opts* o, const void* x0,

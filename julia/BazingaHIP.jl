@@ -32,6 +32,7 @@ Base.@kwdef mutable struct ProblemDesc
     g_lambda::Float64 = 0; g_p::Float64 = 0; g_group::Int64 = 0; g_u::Ptr{Cvoid} = C_NULL
     g_group_ptr::Ptr{Cvoid} = C_NULL; g_ngroups::Int64 = 0; g_l1::Float64 = 0   # g = GroupLasso (BZ_G_GROUP_LASSO) alone
     g_lo::Float64 = 0; g_hi::Float64 = 0
+    g_l2::Float64 = 0; g_weights::Ptr{Cvoid} = C_NULL   # g = ElasticNet (BZ_G_ELASTIC_NET) alone
     g_lo_vec::Ptr{Cvoid} = C_NULL; g_hi_vec::Ptr{Cvoid} = C_NULL; g_lambda_vec::Ptr{Cvoid} = C_NULL
     c_A::Ptr{Cvoid} = C_NULL; c_b::Ptr{Cvoid} = C_NULL
     D_lo::Float64 = 0; D_hi::Float64 = 0; D_lo_vec::Ptr{Cvoid} = C_NULL; D_hi_vec::Ptr{Cvoid} = C_NULL
@@ -342,6 +343,35 @@ function ProximalOperators.prox!(z, g::GroupLasso, x, gamma)
     return gz
 end
 
+"""`ElasticNet(l1, l2)` / `ElasticNet(l1, l2, weights)`: the elastic net with penalty factors,
+g(x) = Σᵢ wᵢ (l1 |xᵢ| + l2/2 xᵢ²) (BZ_G_ELASTIC_NET; `ProximalOperators.ElasticNet(mu, lambda)` is the form without weights and
+lowers to the same kind).  l1 and l2 are finite numbers ≥ 0; `weights` is a vector in the problem's type with one finite entry
+≥ 0 per element (a zero leaves its element wholly unpenalised: an intercept), or `nothing`: every wᵢ = 1.  glmnet's penalty
+λ Σ pfⱼ (α |βⱼ| + (1 − α)/2 βⱼ²) is `ElasticNet(λ α, λ (1 − α), pf)`.  A weight vector must stay alive until bz_problem_create
+returns."""
+struct ElasticNet{W<:Union{Nothing,AbstractVector{<:Real}}} <: Bazinga.ProximableFunction
+    l1::Float64; l2::Float64; weights::W
+    function ElasticNet(l1::Real, l2::Real, weights::W = nothing) where {W<:Union{Nothing,AbstractVector{<:Real}}}
+        isfinite(l1) && l1 >= 0 || throw(ArgumentError("l1 must be finite and nonnegative"))
+        isfinite(l2) && l2 >= 0 || throw(ArgumentError("l2 must be finite and nonnegative"))
+        weights === nothing || all(v -> isfinite(v) && v >= 0, weights) || throw(ArgumentError("weights must be finite and nonnegative"))
+        new{W}(Float64(l1), Float64(l2), weights)
+    end
+end
+# the definition of include/bazinga_hip.h, operation for operation in the type of x (the host twin of prox_elem's arm)
+function ProximalOperators.prox!(z, g::ElasticNet, x, gamma)
+    T = eltype(x); l1 = T(g.l1); l2 = T(g.l2); h2 = T(0.5) * l2; gz = zero(T)
+    for i in eachindex(x)
+        t = g.weights === nothing ? T(gamma) : T(gamma) * T(g.weights[i])
+        a = t * l1; d = one(T) + t * l2; y = x[i]
+        s = y + (y <= -a ? a : (y >= a ? -a : -y))
+        z[i] = s / d
+        term = l1 * abs(z[i]) + h2 * (z[i] * z[i])
+        gz += g.weights === nothing ? term : T(g.weights[i]) * term
+    end
+    return gz
+end
+
 "`LBFGS(M; compact = nothing)`: how the operator is evaluated (bz_panoc_opts.lbfgs_compact) — `false` the two-loop recursion in the reference's order, `true` the compact representation, `nothing` (default) compact where the one-pass kernel applies"
 struct LBFGS
     memory::Int; compact::Union{Nothing,Bool}
@@ -403,6 +433,11 @@ lower_g!(d, g::NormL21{<:AbstractVector}) = (d.g_kind = 9; d.g_group = g.group; 
 # (the group Lasso over a group pointer: the pointer is the object's own; ptr[end] == n and the slack form are checked by bz_problem_create)
 lower_g!(d, g::GroupLasso{<:Real}) = (d.g_kind = 10; d.g_group_ptr = pointer(g.ptr); d.g_ngroups = length(g.ptr) - 1; d.g_l1 = g.l1; d.g_lambda = g.lambda)
 lower_g!(d, g::GroupLasso{<:AbstractVector}) = (d.g_kind = 10; d.g_group_ptr = pointer(g.ptr); d.g_ngroups = length(g.ptr) - 1; d.g_l1 = g.l1; d.g_lambda_vec = pointer(g.lambda))
+# the elastic net (BZ_G_ELASTIC_NET): ProximalOperators' type with numbers, or BazingaHIP.ElasticNet with optional penalty factors
+lower_g!(d, g::ProximalOperators.ElasticNet{<:Real,<:Real}) = (d.g_kind = 11; d.g_lambda = g.mu; d.g_l2 = g.lambda)
+lower_g!(d, g::ElasticNet{Nothing}) = (d.g_kind = 11; d.g_lambda = g.l1; d.g_l2 = g.l2)
+# (penalty factors: one per element, in the problem's type; the array must stay alive until bz_problem_create returns)
+lower_g!(d, g::ElasticNet{<:AbstractVector}) = (d.g_kind = 11; d.g_lambda = g.l1; d.g_l2 = g.l2; d.g_weights = pointer(g.weights))
 lower_g!(d, g::Bazinga.NormL1Box) = (d.g_kind = 3; d.g_lambda = g.lambda; d.g_u = pointer(g.u))
 lower_g!(d, g::ProximalOperators.IndBox{<:Real,<:Real}) = (d.g_kind = 4; d.g_lo = g.lb; d.g_hi = g.ub)
 lower_g!(d, g::Bazinga.NormL0Box) = (d.g_kind = 5; d.g_lambda = g.lambda; d.g_u = pointer(g.u))
@@ -530,6 +565,10 @@ set_g_lambda!(p::Problem, lambda::Real) = check(ccall((:bz_problem_set_g_lambda,
     (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), p.h, lambda, C_NULL))
 set_g_lambda!(p::Problem, lambda::AbstractVector) = GC.@preserve lambda check(ccall((:bz_problem_set_g_lambda, lib), Cint,
     (Ptr{Cvoid}, Cdouble, Ptr{Cvoid}), p.h, 0.0, pointer(lambda)))
+
+# l1 and l2 of g = ElasticNet between solves, on the live problem (a glmnet path moves λ, hence both); the weights stay
+set_g_elastic_net!(p::Problem, l1::Real, l2::Real) = check(ccall((:bz_problem_set_g_elastic_net, lib), Cint,
+    (Ptr{Cvoid}, Cdouble, Cdouble), p.h, l1, l2))
 
 # ---- the subsolver seam: drop-in for ProximalAlgorithms.PANOCplus -----------------------------
 struct PANOCplusHIP
