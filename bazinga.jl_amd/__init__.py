@@ -8,7 +8,7 @@ from ._lib import BazingaHipError
 from .device import Context, Problem, default_context, runtime_tuning, set_default_context, shard_bounds
 from .oracles import (CallbackError, ClosedSet, DenseAffine, DiagQuadratic, FreeSet, IdentityFunction, IndBox, IndFree, IndicatorSet,
                       LeastSquares, NormL0Box, NormLpPowerBox, NormLpPowerNonneg, Quadratic,
-                      ElasticNet, GroupLasso, NormL1, NormL1Box, NormL1Nonneg, NormL21, SparseAffine, SparseGLM, SparseLeastSquares, SparseLogistic, SparseMultinomial, SparseQuadratic, Stencil5ptQuadratic, UnsupportedOracle, Zero, ZeroSet,
+                      ElasticNet, GroupLasso, NormL1, NormL1Box, NormL1Nonneg, NormL21, SparseAffine, SparseGLM, SparseLeastSquares, SparseLogistic, SparseMultiGLM, SparseMultinomial, SparseQuadratic, Stencil5ptQuadratic, UnsupportedOracle, Zero, ZeroSet,
                       PairwiseSet, VanishingConstraintPairs, ComplementarityPairs, EitherOrPairs, XorPairs)
 from .solvers import (LBFGS, NoAcceleration, AndersonAcceleration, Broyden, AugLagFun, AugLagFunSlack, AugLagUpdate, NonsmoothCostFun, NonsmoothCostFunSlack,
                       PANOCplus, alps, als,

@@ -29,6 +29,7 @@ BZ_F_SPARSE_LEAST_SQUARES = 7
 BZ_F_SPARSE_LOGISTIC = 8
 BZ_F_SPARSE_GLM = 9
 BZ_F_SPARSE_MULTINOMIAL = 10
+BZ_F_SPARSE_MULTI_GLM = 11
 BZ_LOSS_LEAST_SQUARES, BZ_LOSS_LOGISTIC, BZ_LOSS_HUBER, BZ_LOSS_SQUARED_HINGE, BZ_LOSS_POISSON = 0, 1, 2, 3, 4
 # host-callback oracle protocol (include/bazinga_hip.h)
 F_GRADIENT_FN = C.CFUNCTYPE(C.c_double, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64)

@@ -192,6 +192,11 @@ template <class F> static void with_sparse_f_mode(int mode, F&& f) {
     case SP_GLM_MODE0 + BZ_LOSS_HUBER: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_HUBER>{}); break;
     case SP_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE>{}); break;
     case SP_GLM_MODE0 + BZ_LOSS_POISSON: f(std::integral_constant<int, SP_GLM_MODE0 + BZ_LOSS_POISSON>{}); break;
+    case SPMM_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES: f(std::integral_constant<int, SPMM_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES>{}); break;
+    case SPMM_GLM_MODE0 + BZ_LOSS_LOGISTIC: f(std::integral_constant<int, SPMM_GLM_MODE0 + BZ_LOSS_LOGISTIC>{}); break;
+    case SPMM_GLM_MODE0 + BZ_LOSS_HUBER: f(std::integral_constant<int, SPMM_GLM_MODE0 + BZ_LOSS_HUBER>{}); break;
+    case SPMM_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE: f(std::integral_constant<int, SPMM_GLM_MODE0 + BZ_LOSS_SQUARED_HINGE>{}); break;
+    case SPMM_GLM_MODE0 + BZ_LOSS_POISSON: f(std::integral_constant<int, SPMM_GLM_MODE0 + BZ_LOSS_POISSON>{}); break;
     default: f(std::integral_constant<int, SPMM_SOFTMAX>{}); break;
     }
 }
@@ -288,13 +293,15 @@ template <class T> class Solver final : public SolverBase {
         for (const SparseRowF& k : SPARSE_ROW_F)
             if (k.f_kind == d.f_kind) { spf_ = k; sparse_ls = true; }
         sparse_mn = d.f_kind == BZ_F_SPARSE_MULTINOMIAL;
+        sparse_kw = sparse_mn || d.f_kind == BZ_F_SPARSE_MULTI_GLM;
+        const bool glm_loss = d.f_kind == BZ_F_SPARSE_GLM || d.f_kind == BZ_F_SPARSE_MULTI_GLM;      // (a kind that reads f_loss and f_loss_delta)
         if (sparse_ls) {
             sparse_rowwise_check(d);
-            if (d.f_kind == BZ_F_SPARSE_GLM) {
+            if (glm_loss) {
                 if (d.f_loss < BZ_LOSS_LEAST_SQUARES || d.f_loss > BZ_LOSS_POISSON)
-                    throw Error(BZ_ERR_ARG, "SparseGLM: f_loss must be one of BZ_LOSS_* (0 .. 4)");
+                    throw Error(BZ_ERR_ARG, std::string(spf_.name) + ": f_loss must be one of BZ_LOSS_* (0 .. 4)");
                 if (d.f_loss == BZ_LOSS_HUBER && !(std::isfinite(d.f_loss_delta) && d.f_loss_delta > 0))
-                    throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0");
+                    throw Error(BZ_ERR_ARG, std::string(spf_.name) + ": the Huber loss needs f_loss_delta finite and > 0");
             }
             if (spf_.weighted && !(std::isfinite(d.f_scale) && d.f_scale > 0))
                 throw Error(BZ_ERR_ARG, std::string(spf_.name) + ": f_scale must be finite and > 0 (1 for the plain sum)");
@@ -304,7 +311,9 @@ template <class T> class Solver final : public SolverBase {
                 spf_.weighted = d.f_w != nullptr || d.f_scale != 1.0 || d.f_loss >= BZ_LOSS_HUBER;
                 spf_.mode = spf_.weighted ? SP_GLM_MODE0 + (int)d.f_loss : d.f_loss == BZ_LOSS_LOGISTIC ? SP_LOGIT_R : SP_LS_R;
             }
-            if (sparse_mn) {
+            // (the multi-response GLM f: always the weighted epilogue, the loss fixing the K-wide mode)
+            if (d.f_kind == BZ_F_SPARSE_MULTI_GLM) spf_.mode = SPMM_GLM_MODE0 + (int)d.f_loss;
+            if (sparse_kw) {
                 // (the three row launches are the K-wide kernels of bz_spmm.h; x is n / K rows of K)
                 mn_K_ = (int)d.f_classes;
                 mn_KP_ = 2;
@@ -462,12 +471,14 @@ template <class T> class Solver final : public SolverBase {
             // r^2, halved by fscale ; every other mode: the plain sum of the rows' losses)
             frows = d.f_rows;
             sparse_ls_create(d);
-            upload(fb_, d.f_b, frows);
-            FR_.alloc(sparse_mn ? frows * mn_K_ : frows);                   // (the multinomial f: R is m rows of K)
+            // (the multi-response GLM f: B is m rows of K ; both K-wide kinds: R is m rows of K)
+            upload(fb_, d.f_b, d.f_kind == BZ_F_SPARSE_MULTI_GLM ? frows * mn_K_ : frows);
+            FR_.alloc(sparse_kw ? frows * mn_K_ : frows);
             if (d.c_kind == BZ_C_SPARSE_AFFINE || !spls_fused_on()) DFX_.alloc(nx);
-            fscale = spf_.mode == SP_LS_R || spf_.mode == SP_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES ? T(0.5) : T(1);
+            fscale = spf_.mode == SP_LS_R || spf_.mode == SP_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES ||
+                             spf_.mode == SPMM_GLM_MODE0 + BZ_LOSS_LEAST_SQUARES ? T(0.5) : T(1);
             if (sparse_mn) mn_labels_check(d);
-            if (d.f_kind == BZ_F_SPARSE_GLM || sparse_mn) glm_weights_create(d);
+            if (d.f_kind == BZ_F_SPARSE_GLM || sparse_kw) glm_weights_create(d);
         }
         if (d.c_kind == BZ_C_DENSE_AFFINE) {
             A_.alloc((size_t)ny * nx);
@@ -2096,8 +2107,9 @@ template <class T> class Solver final : public SolverBase {
     };
     SpCsr spA_, spAt_, spQ_;               // (Q: the sparse quadratic f; symmetric, so no transpose)
     DBuf<int64_t> spQ_rowptr_;             // a cut Q: the row pointers as given (k_spmv_q_algrad walks rows, not virtual rows)
-    // the profile labels of the row launches by the epilogue's MODE (SPMM_SOFTMAX's behind the others), filled at creation
-    static constexpr int sp_label_at(int mode) { return mode == SPMM_SOFTMAX ? SP_NMODES : mode; }
+    // the profile labels of the row launches by the epilogue's MODE (the K-wide mode over A_f — SPMM_SOFTMAX or a K-wide GLM
+    // mode, one per problem — behind the others), filled at creation
+    static constexpr int sp_label_at(int mode) { return mode >= SPMM_SOFTMAX ? SP_NMODES : mode; }
     std::string sp_label_[SP_NMODES + 1];
     template <class V> static void sp_upload(DBuf<V>& dst, const std::vector<V>& src) {
         dst.alloc(src.size());
@@ -2205,7 +2217,7 @@ template <class T> class Solver final : public SolverBase {
         if (ctx->nranks > 1) throw Error(BZ_ERR_UNSUPPORTED, kind + ": the " + f + " is not sharded (one rank)");
         if (d.g_kind == BZ_G_CALLBACK || d.c_kind == BZ_C_CALLBACK || d.D_kind == BZ_D_CALLBACK)
             throw Error(BZ_ERR_UNSUPPORTED, kind + ": the " + f + " does not mix with host callbacks");
-        if (d.f_kind == BZ_F_SPARSE_MULTINOMIAL) {
+        if (d.f_kind == BZ_F_SPARSE_MULTINOMIAL || d.f_kind == BZ_F_SPARSE_MULTI_GLM) {
             if (d.f_classes < 2 || d.f_classes > 64)
                 throw Error(BZ_ERR_ARG, kind + ": f_classes = K must be in 2 .. 64");
             if (n % d.f_classes != 0)
@@ -2220,14 +2232,15 @@ template <class T> class Solver final : public SolverBase {
     // a row-wise sparse f: A_f validated on a host copy; A_f and A_f' in HBM with the segment and lane rules of A and A'
     void sparse_ls_create(const bz_problem_desc& d) {
         std::vector<int64_t> rp, tp; std::vector<int32_t> col, tcol; std::vector<T> val, tval;
-        // (the multinomial f: A_f is m x n_f, n_f = n / K, and the transpose is built over n_f columns)
-        const int64_t nf = sparse_mn ? nx / mn_K_ : nx;
-        sp_read(spf_.name, "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val, sparse_mn ? nf : -1);
+        // (the K-wide kinds: A_f is m x n_f, n_f = n / K, and the transpose is built over n_f columns)
+        const int64_t nf = sparse_kw ? nx / mn_K_ : nx;
+        sp_read(spf_.name, "m", frows, d.f_sp_rowptr, d.f_sp_col, d.f_sp_val, d.f_sp_nnz, rp, col, val, sparse_kw ? nf : -1);
         csr_transpose(frows, nf, rp, col, val, tp, tcol, tval);
         sp_build(spF_, frows, nf, rp, col, val);
         sp_build(spFt_, nf, frows, tp, tcol, tval);
         std::string lead, lead_t;              // what the kind puts in front of L and SEG in its labels
-        if (sparse_mn) {
+        static const char* const loss_names[] = {"least_squares", "logistic", "huber", "squared_hinge", "poisson"};
+        if (sparse_kw) {
             for (SpCsr* m : {&spF_, &spFt_}) {
                 m->kw = mn_K_;
                 m->L = spmm_lanes(m->nnz, m->nv, mn_KP_);
@@ -2235,11 +2248,12 @@ template <class T> class Solver final : public SolverBase {
                 if (m->ncut) m->part.alloc(m->part.n * (size_t)mn_K_);      // (a segment of a cut row leaves K sums)
             }
             lead = lead_t = "K=" + std::to_string(mn_K_) + ",";
+            if (spmm_glm_mode(spf_.mode))
+                lead = std::string("LOSS=") + loss_names[spf_.mode - SPMM_GLM_MODE0] + ",W=" + (desc.f_w ? "1" : "0") + "," + lead;
         } else if (spf_.mode >= SP_GLM_MODE0) {
-            static const char* const names[] = {"least_squares", "logistic", "huber", "squared_hinge", "poisson"};
-            lead = std::string("LOSS=") + names[spf_.mode - SP_GLM_MODE0] + ",W=" + (desc.f_w ? "1" : "0") + ",";
+            lead = std::string("LOSS=") + loss_names[spf_.mode - SP_GLM_MODE0] + ",W=" + (desc.f_w ? "1" : "0") + ",";
         }
-        auto kernel = [&](int mode) { return sparse_mn ? spmm_kernel_name(mode) : sp_kernel_name(mode); };
+        auto kernel = [&](int mode) { return sparse_kw ? spmm_kernel_name(mode) : sp_kernel_name(mode); };
         sp_label_[sp_label_at(spf_.mode)] = sp_form(kernel(spf_.mode), spF_, lead);
         for (int mode : {SP_LS_T_ALGRAD, SP_T}) sp_label_[mode] = sp_form(kernel(mode), spFt_, lead_t);
     }
@@ -2252,8 +2266,9 @@ template <class T> class Solver final : public SolverBase {
         // (what the kernel multiplies by is the ROUNDED number: an fp32 problem can overflow where the double was finite)
         if (!std::isfinite((double)glm_w_uniform_))
             throw Error(BZ_ERR_ARG, what + ": f_scale must be finite and > 0 in the problem's type");
-        if (d.f_kind == BZ_F_SPARSE_GLM && d.f_loss == BZ_LOSS_HUBER && !(std::isfinite((double)glm_delta_) && glm_delta_ > T(0)))
-            throw Error(BZ_ERR_ARG, "SparseGLM: the Huber loss needs f_loss_delta finite and > 0 in the problem's type");
+        if ((d.f_kind == BZ_F_SPARSE_GLM || d.f_kind == BZ_F_SPARSE_MULTI_GLM) && d.f_loss == BZ_LOSS_HUBER &&
+            !(std::isfinite((double)glm_delta_) && glm_delta_ > T(0)))
+            throw Error(BZ_ERR_ARG, what + ": the Huber loss needs f_loss_delta finite and > 0 in the problem's type");
         if (!d.f_w) return;
         std::vector<T> w((size_t)frows);
         BZ_HIP(hipMemcpy(w.data(), d.f_w, w.size() * sizeof(T), hipMemcpyDefault));
@@ -2329,7 +2344,7 @@ template <class T> class Solver final : public SolverBase {
         pending_bytes_ += (double)m.part.n * 8 + (double)m.ncut * 8;
         launch(C_MISC, kernel, pl.gfold, (const double*)m.part.p, (const int32_t*)m.crow.p, (const int32_t*)m.cptr.p, m.ncut, tail...);
     }
-    // one pass of the K-wide row kernel (spmm_kernel: SPMM_SOFTMAX over A_f, SP_LS_T_ALGRAD and SP_T over A_f') and, for a cut
+    // one pass of the K-wide row kernel (spmm_kernel: SPMM_SOFTMAX or a K-wide GLM mode over A_f, SP_LS_T_ALGRAD and SP_T over A_f') and, for a cut
     // matrix, the fold of its cut rows; returns the number of block partials left in `slot`.  vec_bytes: the K-wide per-row vectors.
     template <int MODE> int spmm_pass(SpCsr& m, const T* gathered, const SpEpi<T>& E, int slot, double vec_bytes) {
         const SpPlan pl = sp_plan(m, vec_bytes);
@@ -2426,15 +2441,17 @@ template <class T> class Solver final : public SolverBase {
     // ---- a row-wise sparse f (SparseRowF)
     // rows of A_f: r_i = w_i l'(b_i, a_i'x) -> r_out (null: not kept) and the partials of the rows' losses -> slot, in the kind's
     // mode (least squares: r = A_f x - b and sum r^2 ; the multinomial f: R = w (softmax(A_f X) - onehot(b)), m rows of K).
-    // Per row: b (and r, the multinomial f's K values); a weight vector is one more stream.
+    // Per row: b (the multi-response GLM f: K values) and r if kept (the K-wide kinds: K values); a weight vector is one more
+    // stream.
     int spls_residual(const T* x, T* r_out, int slot) {
         SpEpi<T> E{fb_.p, nullptr, r_out, nullptr, P, nullptr};
         if (spf_.weighted) { E.w = glm_w_.p; E.w_uniform = glm_w_uniform_; E.delta = glm_delta_; }
-        const double vecs = (1 + (r_out ? (sparse_mn ? mn_K_ : 1) : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T);
+        const int kb = spmm_glm_mode(spf_.mode) ? mn_K_ : 1, kr = sparse_kw ? mn_K_ : 1;
+        const double vecs = (kb + (r_out ? kr : 0) + (E.w ? 1 : 0)) * (double)frows * sizeof(T);
         int nparts = 0;
         with_sparse_f_mode(spf_.mode, [&](auto mode_) {
             constexpr int MODE = decltype(mode_)::value;
-            if constexpr (MODE == SPMM_SOFTMAX) nparts = spmm_pass<MODE>(spF_, x, E, slot, vecs);
+            if constexpr (MODE >= SPMM_SOFTMAX) nparts = spmm_pass<MODE>(spF_, x, E, slot, vecs);
             else nparts = sp_pass<MODE>(spF_, x, E, slot, vecs);
         });
         return nparts;
@@ -2444,12 +2461,12 @@ template <class T> class Solver final : public SolverBase {
     int spls_t_algrad(const T* x, T* grad, int slot) {
         SpEpi<T> E{nullptr, nullptr, grad, x, P, nullptr};
         const double vecs = (1 + (grad ? 1 : 0) + pstreams(false, true, false)) * (double)n * sizeof(T);
-        return sparse_mn ? spmm_pass<SP_LS_T_ALGRAD>(spFt_, FR_.p, E, slot, vecs) : sp_pass<SP_LS_T_ALGRAD>(spFt_, FR_.p, E, slot, vecs);
+        return sparse_kw ? spmm_pass<SP_LS_T_ALGRAD>(spFt_, FR_.p, E, slot, vecs) : sp_pass<SP_LS_T_ALGRAD>(spFt_, FR_.p, E, slot, vecs);
     }
     // rows of A_f': A_f' r -> DFX_ (r in FR_)
     void spls_product() {
         SpEpi<T> E{nullptr, nullptr, DFX_.p, nullptr, P, nullptr};
-        if (sparse_mn) spmm_pass<SP_T>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
+        if (sparse_kw) spmm_pass<SP_T>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
         else sp_pass<SP_T>(spFt_, FR_.p, E, (int)SL_SCRATCH, (double)n * sizeof(T));
     }
     // (pairwise D: the projection of element j needs its partner, which a row's first lane does not have)
@@ -3930,12 +3947,12 @@ template <class T> class Solver final : public SolverBase {
     }
 
     // ---- a row-wise sparse f (kept behind every older member: their layout is the parent's).  SparseLeastSquares,
-    // SparseLogistic, SparseGLM and SparseMultinomial are one path, `sparse_ls`: a pass over A_f that leaves r and the rows'
+    // SparseLogistic, SparseGLM, SparseMultinomial and SparseMultiGLM are one path, `sparse_ls`: a pass over A_f that leaves r and the rows'
     // losses, then the passes over A_f' on r.  What a kind differs in is one row, copied to spf_ at creation:
     struct SparseRowF {
         int f_kind;
         const char *name, *noun, *b;       // in the messages: the kind, "a sparse <noun> f" and what the kind calls its vector
-        int mode;                          // the epilogue of the pass over A_f (SPMM_SOFTMAX: the K-wide kernels of bz_spmm.h)
+        int mode;                          // the epilogue of the pass over A_f (from SPMM_SOFTMAX on: the K-wide kernels of bz_spmm.h)
         bool weighted;                     // the epilogue takes w, w_uniform and delta (one more stream with a weight vector)
     };
     static constexpr SparseRowF SPARSE_ROW_F[] = {
@@ -3943,13 +3960,15 @@ template <class T> class Solver final : public SolverBase {
         {BZ_F_SPARSE_LOGISTIC, "SparseLogistic", "logistic", "the labels b[m]", SP_LOGIT_R, false},
         {BZ_F_SPARSE_GLM, "SparseGLM", "GLM", "b[m]", SP_GLM_MODE0, true},       // (mode and weighted: from f_loss, f_w and f_scale)
         {BZ_F_SPARSE_MULTINOMIAL, "SparseMultinomial", "multinomial", "the labels b[m]", SPMM_SOFTMAX, true},
+        {BZ_F_SPARSE_MULTI_GLM, "SparseMultiGLM", "multi-response GLM", "B[m][K]", SPMM_GLM_MODE0, true},      // (mode: from f_loss)
     };
     SparseRowF spf_ = SPARSE_ROW_F[0];
-    bool sparse_ls = false, sparse_mn = false;     // (sparse_mn: spf_.mode == SPMM_SOFTMAX)
+    bool sparse_ls = false, sparse_mn = false;     // (sparse_mn: spf_.mode == SPMM_SOFTMAX, the softmax and its label check)
+    bool sparse_kw = false;                // the K-wide kernels of bz_spmm.h: the multinomial and the multi-response GLM f
     SpCsr spF_, spFt_;                     // A_f (m x n) and A_f' (n x m)
     DBuf<T> glm_w_;                        // [m] scale * w, or empty: glm_w_uniform_ = scale for every row
     T glm_w_uniform_ = T(1), glm_delta_ = T(0);
-    int mn_K_ = 0, mn_KP_ = 0;             // the multinomial f: the classes, and the power of two >= K
+    int mn_K_ = 0, mn_KP_ = 0;             // the K-wide kinds: the classes / responses, and the power of two >= K
 };
 
 // one-pass kernel of an oracle family: the instantiations live in bz_families_dk*.hip (one file per D class, so that

@@ -1,10 +1,14 @@
 // bz_spmm.h — the K-wide CSR row kernels of the sparse multinomial (softmax) f (BZ_F_SPARSE_MULTINOMIAL):
-//   f(X) = sum_i w_i (logsumexp_k(t_ik) - t_{i,b_i}),  T = A_f X,  X n_f x K row-major (class fastest: x[j * K + k]).
+//   f(X) = sum_i w_i (logsumexp_k(t_ik) - t_{i,b_i}),  T = A_f X,  X n_f x K row-major (class fastest: x[j * K + k]),
+// and of the sparse multi-response GLM f (BZ_F_SPARSE_MULTI_GLM), the same passes with K independent row losses as the epilogue:
+//   f(X) = sum_i w_i sum_k l(b_ik, t_ik),  B m x K row-major  (k_spmm_glm_r<LOSS> in k_spmm_softmax_r's place).
 //
 // The passes are those of the sparse least-squares f (bz_spmv.h) with K values behind every gathered index:
 //   k_spmm_softmax_r  rows of A_f :  t_ik = sum_j a_ij x_jk, and on the K sums of a row the softmax: r_ik = w_i (p_ik - [k = b_i])
 //                     -> R[i * K + k] (if kept) and the row's loss w_i ((mx - t_{i,b_i}) + log S)
-//   k_spmm_t_algrad   rows of A_f', c = Identity:  (A_f' R)_jk, and on element j * K + k what k_algrad_elem does in its mode 1
+//   k_spmm_glm_r<LOSS>  rows of A_f, the multi-response GLM f:  the same sums, and on each of them by itself the row loss of
+//                     bz_spmv.h's k_spmv_glm_r<LOSS>: r_ik = w_i l'(b_ik, t_ik) -> R[i * K + k] (if kept) and the term w_i l(b_ik, t_ik)
+//   k_spmm_t_algrad  rows of A_f', c = Identity:  (A_f' R)_jk, and on element j * K + k what k_algrad_elem does in its mode 1
 //                     (sp_epilogue's SP_LS_T_ALGRAD on every class lane): the whole AL gradient in two launches, grad f never in HBM
 //   k_spmm_t          rows of A_f':  A_f' R -> DFX (SP_T) for the forms that finish element-wise or in k_spmv_t_finish
 //
@@ -21,7 +25,7 @@
 // Cut rows (sp_build's segments).  A segment leaves its K sums in `part` (K times the scalar kernels' side buffer:
 // part[slot * K + k]); k_spmm_fold, one wave per cut row with the same class-fastest lane map (64 / KP lanes per class), adds a
 // row's segment sums per class in a fixed order (lane l the segments l, l + 64 / KP, ..., then the xor tree) and runs the row's
-// epilogue — for A_f the softmax across the K classes.
+// epilogue — for A_f the softmax across the K classes, or the multi-response GLM f's loss arm on each response lane.
 //
 // Included by bz_solver.hip alone, as bz_spmv.h is.
 #pragma once
@@ -32,9 +36,12 @@ namespace bz {
 __device__ __forceinline__ float sp_log(float v) { return logf(v); }
 __device__ __forceinline__ double sp_log(double v) { return log(v); }
 
-// what a row's K sums go into: SPMM_SOFTMAX (rows of A_f), or sp_epilogue's SP_LS_T_ALGRAD / SP_T per element j * K + k (rows
-// of A_f')
+// what a row's K sums go into: SPMM_SOFTMAX or SPMM_GLM_MODE0 + BZ_LOSS_* (rows of A_f), or sp_epilogue's SP_LS_T_ALGRAD / SP_T
+// per element j * K + k (rows of A_f')
 constexpr int SPMM_SOFTMAX = 100;
+constexpr int SPMM_GLM_MODE0 = 101;  // the multi-response GLM f: K independent row losses, SPMM_GLM_MODE0 + BZ_LOSS_* (101 least
+                                     // squares .. 105 Poisson), each sp_epilogue's loss arm on element i * K + k with row i's weight
+constexpr bool spmm_glm_mode(int MODE) { return MODE >= SPMM_GLM_MODE0 && MODE <= SPMM_GLM_MODE0 + BZ_LOSS_POISSON; }
 
 // the entries [s, e) of one row for class kc, this lane being entry lane l of the row's L: spmv_row with K values behind
 // every column index.  Every lane of the row's group returns its class's folded sum.
@@ -75,6 +82,10 @@ __device__ __forceinline__ double spmm_row(const SpMat<T>& M, const T* __restric
 //   copy of t_{K-1} cannot change the max; its e is dropped from S).  The max is an ordered compare, which drops a NaN — the
 //   lanes may then disagree on mx — but the NaN lane's own e = exp(NaN - .) is NaN and the sum gives it to every lane: p, r and
 //   the loss of the whole row are NaN.  The lane of class b_i adds the row's loss.
+//   SPMM_GLM_MODE0 + LOSS: the K sums are K responses of their own.  The lead lane of response k < K runs sp_epilogue's loss arm
+//   (its weighted mode SP_GLM_MODE0 + LOSS: the same operations in the same order, NaN kept by the ordered compares) on element
+//   r * K + k of b and out, with the ROW's weight w[r]: out[r * K + k] = w l' (if kept), and w l goes to its acc[0].  Nothing is
+//   exchanged between the response lanes; an idle lane (k >= K) writes nothing and adds nothing.
 //   SP_LS_T_ALGRAD / SP_T: sp_epilogue on element r * K + k.
 template <class T, int KP, int MODE>
 __device__ __forceinline__ void spmm_epilogue(const SpEpi<T>& E, int K, int64_t r, double d, int k, bool lead, double (&acc)[1]) {
@@ -97,6 +108,8 @@ __device__ __forceinline__ void spmm_epilogue(const SpEpi<T>& E, int K, int64_t 
             if (E.out) E.out[r * K + k] = wv * (ev / S - (mine ? T(1) : T(0)));
             if (mine) acc[0] += (double)(wv * ((mx - t) + sp_log(S)));
         }
+    } else if constexpr (spmm_glm_mode(MODE)) {
+        if (lead && k < K) sp_epilogue<T, SP_GLM_MODE0 + (MODE - SPMM_GLM_MODE0)>(E, r * K + k, d, acc, r);
     } else {
         if (lead && k < K) sp_epilogue<T, MODE>(E, r * K + k, d, acc);
     }
@@ -131,6 +144,17 @@ __global__ void __launch_bounds__(BLOCK)
 k_spmm_softmax_r(SpMat<T> M, const T* __restrict__ x, int K, SpEpi<T> E, double* __restrict__ parts, int slot0) {
     double acc[1] = {0.0};
     spmm_rows<T, KP, L, NT, SPMM_SOFTMAX>(M, x, K, E, acc);
+    block_reduce_store<1>(acc, 0u, parts, slot0);
+}
+
+// rows of A_f, the multi-response GLM f with the loss MODE - SPMM_GLM_MODE0: r_ik = w_i l'(b_ik, t_ik) -> E.out (if kept) ;
+// partials: slot0 the terms w_i l(b_ik, t_ik)
+template <class T, int KP, int L, bool NT, int MODE>
+__global__ void __launch_bounds__(BLOCK)
+k_spmm_glm_r(SpMat<T> M, const T* __restrict__ x, int K, SpEpi<T> E, double* __restrict__ parts, int slot0) {
+    static_assert(spmm_glm_mode(MODE), "a K-wide GLM mode");
+    double acc[1] = {0.0};
+    spmm_rows<T, KP, L, NT, MODE>(M, x, K, E, acc);
     block_reduce_store<1>(acc, 0u, parts, slot0);
 }
 
@@ -177,13 +201,14 @@ k_spmm_fold(const double* __restrict__ part, const int32_t* __restrict__ crow, c
 
 // MODE -> the K-wide row kernel's entry point and its name, as sp_kernel and sp_kernel_name
 template <class T, int KP, int L, bool NT, int MODE> constexpr auto spmm_kernel() {
-    static_assert(MODE == SPMM_SOFTMAX || MODE == SP_LS_T_ALGRAD || MODE == SP_T, "a mode of the K-wide row loop");
+    static_assert(MODE == SPMM_SOFTMAX || spmm_glm_mode(MODE) || MODE == SP_LS_T_ALGRAD || MODE == SP_T, "a mode of the K-wide row loop");
     if constexpr (MODE == SPMM_SOFTMAX) return &k_spmm_softmax_r<T, KP, L, NT>;
+    else if constexpr (spmm_glm_mode(MODE)) return &k_spmm_glm_r<T, KP, L, NT, MODE>;
     else if constexpr (MODE == SP_LS_T_ALGRAD) return &k_spmm_t_algrad<T, KP, L, NT>;
     else return &k_spmm_t<T, KP, L, NT>;
 }
 constexpr const char* spmm_kernel_name(int MODE) {
-    return MODE == SPMM_SOFTMAX ? "k_spmm_softmax_r" : MODE == SP_LS_T_ALGRAD ? "k_spmm_t_algrad" : "k_spmm_t";
+    return MODE == SPMM_SOFTMAX ? "k_spmm_softmax_r" : spmm_glm_mode(MODE) ? "k_spmm_glm_r" : MODE == SP_LS_T_ALGRAD ? "k_spmm_t_algrad" : "k_spmm_t";
 }
 
 }  // namespace bz

@@ -87,9 +87,10 @@ __device__ __forceinline__ double sp_log1p(double v) { return log1p(v); }
 
 // (called by the row's first lane alone; every arm is written into this one body and none behind a call: the inlined form of a
 // helper gives the same instructions in another order, and the kernels are kept instruction for instruction.  The per-row
-// parameters are loaded once per row.)
+// parameters are loaded once per row.  `rw`: the row the weight is taken from where it is not r — the K-wide loss modes of
+// bz_spmm.h, whose element r = i * K + k of b and out shares row i's weight; every other caller leaves it out.)
 template <class T, int MODE>
-__device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double d, double (&acc)[sp_nacc<MODE>()]) {
+__device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double d, double (&acc)[sp_nacc<MODE>()], int64_t rw = -1) {
     const ElemParams<T>& P = E.P;
     if constexpr (MODE == SP_YUPD) {
         const T c = (T)d - E.b[r];                                  // eval!(cx, c, x)
@@ -120,8 +121,8 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
             dfx = e + qv;
             fterm = xv * (T(0.5) * e + qv);
         } else if (P.f_kind == BZ_F_SPARSE_LEAST_SQUARES || P.f_kind == BZ_F_SPARSE_LOGISTIC || P.f_kind == BZ_F_SPARSE_GLM ||
-                   P.f_kind == BZ_F_SPARSE_MULTINOMIAL) {
-            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r / k_spmv_logit_r / k_spmv_glm_r / k_spmm_softmax_r)
+                   P.f_kind == BZ_F_SPARSE_MULTINOMIAL || P.f_kind == BZ_F_SPARSE_MULTI_GLM) {
+            dfx = E.ext[r];                                             // (k_gemv_t_finish_ext, fext 1: f's value comes from k_spmv_ls_r / k_spmv_logit_r / k_spmv_glm_r / k_spmm_softmax_r / k_spmm_glm_r)
         }
         if (E.out) E.out[r] = dfx + (T)d;
         acc[0] += (double)fterm;
@@ -161,7 +162,7 @@ __device__ __forceinline__ void sp_epilogue(const SpEpi<T>& E, int64_t r, double
         constexpr bool W = MODE >= SP_GLM_MODE0;
         constexpr int LOSS = W ? MODE - SP_GLM_MODE0 : MODE == SP_LS_R ? BZ_LOSS_LEAST_SQUARES : BZ_LOSS_LOGISTIC;
         [[maybe_unused]] T wv = T(1);
-        if constexpr (W) wv = E.w ? E.w[r] : E.w_uniform;
+        if constexpr (W) wv = E.w ? E.w[rw >= 0 ? rw : r] : E.w_uniform;
         const T bv = E.b[r];
         const T t = (T)d;
         T loss, dl;

@@ -537,6 +537,95 @@ class SparseMultinomial(_CSR, _RowWeighted, ProximableFunction):
         return x.dtype.type(np.sum(loss))
 
 
+class SparseMultiGLM(_CSR, _RowWeighted, ProximableFunction):
+    """K independent row losses of one sparse design matrix: f(X) = sum_i w^_i sum_k l(B_ik, t_ik), T = A X, w^_i = scale * w_i;
+    A m-by-n_features in CSR (indptr[m + 1], indices[nnz] 0-based, data[nnz]), never densified; B is (m, K), K in 2 .. 64 (a
+    vector b is SparseGLM's).  Multi-response regression with "least_squares" (0.5 ||A X - B||_F^2; with NormL21(lam, group=K) the
+    multi-task Lasso), multi-label classification with "logistic" or "squared_hinge" and B in {-1, +1}.  X is n_features x K
+    ROW-MAJOR (response fastest), as SparseMultinomial has it: the variable is the flat vector x of length n = n_features * K with
+    x[j * K + k] = X[j, k] (`coef(x)` is that view).  `loss`, `delta`, `weights` and `scale` are SparseGLM's, with its formulas and
+    its checks applied to every entry of B; a weight belongs to a ROW and is shared by its K responses.  The gradient is A'R, laid
+    out as X is, with r_ik = w^_i dl/dt(B_ik, t_ik); the K responses of a row exchange nothing.  The matrix conventions of
+    SparseLeastSquares.  __call__ / gradient below are numpy with SparseGLM.loss_and_derivative on T in the dtype of x (the
+    generic-oracle protocol); on the device the kind is BZ_F_SPARSE_MULTI_GLM.  Every loss sees PANOCplus' step-size probe
+    x0 + 1, so the default PANOCplus() needs no gamma."""
+
+    LOSSES = SparseGLM.LOSSES
+
+    def __init__(self, indptr, indices, data, B, n_features, loss, delta=None, weights=None, scale=1.0):
+        bb = np.asarray(B)
+        self.n_features = int(n_features)
+        if loss not in self.LOSSES:
+            raise ValueError(f"unknown loss {loss!r}: one of {self.LOSSES}")
+        self.loss = loss
+        if bb.ndim == 1:
+            raise ValueError("B must be (m, K) with K >= 2 responses per row: a vector b is SparseGLM's")
+        if bb.ndim != 2:
+            raise ValueError("B must be two-dimensional, (m, K)")
+        self.n_classes = int(bb.shape[1])
+        if not 2 <= self.n_classes <= 64:
+            raise ValueError("B must have K in 2 .. 64 columns (K = 1 is SparseGLM)")
+        self._csr_types(indptr, indices, data, bb.reshape(-1), "B")
+        self.B = _real_array(bb, "B", self.data.dtype)
+        if loss in ("logistic", "squared_hinge") and not np.all(np.abs(self.B) == 1):
+            raise ValueError(f"labels must be -1 or +1 for the {loss} loss")
+        if loss == "poisson" and not np.all(np.isfinite(self.B) & (self.B >= 0)):
+            raise ValueError("counts must be finite and >= 0 for the poisson loss")
+        if loss == "huber":
+            if delta is None or not (np.isfinite(delta) and delta > 0):
+                raise ValueError("the huber loss needs delta finite and > 0")
+        elif delta is not None:
+            raise ValueError(f"delta is the huber loss's parameter, not the {loss} loss's")
+        self.delta = None if delta is None else float(delta)
+        self.m = self.B.shape[0]
+        self.n = self.n_features * self.n_classes
+        if self.n_features <= 0 or self.n > _I32_MAX or self.m <= 0 or self.m > _I32_MAX:
+            raise ValueError("n_features * K and the number of rows of B must be in 1 .. 2^31 - 1")
+        self._set_row_weights(weights, scale)
+        self._csr_shape(self.m, self.n_features, "m")
+
+    @property
+    def b(self):
+        """B as f_b holds it: the flat row-major vector, b[i * K + k] = B[i, k]"""
+        return self.B.reshape(-1)
+
+    @classmethod
+    def from_dense(cls, A, B, loss, **kw):
+        csr, n_features = cls._csr_of_dense(A, "A must be m-by-n_features")
+        return cls(*csr, B, n_features, loss, **kw)
+
+    @classmethod
+    def from_scipy(cls, M, B, loss, **kw):
+        csr, n_features = cls._csr_of_scipy(M)
+        return cls(*csr, B, n_features, loss, **kw)
+
+    def coef(self, x):
+        """the (n_features, K) view of the flat variable"""
+        return np.asarray(x).reshape(self.n_features, self.n_classes)
+
+    def _loss_r(self, x):
+        """the terms w^ l (least_squares: w^ v^2) and R = w^ l', both (m, K), in the dtype of x"""
+        X = self.coef(x)
+        t = np.stack([self._matvec(X[:, k]) for k in range(self.n_classes)], axis=1).astype(x.dtype, copy=False)
+        l, dl = SparseGLM.loss_and_derivative(self.loss, self.delta, self.B.astype(x.dtype, copy=False), t)
+        w = self.row_weights(x.dtype)
+        w = w[:, None] if np.ndim(w) else w
+        with np.errstate(over="ignore", invalid="ignore"):
+            return w * l, w * dl
+
+    def _value(self, terms, dt):
+        fx = dt(np.sum(terms))
+        return dt(0.5) * fx if self.loss == "least_squares" else fx
+
+    def __call__(self, x):
+        return self._value(self._loss_r(x)[0], x.dtype.type)
+
+    def gradient(self, dfx, x):
+        terms, r = self._loss_r(x)
+        dfx[...] = np.stack([self._rmatvec(r[:, k]) for k in range(self.n_classes)], axis=1).reshape(-1)
+        return self._value(terms, x.dtype.type)
+
+
 class Stencil5ptQuadratic(ProximableFunction):
     """f(x) = 0.5 x'A_h x - b'x on an nx-by-ny grid (row-major), A_h the 5-point Laplacian
     (4,-1,-1,-1,-1) with homogeneous Dirichlet halo — the structured `Quadratic` of BASELINE
@@ -1105,6 +1194,7 @@ _SPARSE_F = {
     SparseLogistic: (L.BZ_F_SPARSE_LOGISTIC, "A must have {n} columns", "labels"),
     SparseGLM: (L.BZ_F_SPARSE_GLM, "A must have {n} columns", "b"),
     SparseMultinomial: (L.BZ_F_SPARSE_MULTINOMIAL, "x must have n_features * n_classes = {fn} elements, not {n}", "labels"),
+    SparseMultiGLM: (L.BZ_F_SPARSE_MULTI_GLM, "x must have n_features * K = {fn} elements, not {n}", "B"),
 }
 
 _LOWERED_F = lambda f: isinstance(f, (Zero, DiagQuadratic, LeastSquares, Quadratic, *_SPARSE_F, Stencil5ptQuadratic))
@@ -1235,13 +1325,13 @@ def lower(f, g, c, D, n, ny, dtype, slack=False):
             d.f_b = ptr(_vec(f.q, dtype, n, name))
             return
         d.f_rows = f.m
-        d.f_b = ptr(_vec(f.b, dtype, f.m, name))
+        d.f_b = ptr(_vec(f.b, dtype, f.m * (f.n_classes if cls is SparseMultiGLM else 1), name))     # (B: m rows of K, row-major)
         delta, finite = None, "scale and scale * weights"          # what must be finite in dtype
-        if cls is SparseGLM:
+        if cls in (SparseGLM, SparseMultiGLM):
             d.f_loss = SparseGLM.LOSSES.index(f.loss)
             d.f_loss_delta = 0.0 if f.delta is None else f.delta
             delta, finite = f.delta, "scale, scale * weights and delta"
-        elif cls is SparseMultinomial:
+        if cls in (SparseMultinomial, SparseMultiGLM):
             d.f_classes = f.n_classes
         if isinstance(f, _RowWeighted):
             d.f_scale = f.scale

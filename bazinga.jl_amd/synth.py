@@ -259,6 +259,49 @@ def sparse_multinomial(m: int, n_f: int, K: int, k: int = 5, dtype=np.float64, s
             "labels": labels.astype(dtype), "m": m, "n_f": n_f, "K": K, "n": n_f * K, "xstar": X.reshape(-1).astype(dtype)}
 
 
+def sparse_multiresponse(m: int, n_f: int, K: int, per_row: int = 5, dtype=np.float64, loss: str = "least_squares", seed: int = SEED):
+    """Sparse multi-response regression / multi-label classification: min sum_i sum_k l(B_ik, t_ik) + g(X), T = A X, with the
+    matrix of sparse_multinomial(m, n_f, K, per_row, dtype, seed) — sparse_lasso's — and a ROW-sparse planted X* (n_f x K,
+    row-major): max(1, n_f div 10) features, those of the smallest keys u5, are active in all K responses, every entry there
+    (1 + u6) of random sign (u7), drawn for the K responses of a row in a run; every other row of X* is zero.  With T* = A X*:
+    least_squares and huber (delta = 1): B = T* + 0.01 (2 u8 - 1) ; logistic and squared_hinge: B_ik = +1 if
+    T*_ik + 0.1 (2 u9 - 1) >= 0 else -1 ; poisson: the margins scaled into [-2, 2] (X* with them) and the counts by inverse CDF at
+    the rate exp(t~_ik), as sparse_glm draws them.  `B` is (m, K); `xstar` is the flat vector X*.reshape(-1)."""
+    if loss not in GLM_LOSSES:
+        raise ValueError(f"loss must be one of {GLM_LOSSES}")
+    if not 2 <= K <= 64:
+        raise ValueError("sparse_multiresponse needs 2 <= K <= 64")
+    if not 1 <= per_row <= n_f or m < 1:
+        raise ValueError("sparse_multiresponse needs m >= 1 and 1 <= per_row <= n_f")
+    cols, data, _, _ = _sparse_rows(m, n_f, per_row, dtype, seed)
+    nz = max(1, n_f // 10)
+    support = np.argsort(uniform(5, n_f, seed=seed), kind="stable")[:nz]
+    X = np.zeros((n_f, K))
+    X[support] = ((1.0 + uniform(6, nz * K, seed=seed)) * np.where(uniform(7, nz * K, seed=seed) < 0.5, -1.0, 1.0)).reshape(nz, K)
+    t = (data.astype(np.float64).reshape(m, per_row, 1) * X[cols]).sum(axis=1)
+    delta = None
+    if loss in ("logistic", "squared_hinge"):
+        B = np.where(t + 0.1 * (2.0 * uniform(9, m * K, seed=seed).reshape(m, K) - 1.0) >= 0, 1.0, -1.0)
+    elif loss == "poisson":
+        top = float(np.max(np.abs(t)))
+        s = 2.0 / top if top > 0 else 1.0
+        X, rate = s * X, np.exp(s * t)
+        u = uniform(9, m * K, seed=seed).reshape(m, K)
+        B = np.zeros((m, K))
+        pmf = np.exp(-rate)
+        cdf = pmf.copy()
+        for c in range(1, 48):                       # (rate <= e^2: the tail beyond 47 is below 2^-53)
+            B[cdf < u] = c
+            pmf = pmf * rate / c
+            cdf += pmf
+    else:
+        B = t + 0.01 * (2.0 * uniform(8, m * K, seed=seed).reshape(m, K) - 1.0)
+        delta = 1.0 if loss == "huber" else None
+    return {"indptr": per_row * np.arange(m + 1, dtype=np.int64), "indices": cols.reshape(-1).astype(np.int32), "data": data,
+            "B": np.ascontiguousarray(B.astype(dtype)), "m": m, "n_f": n_f, "K": K, "n": n_f * K, "xstar": X.reshape(-1).astype(dtype),
+            "loss": loss, "delta": delta}
+
+
 def portfolio(n: int, dtype=np.float64, rank: int | None = None):
     """A stand-in for the absent demo/portfolio_data (demo/portfolio.jl:70-91: Q, rho, mu, ub), from the uniform stream:
 

@@ -114,7 +114,33 @@ extern "C" {
                                     Identity or SparseAffine, slack = 0, one rank, D Zero / Free / Box (and, with c = Identity,
                                     the pairwise sets); refused (BZ_ERR_UNSUPPORTED): slack = 1, c = DenseAffine, more than one
                                     rank, callbacks mixed in.                                                            */
-/* the row losses of BZ_F_SPARSE_GLM (f_loss), with v = t - b and u = b t                                   */
+#define BZ_F_SPARSE_MULTI_GLM 11 /* sum_i w^_i sum_k l(b_ik, t_ik), T = A X, w^_i = f_scale * w_i: K independent row losses of one
+                                    sparse design matrix A[f_rows][n_f] in CSR (f_sp_*), never densified — multi-response
+                                    regression (the least-squares loss: 0.5 ||A X - B||_F^2) and multi-label classification (the
+                                    logistic or squared-hinge loss, B in {+-1}).  K = f_classes responses, 2 <= K <= 64 (K = 1 is
+                                    BZ_F_SPARSE_GLM); X is n_f x K ROW-MAJOR (response fastest: x[j * K + k]), exactly as
+                                    BZ_F_SPARSE_MULTINOMIAL lays it out: the problem's n is n_f * K and the column indices lie in
+                                    [0, n / K).  B is f_rows x K ROW-MAJOR in f_b, in the problem's type: f_b[i * K + k].  l is
+                                    f_loss, one of the five BZ_LOSS_* with the definitions below; f_loss_delta is Huber's delta.
+                                    f_w[f_rows] (NULL: all ones) and f_scale are BZ_F_SPARSE_GLM's fields with its rules: w^_i the
+                                    product in double rounded once to the problem's type, one weight per ROW, shared by the row's
+                                    K responses.  The gradient is A'R, laid out as X is, with r_ik = w^_i dl/dt(b_ik, t_ik).  Per
+                                    (i, k), in the problem's type, BZ_F_SPARSE_GLM's operations in its order: ordered compares and
+                                    arithmetic alone, so a NaN in t_ik reaches r_ik and the value — and nothing else: the K
+                                    responses of a row exchange nothing, and an infinite or NaN t_ik leaves the row's other K - 1
+                                    entries of R as they are.  The term of (i, k) is w^_i * l, rounded in the problem's type; the
+                                    terms are summed in double.  The least-squares loss sums w^ v^2 and is halved once on the host.
+                                    An empty row has t = 0.  The matrix conventions of BZ_F_SPARSE_LEAST_SQUARES (unsorted and
+                                    repeated column indices, empty rows and columns, nnz = 0).  Limits: n = n_f K and f_rows
+                                    <= 2^31 - 1, nnz and every index into X, R and B (f_rows * K elements) 64-bit.  Checked at
+                                    bz_problem_create (BZ_ERR_ARG): K in range, n % K == 0, the column indices, f_rows > 0 and the
+                                    pointers, f_loss in range, f_loss_delta finite and > 0 for Huber, f_scale finite and > 0 (a
+                                    zeroed field is an error), every w_i finite and >= 0, each of them also as rounded to the
+                                    problem's type; labels and counts are the caller's contract.  c Identity or SparseAffine,
+                                    slack = 0, one rank, D Zero / Free / Box (and, with c = Identity, the pairwise sets); refused
+                                    (BZ_ERR_UNSUPPORTED): slack = 1, c = DenseAffine, more than one rank, callbacks mixed in.
+                                    With BZ_G_NORM_L21 and g_group = K: the multi-task Lasso.                               */
+/* the row losses of BZ_F_SPARSE_GLM and BZ_F_SPARSE_MULTI_GLM (f_loss), with v = t - b and u = b t       */
 #define BZ_LOSS_LEAST_SQUARES 0  /* l = v^2 / 2, l' = v                                                      */
 #define BZ_LOSS_LOGISTIC      1  /* b = +-1: BZ_F_SPARSE_LOGISTIC's l = softplus(-u), l' = -b sigma(-u)       */
 #define BZ_LOSS_HUBER         2  /* delta = f_loss_delta > 0: |v| <= delta: l = v^2 / 2, l' = v ; otherwise
@@ -292,7 +318,7 @@ typedef struct {
     const void* f_A;               /* LEAST_SQUARES: A[f_rows][n]; QUADRATIC: Q[n][n]; row-major;
                                       f_b then holds b[f_rows] resp. q[n]                */
     int64_t     f_rows;
-    int64_t     f_classes;         /* SPARSE_MULTINOMIAL alone: K, 2 <= K <= 64 (x is n / K rows of K); the other kinds ignore it */
+    int64_t     f_classes;         /* SPARSE_MULTINOMIAL and SPARSE_MULTI_GLM: K, 2 <= K <= 64 (x is n / K rows of K); the other kinds ignore it */
     /* g */
     double      g_lambda;          /* NORM_L1*, NORM_L0_BOX, NORM_L21, GROUP_LASSO: lambda >= 0; NORM_LP_*: alpha */
     double      g_p;               /* NORM_LP_*: exponent p in (0,1)                  */
@@ -332,12 +358,13 @@ typedef struct {
        f, SPARSE_LOGISTIC (with f_rows = m and the labels b[m] in f_b): A in CSR with m rows, as SPARSE_LEAST_SQUARES.
        f, SPARSE_GLM: A, f_rows and f_b as SPARSE_LEAST_SQUARES, and the four fields behind f_sp_nnz.
        f, SPARSE_MULTINOMIAL: A[f_rows][n / f_classes], the labels b[f_rows] in f_b, and f_w / f_scale of the GLM's four.
+       f, SPARSE_MULTI_GLM: A[f_rows][n / f_classes], B[f_rows][f_classes] row-major in f_b, and the GLM's four.
        (All of these sit in front of c_sp_*: the sparse constraint's fields stay the descriptor's last four.) */
     const int64_t* f_sp_rowptr;    /* rowptr[n + 1], rowptr[0] = 0, non-decreasing, rowptr[n] = nnz */
     const int32_t* f_sp_col;       /* col[nnz], 0-based, in [0, n)                    */
     const void*    f_sp_val;       /* val[nnz]                                        */
     int64_t        f_sp_nnz;
-    /* f, SPARSE_GLM alone (the other kinds ignore them) */
+    /* f, SPARSE_GLM and SPARSE_MULTI_GLM (SPARSE_MULTINOMIAL: f_w and f_scale; the other kinds ignore them) */
     int32_t        f_loss;         /* BZ_LOSS_*                                       */
     double         f_loss_delta;   /* BZ_LOSS_HUBER: delta, finite and > 0            */
     const void*    f_w;            /* w[f_rows] >= 0 in the problem's type, or NULL: no weights */

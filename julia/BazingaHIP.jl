@@ -28,7 +28,7 @@ Base.@kwdef mutable struct ProblemDesc
     n::Int64 = 0; ny::Int64 = 0
     f_q::Ptr{Cvoid} = C_NULL; f_b::Ptr{Cvoid} = C_NULL; f_grid_nx::Int64 = 0; f_grid_ny::Int64 = 0
     f_A::Ptr{Cvoid} = C_NULL; f_rows::Int64 = 0
-    f_classes::Int64 = 0                  # f = SparseMultinomial (BZ_F_SPARSE_MULTINOMIAL) alone: K, x is n / K rows of K
+    f_classes::Int64 = 0                  # f = SparseMultinomial / SparseMultiGLM (BZ_F_SPARSE_MULTINOMIAL, _MULTI_GLM): K, x is n / K rows of K
     g_lambda::Float64 = 0; g_p::Float64 = 0; g_group::Int64 = 0; g_u::Ptr{Cvoid} = C_NULL
     g_group_ptr::Ptr{Cvoid} = C_NULL; g_ngroups::Int64 = 0; g_l1::Float64 = 0   # g = GroupLasso (BZ_G_GROUP_LASSO) alone
     g_lo::Float64 = 0; g_hi::Float64 = 0
@@ -185,27 +185,67 @@ struct SparseGLM{T} <: Bazinga.ProximableFunction
                Int64.(At.colptr .- 1), Int32.(At.rowval .- 1), Vector{T}(At.nzval))
     end
 end
-function Bazinga.gradient!(dfx, f::SparseGLM{T}, x) where {T}
-    t = f.A * x; b = f.b
-    w = f.w === nothing ? T(f.scale) : T.(f.scale .* Float64.(f.w))
-    if f.loss == 0
+# the losses l(b, t) and l'(b, t) of loss code `loss` (BZ_LOSS_*), element by element on arrays of one shape (least squares: v^2,
+# halved on the sum): ordered compares and arithmetic alone
+function glm_terms(::Type{T}, loss, delta, b, t) where {T}
+    if loss == 0
         v = t .- b; l = v .* v; dl = v
-    elseif f.loss == 1
+    elseif loss == 1
         u = b .* t; e = exp.(.-abs.(u))
         l = ifelse.(u .< 0, .-u, zero(T)) .+ log1p.(e)
         dl = .-b .* ifelse.(u .>= 0, e ./ (one(T) .+ e), one(T) ./ (one(T) .+ e))
-    elseif f.loss == 2
-        v = t .- b; d = T(f.delta); a = ifelse.(v .< 0, .-v, v); inside = a .<= d
+    elseif loss == 2
+        v = t .- b; d = T(delta); a = ifelse.(v .< 0, .-v, v); inside = a .<= d
         l = ifelse.(inside, T(0.5) .* v .* v, d .* (a .- T(0.5) * d))
         dl = ifelse.(inside, v, ifelse.(v .> 0, d, ifelse.(v .< 0, -d, v)))
-    elseif f.loss == 3
+    elseif loss == 3
         h = one(T) .- b .* t; off = h .<= 0
         l = ifelse.(off, zero(T), T(0.5) .* h .* h); dl = ifelse.(off, zero(T), .-b .* h)
     else
         e = exp.(t); bt = ifelse.(b .== 0, zero(T), b .* t)
         l = ifelse.(e .< T(Inf), e .- bt, e); dl = e .- b
     end
+    return l, dl
+end
+function Bazinga.gradient!(dfx, f::SparseGLM{T}, x) where {T}
+    w = f.w === nothing ? T(f.scale) : T.(f.scale .* Float64.(f.w))
+    l, dl = glm_terms(T, f.loss, f.delta, f.b, f.A * x)
     dfx .= f.A' * (w .* dl)
+    return f.loss == 0 ? sum(w .* l) / 2 : sum(w .* l)
+end
+
+"""`SparseMultiGLM(A::SparseMatrixCSC, B::Matrix, loss; delta = 0, weights = nothing, scale = 1)`: K independent row losses of one
+sparse design matrix, f(X) = sum_i scale w_i sum_k l(B_ik, t_ik), T = A X, with A (m x n_f) never densified and B m x K,
+2 <= K <= 64 (a vector b is `SparseGLM`'s): multi-response regression with :least_squares (with `NormL21(lambda, K)` the multi-task
+Lasso), multi-label classification with :logistic or :squared_hinge and B in {-1, +1}.  `loss`, `delta`, `weights` (one per ROW,
+shared by its K responses) and `scale` are `SparseGLM`'s, checked here on every entry of B.  The variable is the flat vector x of
+length n_f K holding X ROW-MAJOR (response fastest), as `SparseMultinomial` has it; `coef(f, x)` gives X back.  The library takes
+B row-major too: `b` holds `vec(permutedims(B))`."""
+struct SparseMultiGLM{T} <: Bazinga.ProximableFunction
+    A::SparseMatrixCSC{T,Int}; B::Matrix{T}; b::Vector{T}; K::Int; loss::Int32; delta::Float64; w::Union{Nothing,Vector{T}}; scale::Float64
+    rowptr::Vector{Int64}; col::Vector{Int32}; val::Vector{T}
+    function SparseMultiGLM(A::SparseMatrixCSC{T}, B::Matrix{T}, loss::Symbol; delta = 0.0, weights = nothing, scale = 1.0) where {T}
+        code = findfirst(==(loss), (:least_squares, :logistic, :huber, :squared_hinge, :poisson))
+        code === nothing && throw(ArgumentError("unknown loss $loss"))
+        K = size(B, 2)
+        2 <= K <= 64 || throw(ArgumentError("B must have K in 2 .. 64 columns (K = 1 is SparseGLM)"))
+        size(B, 1) == size(A, 1) || throw(ArgumentError("one row of B per row of A"))
+        loss in (:logistic, :squared_hinge) && !all(v -> abs(v) == 1, B) && throw(ArgumentError("labels must be -1 or +1"))
+        loss == :poisson && !all(v -> isfinite(v) && v >= 0, B) && throw(ArgumentError("counts must be finite and >= 0"))
+        loss == :huber && !(isfinite(delta) && delta > 0) && throw(ArgumentError("the huber loss needs delta finite and > 0"))
+        (isfinite(scale) && scale > 0) || throw(ArgumentError("scale must be finite and > 0"))
+        weights === nothing || (length(weights) == size(B, 1) && all(v -> isfinite(v) && v >= 0, weights)) ||
+            throw(ArgumentError("weights must be finite and >= 0, one per row"))
+        At = sparse(A')
+        new{T}(A, B, vec(permutedims(B)), K, Int32(code - 1), Float64(delta), weights === nothing ? nothing : Vector{T}(weights),
+               Float64(scale), Int64.(At.colptr .- 1), Int32.(At.rowval .- 1), Vector{T}(At.nzval))
+    end
+end
+coef(f::SparseMultiGLM, x) = permutedims(reshape(x, f.K, size(f.A, 2)))
+function Bazinga.gradient!(dfx, f::SparseMultiGLM{T}, x) where {T}
+    w = f.w === nothing ? T(f.scale) : T.(f.scale .* Float64.(f.w))       # (a vector broadcasts over the K columns of a row)
+    l, dl = glm_terms(T, f.loss, f.delta, f.B, f.A * coef(f, x))
+    dfx .= vec(permutedims(f.A' * (w .* dl)))
     return f.loss == 0 ? sum(w .* l) / 2 : sum(w .* l)
 end
 
@@ -415,6 +455,13 @@ function lower_f!(d, f::SparseMultinomial)
     d.f_kind = 10; d.f_rows = length(f.b); d.f_classes = f.K; d.f_sp_rowptr = pointer(f.rowptr); d.f_sp_col = pointer(f.col)
     d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val); d.f_b = pointer(f.b)
     d.f_scale = f.scale
+    d.f_w = f.w === nothing ? C_NULL : pointer(f.w)
+    return nothing
+end
+function lower_f!(d, f::SparseMultiGLM)
+    d.f_kind = 11; d.f_rows = size(f.B, 1); d.f_classes = f.K; d.f_sp_rowptr = pointer(f.rowptr); d.f_sp_col = pointer(f.col)
+    d.f_sp_val = pointer(f.val); d.f_sp_nnz = length(f.val); d.f_b = pointer(f.b)        # (B row-major: f_rows * K values)
+    d.f_loss = f.loss; d.f_loss_delta = f.delta; d.f_scale = f.scale
     d.f_w = f.w === nothing ? C_NULL : pointer(f.w)
     return nothing
 end
